@@ -8,12 +8,14 @@ ray, shading, one shadow ray per lit pixel, sky) plus, for N > 1, the RCCL gathe
     python bench.py                      # 1 GPU, C3 workload (configs[2] of BASELINE.json)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line. Two measurements of the same frames stand behind `value`: the MEDIAN of --repeats timed blocks of exactly --steps
-frames each (a block is a few milliseconds), and one SUSTAINED block of --sustained-seconds of the same path (the reference's own harness
-samples for 20 s, benchmark-ingame.py:37); `value` is the burst median unless the sustained figure is more than 2 % below it, then the sustained
-one (`value_source` says which). `roofline.achieved` = algorithmic bytes per launch (step counters of the instrumented kernel variant x the
-byte model of DESIGN.md, averaged over the K views) / the render kernel's average duration, measured with HIP events on the stream it is launched
-on. `roofline.issue.clock_mhz_in_kernel` is sampled in THIS run (vx_clock_probe, while the sustained block renders). `configs` = the other
+Rank 0 prints ONE JSON line. A plain run sets up, warms up, times exactly --steps frames (one block), writes the last timed frame where
+--dump-outputs asks for it, and prints the line: `value` = the rays of those frames / their time, `ms_per_step` = that time / --steps.
+Everything below is --full (the line of a plain run has none of it): two measurements of the same frames stand behind `value`, the MEDIAN
+of --repeats timed blocks of exactly --steps frames each (a block is a few milliseconds), and one SUSTAINED block of --sustained-seconds of
+the same path (the reference's own harness samples for 20 s, benchmark-ingame.py:37); `value` is the burst median unless the sustained
+figure is more than 2 % below it, then the sustained one (`value_source` says which). `roofline.achieved` = algorithmic bytes per launch
+(step counters of the instrumented kernel variant x the byte model of DESIGN.md, averaged over the K views) / the render kernel's average
+duration, measured with HIP events on the stream it is launched on. `roofline.issue.clock_mhz_in_kernel` is sampled in THIS run (vx_clock_probe, while the sustained block renders). `configs` = the other
 BASELINE configurations (C2, C4 static and streamed, C5) on this GPU; `forced_sharded` = the N > 1 code path on this one GPU (a child process).
 `cpu_baseline` = the C oracle (restatement of the reference's GLSL; the reference has no CPU raycast) timed on this box's host cores over
 whole frames of the first view at 1 / 8 / 32 / all threads, with what the box grants this process (affinity, cgroup quota) stated.
@@ -113,6 +115,14 @@ def moving_uniforms(scenes, depth, h_max, W, H, i, shadows=True):
     return scenes.render_params_to_uniforms(eye, fwd, (0.0, 1.0, 0.0), math.radians(72.0), W / H, 0.3, (-1.0, -1.0, -1.0), shadows, 3.0e38)
 
 
+def counted_views(n, most):
+    """[(view, how many views of the path it is counted for)]: every one of the path's n views while n <= most, else `most` runs of consecutive
+    views, each counted on its middle view"""
+    m = max(1, min(n, most))
+    bounds = [j * n // m for j in range(m + 1)]
+    return [((a + b - 1) // 2, b - a) for a, b in zip(bounds, bounds[1:])]
+
+
 class Workload:
     """The scene (replicated per GPU: every rank builds and uploads the same serialized SVO), the camera's path and the work per frame of this rank."""
 
@@ -135,12 +145,18 @@ class Workload:
         # the K views of a timed block (every block walks the same path: its first view follows its last one, a cut)
         self.path = [moving_uniforms(scenes, args.depth, self.st["h_max"], W, H, i) for i in range(args.steps)]
         self.still = scenes.bench_camera(args.depth, self.st["h_max"], W, H, shadow_distance=3.0e38, render_shadows=True)
-        # work per frame: deterministic for a fixed scene / camera, counted by the instrumented kernel for this rank's tiles
-        self.counters = [self.svo.render_counters(u, W, H, rank, world_size) for u in self.path]
-        self.rays_per_block = sum(c["rays"] for c in self.counters)
-        self.iterations_per_block = sum(c["iterations"] for c in self.counters)
-        self.bytes_per_frame = sum(algorithmic_bytes(args.format, c) for c in self.counters) / len(self.counters)
-        self.image_bytes_per_frame = sum(image_model_bytes(c) for c in self.counters) / len(self.counters)
+        # work per frame: deterministic for a fixed scene / camera, counted by the instrumented kernel for this rank's tiles -- about a millisecond
+        # a view at 1920x1080, so at most --counted-views of them: a longer path is cut into that many runs of consecutive views, and the middle
+        # view of a run is counted for every view of it (the work per frame changes slowly along the path)
+        self.counters = [(self.svo.render_counters(self.path[i], W, H, rank, world_size), k) for i, k in counted_views(args.steps, args.counted_views)]
+
+        def per_block(f):
+            return sum(f(c) * k for c, k in self.counters)
+
+        self.rays_per_block = per_block(lambda c: c["rays"])
+        self.iterations_per_block = per_block(lambda c: c["iterations"])
+        self.bytes_per_frame = per_block(lambda c: algorithmic_bytes(args.format, c)) / args.steps
+        self.image_bytes_per_frame = per_block(image_model_bytes) / args.steps
 
 
 class SingleGpu:
@@ -165,6 +181,10 @@ class SingleGpu:
 
     def flush(self):
         pass
+
+    def last_frame(self):
+        """the image the last step rendered into (the caller drains the device first)"""
+        return self.images[(self.i - 1) % self.frames]
 
 
 class Sharded:
@@ -309,18 +329,21 @@ class Sharded:
         self.svo.sync()
         return img
 
+    def last_frame(self):
+        """rank 0: the frame the path delivered last (the caller drains the device first)"""
+        sh = self.sharder
+        if self.world_size > 1:
+            return sh.image
+        # one rank (--force-sharded): tile_count 1 means "the whole frame, row-major" to vx_render, so this rank's "tile list" is the
+        # frame itself and the assembly kernel (which runs for its cost) scatters something that is no tile list -- what the path
+        # delivered is what the gather delivered. (An RGBA8 frame is stored top row first, a tile list bottom row first: same here, the
+        # "list" IS the frame.)
+        return sh.last_gathered[0].reshape(-1)[:self.H * self.W * 4].view(self.H, self.W, 4)
+
     def frame_is_whole(self):
         """rank 0: what the path delivered last, against the same frame rendered whole on this GPU"""
-        sh = self.sharder
         whole = self.whole_frame(self.last_view)
-        if self.world_size > 1:
-            got = sh.image
-        else:
-            # one rank (--force-sharded): tile_count 1 means "the whole frame, row-major" to vx_render, so this rank's "tile list" is the
-            # frame itself and the assembly kernel (which runs for its cost) scatters something that is no tile list -- the check is
-            # on what the gather delivered. (An RGBA8 frame is stored top row first, a tile list bottom row first: same here, the
-            # "list" IS the frame.)
-            got = sh.last_gathered[0].reshape(-1)[:self.H * self.W * 4].view(self.H, self.W, 4)
+        got = self.last_frame()
         a, b = whole.contiguous().view(self.torch.uint8), got.contiguous().view(self.torch.uint8)
         return bool(self.torch.equal(a, b))
 
@@ -654,8 +677,8 @@ def forced_sharded_child(args):
     its own (a fresh context and process group; this process has finished its GPU work and waits): `bench.py --force-sharded` at the same sizes."""
     import subprocess
 
-    cmd = [sys.executable, str(Path(__file__).resolve()), "--force-sharded", "--no-cpu-baseline", "--no-extras", "--sustained-seconds", "0", "--steps", str(args.steps),
-           "--warmup", str(args.warmup), "--repeats", "9", "--depth", str(args.depth), "--width", str(args.width), "--height", str(args.height), "--format", args.format,
+    cmd = [sys.executable, str(Path(__file__).resolve()), "--full", "--force-sharded", "--no-cpu-baseline", "--no-extras", "--sustained-seconds", "0", "--steps", str(args.steps),
+           "--warmup", str(args.warmup), "--repeats", str(full_blocks(args.steps, 9)), "--depth", str(args.depth), "--width", str(args.width), "--height", str(args.height), "--format", args.format,
            "--textures", args.textures]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     try:
@@ -692,11 +715,42 @@ def picker_latency(wl, hip, np):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+FULL_FRAMES_PER_MEASUREMENT = 25000
+
+
+def full_blocks(steps, n):
+    """--full: n timed blocks of --steps frames for one of its measurements, fewer (never under 3) where --steps is so large that n blocks would
+    pass FULL_FRAMES_PER_MEASUREMENT frames"""
+    return max(3, min(n, FULL_FRAMES_PER_MEASUREMENT // max(steps, 1)))
+
+
+def dump_outputs(directory, frame):
+    """--dump-outputs: `frame` (H x W x 4 on the device) as DIR/image.npy in float32. A frame larger than DUMP_LIMIT_BYTES is written as a
+    fixed, seeded sample of its pixels: DIR/image_sample.npy (pixels x 4, float32) and their row-major indices, DIR/image_sample_index.npy
+    (float64)."""
+    import numpy as np
+
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    a = frame.detach().cpu().numpy().astype(np.float32)
+    if a.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(out / "image.npy", a)
+        return
+    px = a.reshape(-1, a.shape[-1])
+    k = DUMP_LIMIT_BYTES // (px.shape[1] * 4 + 8)
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], size=k, replace=False))
+    np.save(out / "image_sample.npy", px[idx])
+    np.save(out / "image_sample_index.npy", idx.astype(np.float64))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--repeats", type=int, default=25, help="the timed block of --steps frames is run this many times; the MEDIAN block is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="the timed block of --steps frames is run this many times; the MEDIAN block is reported (default: 1 in a plain run, 25 with --full "
+                         "-- fewer, at least 3, where that would pass 25,000 frames)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--depth", type=int, default=12)
     ap.add_argument("--width", type=int, default=1920)
@@ -734,7 +788,20 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="wall-clock target for the cpu_baseline sample on all threads (the sweep's other points: 3 s each)")
     ap.add_argument("--textures", choices=["assets", "procedural"], default="assets",
                     help="assets: the reference's own 64x64 textures (tests/golden/textures) for the blocks the terrain uses")
-    return ap.parse_args(argv)
+    ap.add_argument("--counted-views", type=int, default=10000,
+                    help="the views whose work (rays, iterations, bytes) the instrumented kernel counts before the warm-up, about a millisecond each: every "
+                         "view of the path up to this many; a longer path is cut into this many runs of consecutive views, each counted on its middle view")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: 25 timed blocks by default, the sustained block and its clock samples, the per-kernel event spans, the "
+                         "one-frame-at-a-time kernel runs (roofline), the secondary blocks, configs, forced_sharded, cpu_baseline and the sharded frame's check "
+                         "against the whole render. Without it a run sets up, warms up, times --steps frames and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed frames: the frame the last timed step rendered (what a caller of vx_render receives), as DIR/image.npy in float32 "
+                         "(RGBA8 frames as their byte values); a larger frame than 64 MB as a fixed, seeded sample of its pixels")
+    args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = full_blocks(args.steps, 25) if args.full else 1
+    return args
 
 
 def main():
@@ -743,7 +810,7 @@ def main():
     # mapped (a dozen streams = hardware queues) -- the child's frame streams were time-sliced and the figure was 7-10 % below what the same
     # command does on its own.
     args.forced_sharded_result = None
-    if (int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.force_sharded and not args.no_extras and not args.no_forced_sharded):
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.force_sharded and not args.no_extras and not args.no_forced_sharded:
         args.forced_sharded_result = forced_sharded_child(args)
     import numpy as np
     import torch
@@ -840,15 +907,18 @@ def main():
         barrier()
         calibration = {"chosen": best, "trials": trials, "note": "two untimed blocks per setting, slowest rank's time; outside the timed region"}
     # The timed block -- exactly --steps frames between two barriers -- is run --repeats times back to back and the MEDIAN block is
-    # what is reported: 50 frames are 25 ms of GPU time, too little for one sample to stand on.
-    svo.profile_enable(True)
-    run.profile_on = True
+    # what is reported (a plain run: once; --full: 25 times, with HIP events around every launch -- 50 frames are 25 ms of GPU time, too
+    # little for one sample to stand on).
+    svo.profile_enable(args.full)
+    run.profile_on = args.full
     blocks, enqueue = timed_blocks(args.repeats)
-    kernel_ms, launches = svo.profile_read()
-    gather_ms, gathers = run.exchange_profile() if sharded else (0.0, 0)
+    kernel_ms, launches = svo.profile_read() if args.full else (0.0, 0)
+    gather_ms, gathers = run.exchange_profile() if sharded and args.full else (0.0, 0)
     run.profile_on = False
     svo.profile_enable(False)
     enqueue_s = sorted(enqueue)[len(enqueue) // 2]
+    if args.dump_outputs and rank == 0:  # the last timed step's frame, before anything renders into it again
+        dump_outputs(args.dump_outputs, run.last_frame())
 
     # The sustained block: the same path, again and again, for --sustained-seconds without a pause -- what the device holds over seconds (clock,
     # power, temperature), which a 5 ms block cannot say. The host stays a few hundred frames ahead at most: every 100 frames an event is
@@ -856,7 +926,7 @@ def main():
     # when it passed -- frames completed against time, from which the first and the last second's rates are read. Meanwhile a second thread
     # samples the shader clock (vx_clock_probe: a one-lane kernel beside the render kernels).
     sustained, clock = None, None
-    if args.sustained_seconds > 0:
+    if args.full and args.sustained_seconds > 0:
         import threading
 
         probes, stop = [], threading.Event()
@@ -942,26 +1012,28 @@ def main():
         svo.profile_enable(False)
         return ms / max(k, 1), wall_ms
 
-    kernel_exclusive_frame_stream_ms, one_frame_wall_ms = exclusive(min(args.steps, 25))
-    kernel_exclusive_ms = kernel_exclusive_frame_stream_ms
-    if not sharded:
-        svo.set_frames_in_flight(1)
-        for _ in range(4):
-            run.step()
-        kernel_exclusive_ms, one_frame_wall_ms = exclusive(min(args.steps, 25))
-        svo.set_frames_in_flight(run.frames)
+    kernel_exclusive_frame_stream_ms, kernel_exclusive_ms, one_frame_wall_ms = 0.0, 0.0, None
+    if args.full:
+        kernel_exclusive_frame_stream_ms, one_frame_wall_ms = exclusive(min(args.steps, 25))
+        kernel_exclusive_ms = kernel_exclusive_frame_stream_ms
+        if not sharded:
+            svo.set_frames_in_flight(1)
+            for _ in range(4):
+                run.step()
+            kernel_exclusive_ms, one_frame_wall_ms = exclusive(min(args.steps, 25))
+            svo.set_frames_in_flight(run.frames)
 
     # Secondary blocks (one GPU): the camera standing still (round 3's headline: the same view again and again), the game's own shadow
     # cut-off (500 blocks, src/gamelogic/world.rs:105-108: from this altitude few or no hits are that near, so it is close to a
     # primary-rays-only frame; SURVEY.md 8d asks for both), the picker's latency.
     still, sd500, picker = None, None, None
-    if not sharded and not args.no_extras:
+    if args.full and not sharded and not args.no_extras:
         def view_block(u, repeats=9):
             rays = svo.render_counters(u, W, H, 0, 1)["rays"]
             run.view = u
             for _ in range(args.warmup):
                 run.step()
-            b, _ = timed_blocks(repeats)
+            b, _ = timed_blocks(full_blocks(args.steps, repeats))
             run.view = None
             ms = sorted(b)[len(b) // 2] / args.steps * 1e3
             return {"rays_per_frame": int(rays), "ms_per_step": round(ms, 4), "value": round(rays / (ms * 1e-3) / 1e6, 3), "unit": "Mrays/s"}
@@ -972,14 +1044,14 @@ def main():
         sd500.update({"shadow_distance": 500.0, "note": "the timed frames cast a shadow ray from every primary hit (shadow_distance = inf); this is the game's default cut-off, a still view"})
         picker = picker_latency(wl, hip, np)
     scale = None
-    if not sharded and not args.no_extras and rank == 0:
+    if args.full and not sharded and not args.no_extras and rank == 0:
         try:
             scale = scale_model(svo, hip, torch, wl.path, W, H, sorted(blocks)[len(blocks) // 2] / args.steps * 1e3)
         except Exception as e:
             scale = {"error": f"{type(e).__name__}: {e}"[:200]}
         svo.set_frames_in_flight(run.frames)
     configs, forced = None, None
-    if not sharded and not args.no_extras and rank == 0:
+    if args.full and not sharded and not args.no_extras and rank == 0:
         if not args.no_configs:
             try:
                 configs = other_configs(args, vra, hip, scenes, torch, [f for f in args.config_formats.split(",") if f in ("csvo", "esvo")], clock=clock)
@@ -1000,15 +1072,15 @@ def main():
         total_iterations_per_block = float(sm[5])
         every = [torch.zeros_like(stats) for _ in range(world_size)]
         dist.all_gather(every, stats)
-        per_rank = [{"rank": r, "rays_per_block": int(e[0]), "kernel_span_ms_in_flight": round(float(e[2]), 4), "kernel_exclusive_ms": round(float(e[3]), 4),
-                     "exchange_ms": round(float(e[4]), 4)} for r, e in enumerate(every)]
+        per_rank = [{"rank": r, "rays_per_block": int(e[0]), **({"kernel_span_ms_in_flight": round(float(e[2]), 4), "kernel_exclusive_ms": round(float(e[3]), 4),
+                     "exchange_ms": round(float(e[4]), 4)} if args.full else {})} for r, e in enumerate(every)]
     else:
         total_rays_per_block = float(wl.rays_per_block)
         total_iterations_per_block = float(wl.iterations_per_block)
     block_s = sorted(float(t) for t in times)
     elapsed = block_s[len(block_s) // 2]
     # sharded: the frame rank 0 assembled last against the same frame rendered whole on this GPU (outside the timed region)
-    sharded_frame_identical = run.frame_is_whole() if sharded and rank == 0 else None
+    sharded_frame_identical = run.frame_is_whole() if args.full and sharded and rank == 0 else None
     if rank != 0:
         if sharded and run.gather_used == "library":
             svo.comm_destroy()
@@ -1022,7 +1094,7 @@ def main():
     value = total_rays_per_block / elapsed / 1e6  # Mrays/s, whole job
     timed_region_s = sum(block_s) + (sustained["seconds"] if sustained else 0.0)  # every timed block and the sustained one: what `value` stands on
     burst = {"value": round(value, 3), "ms_per_step": round(ms_per_step, 4)}
-    value_source = f"median of {len(block_s)} timed blocks of {args.steps} frames"
+    value_source = f"median of {len(block_s)} timed blocks of {args.steps} frames" if len(block_s) > 1 else f"one timed block of {args.steps} frames"
     if sustained:
         # the same path's views in the same order: rays per frame as in the blocks. The sustained figure is the headline if it is more than 2 % lower.
         rays_per_frame_all = total_rays_per_block / args.steps
@@ -1079,9 +1151,11 @@ def main():
                      "instructions_per_launch": issue["instructions_per_launch"] if issue else None,
                      "wait_share_of_wave_cycles": issue["wait_share_of_wave_cycles"] if issue else None,
                      "valu_lane_utilisation": issue["valu_lane_utilisation"] if issue else None})
+    if not args.full:
+        roofline = None  # (its figures stand on the event spans and the kernel-alone runs: --full)
 
     cpu = None
-    if not args.no_cpu_baseline and world_size == 1:  # rank 0 at N = 1 only: a baseline of the workload, not of the scaling run
+    if args.full and not args.no_cpu_baseline and world_size == 1:  # rank 0 at N = 1 only: a baseline of the workload, not of the scaling run
         from oracle import oracle as orc  # the checker, timed here as the CPU baseline ("port": the reference has no CPU raycast)
 
         cpu = cpu_baseline(args, wl, orc)
@@ -1118,17 +1192,17 @@ def main():
                    **({"rccl_ranks": world_size, "gather": "vx_gather_tiles (grouped ncclSend/ncclRecv on the render context's own communicator)" if run.gather_used == "library"
                        else "torch.distributed.gather (nccl backend)", "gather_requested": args.gather, **({"gather_note": run.gather_note} if run.gather_note else {}),
                        "gather_format": args.gather_format, "bytes_gathered_per_frame": int((world_size - 1) * run.sharder.n_max * 1024 * (4 if args.gather_format == "rgba8" else 16)),
-                       "exchange_ms_per_gather_rank0": round(gather_ms / max(gathers, 1), 4), "per_rank": per_rank,
+                       "exchange_ms_per_gather_rank0": round(gather_ms / max(gathers, 1), 4) if args.full else None, "per_rank": per_rank,
                        "sharded_frame_identical_to_whole_render": sharded_frame_identical,
                        **({"calibration": calibration, "comm_headroom": calibration["chosen"]["comm_headroom"]} if calibration else {})} if sharded else {}),
-                   "scene_build_s": round(wl.build_s, 2), "upload_s": round(wl.upload_s, 3),
+                   "scene_build_s": round(wl.build_s, 2), "upload_s": round(wl.upload_s, 3), "counted_views": len(wl.counters),
                    "host_issue_ms_per_step": round(enqueue_s / args.steps * 1e3, 4),
                    # flat copies of what the nested objects say (`sustained`, `burst`, `configs`, `forced_sharded`)
                    "burst_value": burst["value"], "burst_ms_per_step": burst["ms_per_step"],
                    "sustained_value": sustained["value"] if sustained else None, "sustained_ms_per_step": sustained["ms_per_step"] if sustained else None,
                    "sustained_seconds": sustained["seconds"] if sustained else None, "sustained_frames": sustained["frames"] if sustained else None,
                    # every frame waited for before the next is issued, the host's wall clock per frame (kernel_exclusive_ms is the kernel's event span there)
-                   "one_frame_at_a_time_wall_ms": round(one_frame_wall_ms, 4),
+                   "one_frame_at_a_time_wall_ms": round(one_frame_wall_ms, 4) if one_frame_wall_ms is not None else None,
                    "forced_sharded_ms": forced.get("ms_per_step") if forced else None,
                    "forced_sharded_vs_plain": round(forced["value"] / burst["value"], 4) if forced and forced.get("value") else None,
                    **flat_configs,

@@ -1,6 +1,6 @@
 #!/bin/bash
 # a short A/B of the headline: bench.py without its secondary blocks, both formats; prints burst / sustained / exclusive ms per frame
-B="python3 bench.py --steps 20 --warmup 5 --repeats 15 --no-cpu-baseline --no-extras --sustained-seconds 2"
+B="python3 bench.py --full --steps 20 --warmup 5 --repeats 15 --no-cpu-baseline --no-extras --sustained-seconds 2"
 j() { python3 -c "
 import sys,json
 d=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1])

@@ -2,7 +2,7 @@
 # (the experiment of commit ebcb2fe, reverted by faed70b: run it on a checkout of ebcb2fe; results: r6_ab_eye.txt)
 # Primary rays on the eye's path (PersistentArgs::eye_*) against VX_EYE_PATH=0, same build: C3 (bench.py's headline without its secondary blocks) and C4
 # (deep_frames.py: a still 4K view of the depth-14 terrain, one / two frames in flight), both formats.
-B="python3 bench.py --steps 20 --warmup 5 --repeats 15 --no-cpu-baseline --no-extras --sustained-seconds 2"
+B="python3 bench.py --full --steps 20 --warmup 5 --repeats 15 --no-cpu-baseline --no-extras --sustained-seconds 2"
 j() { python3 -c "
 import sys,json
 d=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1])

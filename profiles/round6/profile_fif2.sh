@@ -9,7 +9,7 @@ tag=${2:-fif2}
 out=gpurun_out/prof_r6_${fmt}_${tag}
 mkdir -p "$out"
 export TMPDIR=/tmp
-args="--format $fmt --no-cpu-baseline --no-extras --steps 50 --warmup 10 --repeats 5 --sustained-seconds 0"
+args="--format $fmt --full --no-cpu-baseline --no-extras --steps 50 --warmup 10 --repeats 5 --sustained-seconds 0"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- python3 bench.py $args > "$out/trace.log" 2>&1
 python3 profiles/round6/fif2_blocks.py "$out" "$fmt" > "$out/summary.txt"
 cat "$out/summary.txt" | cut -c1-400 | tail -45

@@ -9,7 +9,7 @@ fmt=$1
 out=gpurun_out/prof_r6_$fmt
 mkdir -p "$out"
 export TMPDIR=/tmp
-args="--format $fmt --no-cpu-baseline --no-extras --frames-in-flight 1 --steps 50 --warmup 10 --repeats 3 --sustained-seconds 0"
+args="--format $fmt --full --no-cpu-baseline --no-extras --frames-in-flight 1 --steps 50 --warmup 10 --repeats 3 --sustained-seconds 0"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- python3 bench.py $args > "$out/trace.log" 2>&1
 i=0
 for pmc in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU" \

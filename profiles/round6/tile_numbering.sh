@@ -1,6 +1,6 @@
 #!/bin/bash
 # RenderParams::tile_numbering 1 (strips of eight columns, the default) against 2 (places a golden-ratio stride apart) at C3, C4 and C5's frame size.
-B="python3 bench.py --steps 20 --warmup 5 --repeats 15 --no-cpu-baseline --no-extras --sustained-seconds 2"
+B="python3 bench.py --full --steps 20 --warmup 5 --repeats 15 --no-cpu-baseline --no-extras --sustained-seconds 2"
 j() { python3 -c "
 import sys,json
 d=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1])

@@ -66,6 +66,47 @@ def test_granted_cpus_and_defaults():
     assert u.render_shadows == 1 and u.shadow_distance > 1e30
 
 
+def test_plain_run_and_full_defaults():
+    """A plain run times exactly --steps frames, once; --full keeps the 25 blocks unless --repeats says otherwise."""
+    a = bench.parse_args(["--steps", "40"])
+    assert a.full is False and a.repeats == 1 and a.steps == 40 and a.dump_outputs == ""
+    assert bench.parse_args(["--full"]).repeats == 25 and bench.parse_args(["--full", "--repeats", "9"]).repeats == 9
+    assert bench.parse_args(["--full", "--steps", "45000"]).repeats == 3 and bench.full_blocks(1000, 9) == 9
+
+
+def test_counted_views():
+    """Every view of the path is counted up to --counted-views; a longer path is counted on that many views, one in the middle of each run of
+    consecutive views, which together stand for every view once."""
+    assert bench.counted_views(7, 10000) == [(i, 1) for i in range(7)]
+    assert bench.counted_views(10, 4) == [(0, 2), (3, 3), (5, 2), (8, 3)]
+    for n, most in ((45000, 10000), (10001, 10000), (123457, 777)):
+        runs = bench.counted_views(n, most)
+        assert len(runs) == most and sum(k for _, k in runs) == n and all(0 <= i < n for i, _ in runs)
+        assert [i for i, _ in runs] == sorted({i for i, _ in runs}) and max(k for _, k in runs) - min(k for _, k in runs) <= 1
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: the frame as image.npy in float32 (RGBA8 as its byte values); past the size limit a seeded sample of its pixels and their
+    indices, the same sample every time."""
+    import numpy as np
+    import torch
+
+    frame = torch.arange(6 * 5 * 4, dtype=torch.float32).reshape(6, 5, 4)
+    bench.dump_outputs(tmp_path / "a", frame)
+    got = np.load(tmp_path / "a" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frame.numpy())
+    bench.dump_outputs(tmp_path / "b", frame.to(torch.uint8))
+    assert np.load(tmp_path / "b" / "image.npy").dtype == np.float32 and np.array_equal(np.load(tmp_path / "b" / "image.npy"), frame.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 10 * (4 * 4 + 8))
+    for d in ("c", "d"):
+        bench.dump_outputs(tmp_path / d, frame)
+    px, idx = np.load(tmp_path / "c" / "image_sample.npy"), np.load(tmp_path / "c" / "image_sample_index.npy")
+    assert px.dtype == np.float32 and px.shape == (10, 4) and idx.dtype == np.float64 and len(set(idx.tolist())) == 10
+    assert np.array_equal(px, frame.numpy().reshape(-1, 4)[idx.astype(np.int64)])
+    assert px.nbytes + idx.nbytes <= bench.DUMP_LIMIT_BYTES and not (tmp_path / "c" / "image.npy").exists()
+    assert np.array_equal(idx, np.load(tmp_path / "d" / "image_sample_index.npy"))
+
+
 def _scenes():
     from _pkg import load_package
 

@@ -66,7 +66,7 @@ def test_ranks_sharing_one_gpu_gather_the_whole_frame(tmp_path, world, fmt, gath
 
 
 def bench_ranks(world, extra):
-    argv = [str(ROOT / "bench.py"), "--gpus", str(world), "--steps", "10", "--warmup", "2", "--repeats", "3", "--sustained-seconds", "0.2", "--no-cpu-baseline", "--depth", "9",
+    argv = [str(ROOT / "bench.py"), "--full", "--gpus", str(world), "--steps", "10", "--warmup", "2", "--repeats", "3", "--sustained-seconds", "0.2", "--no-cpu-baseline", "--depth", "9",
             "--width", "640", "--height", "360", "--dist-backend", "gloo", "--comm-library", str(STUB), "--textures", "procedural"] + extra
     res = launch(world, argv)
     for r, (rc, _, err) in enumerate(res):

@@ -1,23 +1,23 @@
 """N4: the Rust a maintainer drops into the reference -- integration/rust/voxel_hip_sys.rs (raw FFI), svo_hip.rs (the
-public surface of graphics::Svo, /root/reference/src/graphics/svo.rs:56-256, over it) and worldsvo_updated_ranges.diff
-(WorldSvo::updated_ranges, /root/reference/src/world/hds/common.rs:3-15) -- cannot be compiled here (no rustc), so it is checked
+public surface of graphics::Svo, the reference's src/graphics/svo.rs:56-256, over it) and worldsvo_updated_ranges.diff
+(WorldSvo::updated_ranges, the reference's src/world/hds/common.rs:3-15) -- cannot be compiled here (no rustc), so it is checked
 against include/voxel_hip.h by parsing both: every constant, every #[repr(C)] struct (field names, order, widths, offsets, size) and
 every extern "C" function (name, arity, argument order, names, integer widths, pointer constness, return type) must agree; every call
-svo_hip.rs makes must pass the declared number of arguments; the patch must apply to the reference (checked when /root/reference is
-present: the build container)."""
+svo_hip.rs makes must pass the declared number of arguments; the patch must apply to the reference's files, as pinned by
+tests/golden/worldsvo_updated_ranges_base.json."""
+import hashlib
+import json
 import re
 import shutil
 import subprocess
 from pathlib import Path
-
-import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
 HEADER = ROOT / "include" / "voxel_hip.h"
 SYS = ROOT / "integration" / "rust" / "voxel_hip_sys.rs"
 WRAPPER = ROOT / "integration" / "rust" / "svo_hip.rs"
 PATCH = ROOT / "integration" / "rust" / "worldsvo_updated_ranges.diff"
-REFERENCE = Path("/root/reference")
+PATCH_BASE = ROOT / "tests" / "golden" / "worldsvo_updated_ranges_base.json"
 
 # C scalar -> (Rust spellings that are the same type on x86-64 Linux, size, alignment)
 C_SCALARS = {
@@ -284,17 +284,61 @@ def test_wrapper_calls_pass_the_declared_arguments():
         assert re.search(r"\b" + used + r"\s*\(", text), f"svo_hip.rs never calls {used}"
 
 
-@pytest.mark.skipif(not REFERENCE.is_dir() or shutil.which("patch") is None, reason="needs /root/reference (the build container) and patch(1)")
+def patch_hunks(text):
+    """{file: [(old_start, old_lines, pre-image lines, post-image lines)]} of a unified diff (context lines belong to both images). A hunk
+    ends where its header's line counts are used up."""
+    out, cur, hunk, left = {}, None, None, [0, 0]
+    for ln in text.splitlines():
+        if hunk is not None and (left[0] or left[1]):
+            tag, body = ln[:1] or " ", ln[1:]
+            if tag != "+":
+                hunk[2].append(body)
+                left[0] -= 1
+            if tag != "-":
+                hunk[3].append(body)
+                left[1] -= 1
+            continue
+        m = re.match(r"^\+\+\+ b/(\S+)", ln)
+        if m:
+            cur = out.setdefault(m.group(1), [])
+            continue
+        m = re.match(r"^@@ -(\d+),(\d+) \+(\d+),(\d+) @@", ln)
+        if m:
+            hunk, left = (int(m.group(1)), int(m.group(2)), [], []), [int(m.group(2)), int(m.group(4))]
+            cur.append(hunk)
+    return out
+
+
 def test_updated_ranges_patch_applies_to_the_reference(tmp_path):
-    """The patch names four files of src/world/hds; they are copied to a scratch tree (the reference is read-only) and the patch is
-    applied there for real, then the result is looked at: WorldSvo gained updated_ranges and both serializers implement it."""
-    files = sorted(set(re.findall(r"^\+\+\+ b/(\S+)", PATCH.read_text(), flags=re.M)))
-    assert files and all(f.startswith("src/world/hds/") for f in files)
-    for f in files:
+    """The patch must apply with no fuzz, at the lines it names, to the reference's files of src/world/hds. The reference is not part of this
+    repository: what those files hold there is pinned by tests/golden/worldsvo_updated_ranges_base.json (per file its length in lines, per hunk
+    the sha256 of the reference's lines the hunk covers). Every hunk's pre-image (context and removed lines) must hash to the recorded value;
+    then each file is rebuilt with those lines at their places and blank lines elsewhere, the patch is applied to the rebuilt tree for real
+    (patch(1), or the hunks at their exact places where patch(1) is not installed), and the result is looked at: WorldSvo gained
+    updated_ranges and both serializers implement it."""
+    base = json.loads(PATCH_BASE.read_text())["files"]
+    hunks = patch_hunks(PATCH.read_text())
+    assert hunks and sorted(hunks) == sorted(base) and all(f.startswith("src/world/hds/") for f in hunks)
+    for f, hs in hunks.items():
+        assert [(h[0], h[1]) for h in hs] == [(r["old_start"], r["old_lines"]) for r in base[f]["hunks"]], f
+        lines = [""] * base[f]["lines"]
+        for (start, n, pre, _), rec in zip(hs, base[f]["hunks"]):
+            assert len(pre) == n, f"{f} @@ -{start},{n}: the hunk has {len(pre)} pre-image lines"
+            assert hashlib.sha256(("\n".join(pre) + "\n").encode()).hexdigest() == rec["sha256"], f"{f} @@ -{start},{n}: not the reference's lines there"
+            assert start - 1 + n <= len(lines)
+            lines[start - 1:start - 1 + n] = pre
         (tmp_path / f).parent.mkdir(parents=True, exist_ok=True)
-        shutil.copy(REFERENCE / f, tmp_path / f)
-    r = subprocess.run(["patch", "-p1", "--forward", "--fuzz=0", "-i", str(PATCH)], cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
+        (tmp_path / f).write_text("\n".join(lines) + "\n")
+    if shutil.which("patch"):
+        r = subprocess.run(["patch", "-p1", "--forward", "--fuzz=0", "-i", str(PATCH)], cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        assert r.returncode == 0, r.stdout
+    else:
+        for f, hs in hunks.items():
+            lines = (tmp_path / f).read_text().split("\n")[:-1]
+            for start, n, pre, post in reversed(hs):
+                assert lines[start - 1:start - 1 + n] == pre, f
+                lines[start - 1:start - 1 + n] = post
+            (tmp_path / f).write_text("\n".join(lines) + "\n")
     assert "fn updated_ranges(&self) -> Vec<Range>;" in (tmp_path / "src/world/hds/common.rs").read_text()
     for f in ("src/world/hds/esvo.rs", "src/world/hds/csvo.rs"):
         assert "fn updated_ranges(&self) -> Vec<Range>" in (tmp_path / f).read_text(), f

@@ -101,6 +101,27 @@ typedef struct vx_picker_result {
     float normal[3], _pad2;
 } vx_picker_result;
 
+/* An entity as systems::Physics steps it (src/systems/physics.rs:10-75: the fields Physics::update_entity reads and writes,
+ * physics.rs:139-170); 64 bytes. Positions in SVO space like everything else here. */
+typedef struct vx_entity {
+    float position[3];
+    float velocity[3];
+    float aabb_offset[3];   /* AABBDef (physics.rs:77-87): the box spans position + offset .. position + offset + extents */
+    float aabb_extents[3];
+    float gravity, max_fall_velocity; /* EntityCapabilities (physics.rs:36-57) */
+    uint32_t flags;     /* bit0 wall_clip, bit1 flying */
+    uint32_t grounded;  /* out: EntityState::is_grounded (physics.rs:30-34) after the last step */
+} vx_entity;
+#define VX_ENTITY_WALL_CLIP 1
+#define VX_ENTITY_FLYING 2
+
+/* AabbResult (src/graphics/svo_picker.rs:163-176): shortest hit distance of a box's ray fan per axis, in negative and in positive
+ * direction, -1 = none; 24 bytes. */
+typedef struct vx_aabb_result {
+    float neg[3];
+    float pos[3];
+} vx_aabb_result;
+
 /* Optional per-pixel record of what trace_ray saw (world.glsl:27-90) -- the "hit position, depth" outputs
  * used for parity checks; not part of the reference's surface. */
 typedef struct vx_hit {
@@ -239,6 +260,23 @@ int vx_render(vx_context* ctx, const vx_uniforms* uniforms, uint32_t width, uint
 /* Svo::raycast (svo.rs:233-255) = picker.glsl over `count` tasks (no 100-task cap); synchronous like the
  * reference's fence wait (:248-249). Host pointers. */
 int vx_raycast(vx_context* ctx, const vx_picker_task* tasks, uint32_t count, vx_picker_result* results);
+/* Physics::step_many (src/systems/physics.rs:122-136) `steps` times over `count` entities in ONE kernel launch, against the world as last
+ * committed: per step and entity the AABB's fan of axis-parallel picker rays (Aabb::generate_picker_tasks, svo_picker.rs:183-243: max_dst
+ * 10), folded into six contact distances (parse_picker_results, svo_picker.rs:245-299), then Physics::update_entity and
+ * apply_axial_physics (physics.rs:139-185). One wave per entity; the entity stays in registers over all the steps and no task or result
+ * array crosses the boundary. Results are bit for bit what Physics::step_many over Svo::raycast gives (the same fp32 operations in the
+ * same order). steps <= 1024 and count <= 16777216 (2^24), else VX_ERR_INVALID_ARGUMENT; steps == 0 moves nothing and only fills `contacts`: a batched AABB distance query
+ * (PickerBatch::add_aabb, svo_picker.rs:57-59).
+ * `contacts` (optional, `count` records, the same memory kind as `entities`) receives the AabbResult each entity's last step was
+ * computed from (steps == 0: the fan at the current position).
+ * memory = VX_MEM_HOST: synchronous like Svo::raycast (svo.rs:248-249); the records travel through pinned memory the kernel reads and
+ * writes directly. VX_MEM_DEVICE: enqueued on the context's stream, returns after enqueueing; ordered like every other launch on that
+ * stream, behind the commits made so far; the fence is Fence::wait (src/graphics/fence.rs:8-42) for the whole context.
+ * An entity can be stepped when every extent is finite, > 0 and <= 8 (the reference divides by ceil(extent); the fan has
+ * (ceil(extent) + 1) points per axis). Host memory: a record that cannot makes the call return VX_ERR_INVALID_ARGUMENT, which names its
+ * index, with nothing changed. Device memory: the kernel leaves such a record's bytes as they are and writes -1 contacts for it. */
+int vx_physics_step(vx_context* ctx, vx_entity* entities, uint32_t count, int memory, float delta_time, uint32_t steps,
+                    vx_aabb_result* contacts);
 /* svo.test.glsl (assets/shaders/svo.test.glsl:63-76): one ray with a StackFrame per loop iteration.
  * n_frames receives the number of iterations (may exceed max_frames). Host pointers. */
 int vx_debug_trace(vx_context* ctx, const float pos[3], const float dir[3], float max_dst, int cast_translucent, vx_result* result,

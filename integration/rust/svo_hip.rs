@@ -187,6 +187,22 @@ impl Svo {
     }
 }
 
+impl Svo {
+    /// `Physics::step_many` (physics.rs:122-136) `steps` times on the device, in one launch and one wait: every entity's AABB fan is cast,
+    /// folded and applied by a wave of its own, and no `PickerTask` / `PickerResult` crosses the boundary. Bit for bit what
+    /// `Physics::step_many` over `raycast` gives. `contacts` (as long as `entities`) receives the `AabbResult` each entity's last step
+    /// was computed from; `steps == 0` only fills it (a batched `PickerBatch::add_aabb` query). Fill a `vx_entity` from an `Entity` with
+    /// `position`, `velocity`, `aabb_def.{offset, extents}`, `caps.{gravity, max_fall_velocity}` and `flags = wall_clip as u32 * VX_ENTITY_WALL_CLIP |
+    /// flying as u32 * VX_ENTITY_FLYING`; afterwards copy `position`, `velocity` back and set `state.is_grounded = grounded != 0`.
+    pub fn physics_step(&self, entities: &mut [vx_entity], delta_time: f32, steps: u32, contacts: Option<&mut [vx_aabb_result]>) {
+        let contacts = contacts.map_or(ptr::null_mut(), |c| {
+            assert!(c.len() >= entities.len());
+            c.as_mut_ptr()
+        });
+        check(unsafe { vx_physics_step(self.ctx, entities.as_mut_ptr(), entities.len() as u32, VX_MEM_HOST, delta_time, steps, contacts) });
+    }
+}
+
 impl Drop for Svo {
     fn drop(&mut self) {
         unsafe { vx_destroy(self.ctx) }

@@ -26,6 +26,8 @@ pub const VX_MEM_DEVICE: i32 = 1;
 pub const VX_FORMAT_RGBA32F: i32 = 0;
 pub const VX_FORMAT_RGBA8: i32 = 1;
 pub const VX_COMM_ID_BYTES: usize = 128;
+pub const VX_ENTITY_WALL_CLIP: u32 = 1; // vx_entity.flags: EntityCapabilities::wall_clip (physics.rs:39)
+pub const VX_ENTITY_FLYING: u32 = 2; // EntityCapabilities::flying (physics.rs:41)
 
 /// Opaque: replaces `struct Svo`'s GL objects (svo.rs:56-73).
 #[repr(C)]
@@ -70,6 +72,28 @@ pub struct vx_hit {
     pub steps: u32,
 }
 
+/// What `Physics::update_entity` reads and writes of an `Entity` (physics.rs:10-75, 138-170).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vx_entity {
+    pub position: [f32; 3],
+    pub velocity: [f32; 3],
+    pub aabb_offset: [f32; 3],
+    pub aabb_extents: [f32; 3],
+    pub gravity: f32,
+    pub max_fall_velocity: f32,
+    pub flags: u32,
+    pub grounded: u32,
+}
+
+/// `AabbResult` (svo_picker.rs:163-176): -1 = none.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vx_aabb_result {
+    pub neg: [f32; 3],
+    pub pos: [f32; 3],
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct vx_stats {
@@ -92,6 +116,8 @@ pub struct vx_target {
 const _: () = assert!(std::mem::size_of::<vx_range>() == 16);
 const _: () = assert!(std::mem::size_of::<vx_uniforms>() == 4 * (16 + 3 + 3 + 3 + 1 + 1 + 3));
 const _: () = assert!(std::mem::size_of::<vx_hit>() == 48);
+const _: () = assert!(std::mem::size_of::<vx_entity>() == 64);
+const _: () = assert!(std::mem::size_of::<vx_aabb_result>() == 24);
 const _: () = assert!(std::mem::size_of::<MaterialInstance>() == 32); // svo_registry.rs:29-40 is #[repr(C)]
 const _: () = assert!(std::mem::size_of::<PickerTask>() == 48 && std::mem::size_of::<PickerResult>() == 48); // svo_picker.rs:13-32
 
@@ -115,6 +141,9 @@ extern "C" {
     // ---- the hot path (Svo::render, Svo::raycast) ---------------------------------------------------------------------------
     pub fn vx_render(ctx: *mut vx_context, uniforms: *const vx_uniforms, width: u32, height: u32, target: *const vx_target) -> c_int;
     pub fn vx_raycast(ctx: *mut vx_context, tasks: *const PickerTask, count: u32, results: *mut PickerResult) -> c_int;
+    /// Physics::step_many (physics.rs:122-136) `steps` times for `count` entities in one launch; `memory`: VX_MEM_HOST / VX_MEM_DEVICE
+    pub fn vx_physics_step(ctx: *mut vx_context, entities: *mut vx_entity, count: u32, memory: c_int, delta_time: f32, steps: u32,
+                           contacts: *mut vx_aabb_result) -> c_int;
     pub fn vx_sync(ctx: *mut vx_context) -> c_int;
     pub fn vx_set_frames_in_flight(ctx: *mut vx_context, frames: c_int) -> c_int;
     pub fn vx_wait_event(ctx: *mut vx_context, hip_event: *mut c_void) -> c_int;

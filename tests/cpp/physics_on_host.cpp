@@ -1,0 +1,114 @@
+// TEST HARNESS ONLY: compiles the DEVICE physics header (voxel-rs_amd/csrc/physics/vx_physics.hpp) together with the device traversal
+// (voxel-rs_amd/csrc/hip/vx_device.hpp) for the host, with the shims of tests/cpp/device_on_host.cpp, so that the fan, the update and a
+// whole step can be checked against the host mirror and the oracle without a GPU. Never linked into the product libraries; the product
+// has no CPU path.
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#define __device__
+#define __host__
+#define __forceinline__ inline
+#define __constant__ static const
+#define __restrict__
+struct uint4 { uint32_t x, y, z, w; };
+struct float4 { float x, y, z, w; };
+static inline float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
+struct uint2 { uint32_t x, y; };
+static inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return uint4{x, y, z, w}; }
+static inline uint2 make_uint2(uint32_t x, uint32_t y) { return uint2{x, y}; }
+static inline uint32_t __popc(uint32_t v) { return uint32_t(__builtin_popcount(v)); }
+static inline int __clz(uint32_t v) { return v ? __builtin_clz(v) : 32; }
+static inline uint32_t __float_as_uint(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
+static inline int32_t __float_as_int(float f) { int32_t u; std::memcpy(&u, &f, 4); return u; }
+static inline float __uint_as_float(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
+static inline float __int_as_float(int32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
+#define HIP_INCLUDE_HIP_HIP_RUNTIME_H  // keep <hip/hip_runtime.h> out
+#define VX_DEVICE_ON_HOST 1
+#include "vx_physics.hpp"
+
+namespace vxd { unsigned char* vx_smem = nullptr; }
+
+using namespace vxd;
+using namespace vxp;
+
+extern "C" uint32_t physhost_sizes(void) { return uint32_t(sizeof(vx_entity)) << 16 | uint32_t(sizeof(vx_aabb_result)); }
+
+extern "C" int physhost_steppable(const vx_entity* e) { return steppable(*e) ? 1 : 0; }
+
+// The live slots of one entity's fan as picker tasks, in slot order: returns how many (fills `out` up to `max`); *slots = the fan's slots
+extern "C" uint32_t physhost_fan(const vx_entity* e, vx_picker_task* out, uint32_t max, uint32_t* slots) {
+    const Fan fan = make_fan(*e);
+    *slots = fan.slots;
+    uint32_t n = 0;
+    for (uint32_t s = 0; s < fan.slots + 64u; ++s) {  // (slots beyond the fan hold no ray)
+        float ro[3], rd[3];
+        int which;
+        if (!fan_ray(fan, *e, s, ro, rd, which)) continue;
+        if (n < max) {
+            vx_picker_task t;
+            std::memset(&t, 0, sizeof t);
+            t.max_dst = kFanMaxDst;
+            std::memcpy(t.pos, ro, 12);
+            std::memcpy(t.dir, rd, 12);
+            out[n] = t;
+        }
+        ++n;
+    }
+    return n;
+}
+
+extern "C" void physhost_update(float delta_time, vx_entity* entities, const vx_aabb_result* results, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i) update_entity(entities[i], results[i], delta_time);
+}
+
+// vx_physics_step as physics_kernel runs it, through the same helpers of vx_physics.hpp (rounds_of, lane_contacts, finish_round, write_back): only the
+// wave is played by a loop over 64 lanes and the cross-lane reduction by the same butterfly on an array. `contacts` (may be null) receives the last step's.
+extern "C" void physhost_step(int svo_type, const uint8_t* world, uint64_t world_bytes, const vx_material* mats, uint32_t n_mats, const uint8_t* tex,
+                              uint32_t tw, uint32_t th, uint32_t layers, uint32_t levels, const uint32_t* level_offset, vx_entity* entities, uint32_t n,
+                              float delta_time, uint32_t steps, vx_aabb_result* contacts) {
+    SceneArgs sa = {};
+    sa.world = world; sa.world_bytes = world_bytes; sa.materials = mats; sa.n_materials = n_mats;
+    sa.tex = tex; sa.tex_bytes = 0;
+    sa.width = tw; sa.height = th; sa.layers = layers; sa.levels = levels;
+    for (uint32_t l = 0; l < levels && l < 16; ++l) {
+        sa.level_offset[l] = level_offset[l];
+        const uint32_t w = (tw >> l) ? (tw >> l) : 1, h = (th >> l) ? (th >> l) : 1;
+        sa.tex_bytes = level_offset[l] + layers * w * h * 4;
+    }
+    const DevScene sc = make_scene(sa);
+    std::vector<unsigned char> lds(Stack<1>::kBytes + 64);
+    vx_smem = lds.data();
+    StackSpill spill;
+    Stack<1> st;
+    st.init(0, &spill);
+    for (uint32_t i = 0; i < n; ++i) {
+        vx_entity e = entities[i];
+        if (!steppable(e)) {
+            write_back_unsteppable(contacts, i);
+            continue;
+        }
+        const Fan fan = make_fan(e);
+        vx_aabb_result result = no_result();
+        for (uint32_t k = 0, rounds = rounds_of(steps); k < rounds; ++k) {
+            Contacts lanes[kLanes];
+            for (uint32_t lane = 0; lane < kLanes; ++lane)
+                lanes[lane] = svo_type == 1 ? lane_contacts<1>(sc, fan, e, lane, st) : lane_contacts<2>(sc, fan, e, lane, st);
+            for (uint32_t d = 32; d > 0; d >>= 1)  // the butterfly of the kernel's wave_min
+                for (uint32_t lane = 0; lane < kLanes; ++lane)
+                    if (!(lane & d))
+                        for (int m = 0; m < 6; ++m) {
+                            const float a = lanes[lane].m[m], b = lanes[lane ^ d].m[m];
+                            lanes[lane].m[m] = gmin(a, b);
+                            lanes[lane ^ d].m[m] = gmin(b, a);
+                        }
+            // every lane makes the identical update: lane 63's copy must end where lane 0's does
+            vx_entity e63 = e;
+            (void)finish_round(e63, lanes[63], delta_time, steps);
+            result = finish_round(e, lanes[0], delta_time, steps);
+            if (std::memcmp(&e, &e63, sizeof e) != 0) return;  // (leaves the remaining records unstepped: the comparison fails)
+        }
+        write_back(entities, contacts, i, e, result, steps);
+    }
+}

@@ -26,7 +26,13 @@ PICKER_RESULT_DTYPE = np.dtype([("dst", "<f4"), ("inside_voxel", "<u4"), ("_p0",
                                 ("_p2", "<f4")])
 FRAME_DTYPE = np.dtype([("t_min", "<f4"), ("ptr", "<u4"), ("idx", "<u4"), ("parent_octant_idx", "<u4"), ("scale", "<i4"), ("is_child", "<i4"),
                         ("is_leaf", "<i4"), ("crossed_boundary", "<i4"), ("next_ptr", "<u4")])
+# vx_entity / vx_aabb_result (src/systems/physics.rs:10-75, src/graphics/svo_picker.rs:163-176)
+ENTITY_DTYPE = np.dtype([("position", "<f4", 3), ("velocity", "<f4", 3), ("aabb_offset", "<f4", 3), ("aabb_extents", "<f4", 3), ("gravity", "<f4"),
+                         ("max_fall_velocity", "<f4"), ("flags", "<u4"), ("grounded", "<u4")])
+AABB_RESULT_DTYPE = np.dtype([("neg", "<f4", 3), ("pos", "<f4", 3)])
+ENTITY_WALL_CLIP, ENTITY_FLYING = 1, 2
 assert HIT_DTYPE.itemsize == 48 and PICKER_TASK_DTYPE.itemsize == 48 and PICKER_RESULT_DTYPE.itemsize == 48 and FRAME_DTYPE.itemsize == 36
+assert ENTITY_DTYPE.itemsize == 64 and AABB_RESULT_DTYPE.itemsize == 24
 
 COUNTER_FIELDS = ["rays", "iterations", "pushes", "leaf_tests", "leaf_tests_trilinear", "boundaries", "csvo_header_bytes", "csvo_pointer_bytes",
                   "pixels", "lit_pixels", "shadow_rays", "wave_steps", "services", "refills", "tail_wave_steps", "tail_iterations"]
@@ -78,6 +84,7 @@ SYMBOLS = {
     "vx_get_stats": (_int, [_vp, C.POINTER(Stats)]),
     "vx_render": (_int, [_vp, C.POINTER(Uniforms), _u32, _u32, C.POINTER(Target)]),
     "vx_raycast": (_int, [_vp, _vp, _u32, _vp]),
+    "vx_physics_step": (_int, [_vp, _vp, _u32, _int, C.c_float, _u32, _vp]),
     "vx_debug_trace": (_int, [_vp, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.c_float, _int, C.POINTER(Result), _vp, _u32, C.POINTER(_u32)]),
     "vx_sync": (_int, [_vp]),
     "vx_set_frames_in_flight": (_int, [_vp, _int]),
@@ -195,6 +202,35 @@ def traversal_image(svo_type, world_frame_words, used_bytes, layout=0, with_orig
     out = np.zeros(n, dtype=np.uint32)
     lib().vx_traversal_image(svo_type, f.ctypes.data_as(_vp), used_bytes, layout, out.ctypes.data_as(_vp), n)
     return (out, out) if with_origin else out
+
+
+def entities_from_rows(rows):
+    """host.py's entity rows (17 floats: position, velocity, aabb offset, aabb extents, wall_clip, flying, gravity, max_fall_velocity,
+    is_grounded) as vx_entity records."""
+    r = np.asarray(rows, dtype=np.float32).reshape(-1, 17)
+    e = np.zeros(len(r), dtype=ENTITY_DTYPE)
+    e["position"], e["velocity"], e["aabb_offset"], e["aabb_extents"] = r[:, 0:3], r[:, 3:6], r[:, 6:9], r[:, 9:12]
+    e["gravity"], e["max_fall_velocity"] = r[:, 14], r[:, 15]
+    e["flags"] = np.where(r[:, 12] != 0, ENTITY_WALL_CLIP, 0) | np.where(r[:, 13] != 0, ENTITY_FLYING, 0)
+    e["grounded"] = r[:, 16] != 0
+    return e
+
+
+def entities_to_rows(entities):
+    """vx_entity records as host.py's entity rows."""
+    e = np.asarray(entities, dtype=ENTITY_DTYPE).reshape(-1)
+    r = np.zeros((len(e), 17), dtype=np.float32)
+    r[:, 0:3], r[:, 3:6], r[:, 6:9], r[:, 9:12] = e["position"], e["velocity"], e["aabb_offset"], e["aabb_extents"]
+    r[:, 12] = (e["flags"] & ENTITY_WALL_CLIP) != 0
+    r[:, 13] = (e["flags"] & ENTITY_FLYING) != 0
+    r[:, 14], r[:, 15] = e["gravity"], e["max_fall_velocity"]
+    r[:, 16] = e["grounded"] != 0
+    return r
+
+
+def _device_ptr(x):
+    """A device pointer (int) or anything with data_ptr() (a torch CUDA tensor)."""
+    return int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x)
 
 
 class Svo:
@@ -358,6 +394,39 @@ class Svo:
         tasks = np.ascontiguousarray(tasks, dtype=PICKER_TASK_DTYPE)
         out = np.zeros(tasks.size, dtype=PICKER_RESULT_DTYPE)
         _check(lib().vx_raycast(self._h, tasks.ctypes.data_as(_vp), tasks.size, out.ctypes.data_as(_vp)))
+        return out
+
+    # -- Physics::step_many (src/systems/physics.rs:122-136), on the device ---------------------------------------
+    def physics_step(self, entities, dt, steps=1, want_contacts=False, count=None, contacts=None):
+        """vx_physics_step: `steps` fixed steps of `dt` for every entity in one launch.
+        Host: `entities` is a C-contiguous NumPy array of ENTITY_DTYPE, updated in place; synchronous; returns the contacts
+        (AABB_RESULT_DTYPE) when want_contacts, else None.
+        Device: `entities` is a torch CUDA tensor (its bytes are vx_entity records) or a raw device pointer with `count`; the call
+        returns after enqueueing -- pair with sync(). want_contacts: into `contacts` (a device tensor or pointer of count x 24 bytes)
+        or, for a tensor, into a fresh float32 tensor of shape (count, 6), which is returned."""
+        if isinstance(entities, np.ndarray):
+            if entities.dtype != ENTITY_DTYPE or not entities.flags.c_contiguous or not entities.flags.writeable:
+                raise TypeError("physics_step: host entities must be a writeable C-contiguous array of hip.ENTITY_DTYPE")
+            out = np.zeros(entities.size, dtype=AABB_RESULT_DTYPE) if want_contacts else None
+            _check(lib().vx_physics_step(self._h, entities.ctypes.data_as(_vp), entities.size, VX_MEM_HOST, float(dt), int(steps),
+                                         out.ctypes.data_as(_vp) if want_contacts else None))
+            return out
+        if count is None:
+            if not hasattr(entities, "numel"):
+                raise TypeError("physics_step: a raw device pointer needs count")
+            nbytes = entities.numel() * entities.element_size()
+            if nbytes % ENTITY_DTYPE.itemsize or not entities.is_contiguous():
+                raise TypeError("physics_step: a device tensor must be contiguous and hold whole 64-byte vx_entity records")
+            count = nbytes // ENTITY_DTYPE.itemsize
+        out = contacts
+        if want_contacts and out is None:
+            if not hasattr(entities, "new_empty"):
+                raise TypeError("physics_step: contacts of a raw device pointer need a `contacts` pointer")
+            import torch
+
+            out = torch.empty((count, 6), dtype=torch.float32, device=entities.device)
+        _check(lib().vx_physics_step(self._h, _vp(_device_ptr(entities)), count, VX_MEM_DEVICE, float(dt), int(steps),
+                                     _vp(_device_ptr(out)) if out is not None else None))
         return out
 
     def debug_trace(self, pos, direction, max_dst, cast_translucent, max_frames=100):

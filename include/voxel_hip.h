@@ -122,6 +122,30 @@ typedef struct vx_aabb_result {
     float pos[3];
 } vx_aabb_result;
 
+/* A batch of rays read where they already lie (vx_raycast_batch). Every pointer is in the memory kind given to the call. Strides are in
+ * bytes and are multiples of 4; a float[3] is read at origin + i*origin_stride (stride >= 12), at dir + i*dir_stride (stride >= 12, or
+ * 0 = one direction for every ray); max_dst: NULL = max_dst_all for every ray, else a float at max_dst + i*max_dst_stride (stride >= 4,
+ * or 0 = that one float for every ray). */
+typedef struct vx_ray_batch {
+    const void* origin;
+    const void* dir;
+    const void* max_dst;
+    uint32_t origin_stride, dir_stride, max_dst_stride;
+    float max_dst_all;
+    uint32_t flags;               /* VX_RAYS_TRANSLUCENT: intersect_octree's cast_translucent = true (picker.glsl passes false) */
+} vx_ray_batch;
+#define VX_RAYS_TRANSLUCENT 1
+
+/* What a ray of a batch found: PickerResult (svo_picker.rs:24-32) with the block id kept and the normal as its face; 32 bytes. */
+typedef struct vx_ray_hit {
+    float dst;                    /* -1 = no hit: every other field 0 then */
+    uint32_t value;               /* BlockId of the voxel hit (OctreeResult.value, svo.glsl:31-40) */
+    int32_t face_id;              /* 0..5 = -x,+x,-y,+y,-z,+z: the picker's normal is this face's */
+    uint32_t inside_voxel;
+    float pos[3];
+    uint32_t _pad;                /* written 0 */
+} vx_ray_hit;
+
 /* Optional per-pixel record of what trace_ray saw (world.glsl:27-90) -- the "hit position, depth" outputs
  * used for parity checks; not part of the reference's surface. */
 typedef struct vx_hit {
@@ -260,6 +284,21 @@ int vx_render(vx_context* ctx, const vx_uniforms* uniforms, uint32_t width, uint
 /* Svo::raycast (svo.rs:233-255) = picker.glsl over `count` tasks (no 100-task cap); synchronous like the
  * reference's fence wait (:248-249). Host pointers. */
 int vx_raycast(vx_context* ctx, const vx_picker_task* tasks, uint32_t count, vx_picker_result* results);
+/* Svo::raycast (svo.rs:233-255) = picker.glsl:30-51 for the plain rays of a batch (PickerBatch::add_ray, svo_picker.rs:53-55), read where
+ * they lie: `count` rays gathered through the strides of `rays` (packed [N,3] arrays, vx_picker_task or vx_entity records, one direction
+ * or one max_dst for all), `count` hits written to `hits`. A ray means what picker.glsl's task means and is not validated, like
+ * vx_raycast's; dst, inside_voxel and pos are bit for bit vx_raycast's, `value` is the block hit (what the reference asks the host world
+ * for after the cast: get_block(floor(pos)), gameplay.rs:161-201) and face_id names the normal. One ray a lane on the world's own bytes.
+ * memory = VX_MEM_HOST: synchronous like Svo::raycast (svo.rs:248-249): the rays are packed into pinned memory the kernel reads and the
+ * hits come back through it; one launch, one wait. VX_MEM_DEVICE: every pointer of `rays` and `hits` is device memory (`rays` itself is
+ * read on the host during the call); enqueued on the context's stream, returns after enqueueing, ordered like every other launch on that
+ * stream -- behind the commits made so far and behind an earlier vx_physics_step, whose vx_entity records it may read directly
+ * (origin = &entities[0].position, origin_stride = 64); later commits wait for it; the fence is vx_sync.
+ * `hits` must not overlap anything `rays` points to.
+ * VX_ERR_INVALID_ARGUMENT (its message names the field; nothing is written): a null ctx, or null rays / hits with count > 0; a null
+ * origin or dir; a stride that breaks the rules of vx_ray_batch; an unknown bit in flags; an unknown memory kind. count == 0: VX_OK.
+ * Before the first commit: VX_ERR_STATE. */
+int vx_raycast_batch(vx_context* ctx, const vx_ray_batch* rays, uint32_t count, int memory, vx_ray_hit* hits);
 /* Physics::step_many (src/systems/physics.rs:122-136) `steps` times over `count` entities in ONE kernel launch, against the world as last
  * committed: per step and entity the AABB's fan of axis-parallel picker rays (Aabb::generate_picker_tasks, svo_picker.rs:183-243: max_dst
  * 10), folded into six contact distances (parse_picker_results, svo_picker.rs:245-299), then Physics::update_entity and

@@ -203,6 +203,34 @@ impl Svo {
     }
 }
 
+impl Svo {
+    /// The plain rays of a `PickerBatch` (`add_ray`, svo_picker.rs:53-55) without `PickerTask`s around them: ray `i` starts at
+    /// `origins[i]`, runs along `dirs[i]` (or `dirs[0]` where `dirs.len() == 1`) for at most `max_dst` (`-1.0`: no limit), and
+    /// `hits[i]` says what it met -- `PickerResult`'s `dst`, `inside_voxel` and `pos` bit for bit, the face of its normal, and the
+    /// `BlockId` of the voxel, which `Gameplay::handle_voxel_placement` (gameplay.rs:161-201) otherwise asks the host world for.
+    /// Synchronous: one launch, one wait. `translucent`: `intersect_octree`'s `cast_translucent` (picker.glsl passes false).
+    pub fn raycast_batch(&self, origins: &[[f32; 3]], dirs: &[[f32; 3]], max_dst: f32, translucent: bool, hits: &mut [vx_ray_hit]) {
+        assert!(dirs.len() == origins.len() || dirs.len() == 1);
+        assert!(hits.len() >= origins.len());
+        let rays = vx_ray_batch {
+            origin: origins.as_ptr().cast(), dir: dirs.as_ptr().cast(), max_dst: ptr::null(),
+            origin_stride: 12, dir_stride: if dirs.len() == origins.len() { 12 } else { 0 }, max_dst_stride: 0,
+            max_dst_all: max_dst, flags: if translucent { VX_RAYS_TRANSLUCENT } else { 0 },
+        };
+        check(unsafe { vx_raycast_batch(self.ctx, &rays, origins.len() as u32, VX_MEM_HOST, hits.as_mut_ptr()) });
+    }
+
+    /// The raw device form: every pointer of `rays`, and `hits`, is device memory of this context's GPU -- e.g. the `vx_entity` records a
+    /// device-memory `vx_physics_step` just wrote (`origin` = the first record's `position`, `origin_stride` = 64). Returns after
+    /// enqueueing, ordered behind everything issued on this context before; `vx_sync` is the fence.
+    ///
+    /// # Safety
+    /// `rays` must describe `count` readable rays and `hits` `count` writable records in device memory, and the two must not overlap.
+    pub unsafe fn raycast_batch_device(&self, rays: &vx_ray_batch, count: u32, hits: *mut vx_ray_hit) {
+        check(vx_raycast_batch(self.ctx, rays, count, VX_MEM_DEVICE, hits));
+    }
+}
+
 impl Drop for Svo {
     fn drop(&mut self) {
         unsafe { vx_destroy(self.ctx) }

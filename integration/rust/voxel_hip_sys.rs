@@ -28,6 +28,7 @@ pub const VX_FORMAT_RGBA8: i32 = 1;
 pub const VX_COMM_ID_BYTES: usize = 128;
 pub const VX_ENTITY_WALL_CLIP: u32 = 1; // vx_entity.flags: EntityCapabilities::wall_clip (physics.rs:39)
 pub const VX_ENTITY_FLYING: u32 = 2; // EntityCapabilities::flying (physics.rs:41)
+pub const VX_RAYS_TRANSLUCENT: u32 = 1; // vx_ray_batch.flags: intersect_octree's cast_translucent (picker.glsl passes false)
 
 /// Opaque: replaces `struct Svo`'s GL objects (svo.rs:56-73).
 #[repr(C)]
@@ -94,6 +95,34 @@ pub struct vx_aabb_result {
     pub pos: [f32; 3],
 }
 
+/// A batch of rays read where they lie (`vx_raycast_batch`): byte strides, multiples of 4; `dir_stride == 0`: one direction for every
+/// ray; `max_dst` null: `max_dst_all` for every ray. Every pointer is in the memory kind given to the call.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct vx_ray_batch {
+    pub origin: *const c_void,
+    pub dir: *const c_void,
+    pub max_dst: *const c_void,
+    pub origin_stride: u32,
+    pub dir_stride: u32,
+    pub max_dst_stride: u32,
+    pub max_dst_all: f32,
+    pub flags: u32,
+}
+
+/// `PickerResult` (svo_picker.rs:24-32) with the block id kept and the normal as its face (0..5 = -x,+x,-y,+y,-z,+z); `dst == -1`: no
+/// hit, every other field 0.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct vx_ray_hit {
+    pub dst: f32,
+    pub value: u32,
+    pub face_id: i32,
+    pub inside_voxel: u32,
+    pub pos: [f32; 3],
+    pub _pad: u32,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct vx_stats {
@@ -118,6 +147,8 @@ const _: () = assert!(std::mem::size_of::<vx_uniforms>() == 4 * (16 + 3 + 3 + 3 
 const _: () = assert!(std::mem::size_of::<vx_hit>() == 48);
 const _: () = assert!(std::mem::size_of::<vx_entity>() == 64);
 const _: () = assert!(std::mem::size_of::<vx_aabb_result>() == 24);
+const _: () = assert!(std::mem::size_of::<vx_ray_batch>() == 48);
+const _: () = assert!(std::mem::size_of::<vx_ray_hit>() == 32);
 const _: () = assert!(std::mem::size_of::<MaterialInstance>() == 32); // svo_registry.rs:29-40 is #[repr(C)]
 const _: () = assert!(std::mem::size_of::<PickerTask>() == 48 && std::mem::size_of::<PickerResult>() == 48); // svo_picker.rs:13-32
 
@@ -141,6 +172,8 @@ extern "C" {
     // ---- the hot path (Svo::render, Svo::raycast) ---------------------------------------------------------------------------
     pub fn vx_render(ctx: *mut vx_context, uniforms: *const vx_uniforms, width: u32, height: u32, target: *const vx_target) -> c_int;
     pub fn vx_raycast(ctx: *mut vx_context, tasks: *const PickerTask, count: u32, results: *mut PickerResult) -> c_int;
+    /// picker.glsl for `count` plain rays (PickerBatch::add_ray) read through the strides of `rays`; `memory`: VX_MEM_HOST / VX_MEM_DEVICE
+    pub fn vx_raycast_batch(ctx: *mut vx_context, rays: *const vx_ray_batch, count: u32, memory: c_int, hits: *mut vx_ray_hit) -> c_int;
     /// Physics::step_many (physics.rs:122-136) `steps` times for `count` entities in one launch; `memory`: VX_MEM_HOST / VX_MEM_DEVICE
     pub fn vx_physics_step(ctx: *mut vx_context, entities: *mut vx_entity, count: u32, memory: c_int, delta_time: f32, steps: u32,
                            contacts: *mut vx_aabb_result) -> c_int;

@@ -1,0 +1,328 @@
+"""vx_raycast_batch on the GPU: ray batches read where they lie, in host or device memory, with block ids (voxel-rs_amd/csrc/raycast),
+against the path it stands beside -- vx_raycast over vx_picker_task records -- and against the oracle. Depth-7 heightfield, both formats;
+every comparison is byte for byte. One seeded set of 200 rays is shared by the tests and left unchanged."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from helpers import orc, vra  # noqa: F401
+from physics_cases import DT, heightfield, place_entities
+from voxel_rs_amd import hip, host
+
+pytestmark = pytest.mark.gpu
+_vp = C.c_void_p
+N_RAYS = 200
+
+
+class Case:
+    pass
+
+
+def unit(v):
+    v = np.asarray(v, dtype=np.float64)
+    return (v / np.linalg.norm(v)).astype(np.float32)
+
+
+def surface_under(scene, x, z, top):
+    """Where a downward oracle ray from (x, top, z) meets the ground."""
+    r, _, _ = scene.intersect(np.float32([x, top, z]), np.float32([0, -1, 0]), -1.0, False)
+    assert r.t > 0
+    return np.float32(r.pos)
+
+
+def build_rays(scene, h_max, seed=17):
+    """(origins [200,3], dirs [200,3], max_dst [200]) over the heightfield, shuffled: rays from the air towards the ground, rays from the
+    air towards the sky, origins a fraction of a block under the surface, rays whose max_dst ends them before their hit, and rays along
+    one axis or in one axis plane (one or two direction components exactly 0). max_dst = -1: no limit (the oracle's convention)."""
+    rng = np.random.default_rng(seed)
+    top = np.float32(h_max + 6.0)
+    o, d, m = [], [], []
+
+    def xz():
+        return rng.uniform(6.0, 122.0), rng.uniform(6.0, 122.0)
+
+    for _ in range(50):  # towards the ground
+        x, z = xz()
+        o.append([x, rng.uniform(h_max + 1.0, h_max + 8.0), z])
+        d.append(unit([rng.uniform(-1, 1), rng.uniform(-1.5, -0.3), rng.uniform(-1, 1)]))
+        m.append(-1.0 if rng.random() < 0.5 else 400.0)
+    for _ in range(50):  # towards the sky
+        x, z = xz()
+        o.append([x, rng.uniform(h_max + 1.0, h_max + 8.0), z])
+        d.append(unit([rng.uniform(-1, 1), rng.uniform(0.2, 1.5), rng.uniform(-1, 1)]))
+        m.append(-1.0 if rng.random() < 0.5 else 64.0)
+    for _ in range(25):  # from inside the ground
+        x, z = xz()
+        s = surface_under(scene, x, z, top)
+        o.append([s[0], s[1] - rng.uniform(0.1, 0.8), s[2]])
+        d.append(unit(rng.uniform(-1, 1, 3)))
+        m.append(-1.0)
+    for _ in range(25):  # ended by max_dst before the hit
+        x, z = xz()
+        p = np.float32([x, rng.uniform(h_max + 2.0, h_max + 8.0), z])
+        v = unit([rng.uniform(-0.5, 0.5), -1.0, rng.uniform(-0.5, 0.5)])
+        r, _, _ = scene.intersect(p, v, -1.0, False)
+        assert r.t > 1.0
+        o.append(p)
+        d.append(v)
+        m.append(r.t * rng.uniform(0.2, 0.9))
+    axes = [[0, -1, 0], [1, 0, 0], [0, 0, -1], [1, -1, 0], [0, -1, 1], [-1, -1, 0], [1, 0, 1], [0, 1, 0], [-1, 0, 0], [0, -2, -1]]
+    for k in range(50):  # one or two components exactly 0
+        x, z = xz()
+        s = surface_under(scene, x, z, top)
+        o.append([s[0], s[1] + rng.uniform(0.2, 3.0), s[2]])
+        d.append(unit(axes[k % len(axes)]))
+        m.append(-1.0 if k % 3 else 50.0)
+    order = rng.permutation(N_RAYS)
+    o, d, m = (np.ascontiguousarray(np.asarray(a, dtype=np.float32)[order]) for a in (o, d, m))
+    assert o.shape == (N_RAYS, 3) and d.shape == (N_RAYS, 3) and m.shape == (N_RAYS,)
+    return o, d, m
+
+
+def oracle_hits(scene, o, d, m, translucent=False):
+    """vx_ray_hit records by the oracle alone."""
+    out = np.zeros(len(o), dtype=hip.RAY_HIT_DTYPE)
+    for i in range(len(o)):
+        r, _, _ = scene.intersect(o[i], d[i], float(m[i]), translucent)
+        if r.t > 0:
+            out[i]["dst"], out[i]["value"], out[i]["face_id"], out[i]["inside_voxel"], out[i]["pos"] = r.t, r.value, r.face_id, r.inside_voxel != 0, list(r.pos)
+        else:
+            out[i]["dst"] = -1.0
+    return out
+
+
+def make_context(svo_type, world, tex, mats):
+    svo = hip.Svo(svo_type, world.size_in_bytes + (1 << 20))
+    svo.set_materials(mats)
+    svo.set_textures(tex, 6)
+    svo.update(world)
+    return svo
+
+
+@pytest.fixture(scope="module", params=[host.SVO_ESVO, host.SVO_CSVO], ids=["esvo", "csvo"])
+def case(request):
+    """The world, its oracle scene, a context that has it, the 200 rays and what the oracle says of them (computed once)."""
+    c = Case()
+    c.svo_type = request.param
+    c.world, c.scene, c.tex, c.mats, c.h_max = heightfield(c.svo_type, 7)
+    c.svo = make_context(c.svo_type, c.world, c.tex, c.mats)
+    c.o, c.d, c.m = build_rays(c.scene, c.h_max)
+    c.oracle = oracle_hits(c.scene, c.o, c.d, c.m)
+    for a in (c.o, c.d, c.m, c.oracle):
+        a.setflags(write=False)
+    yield c
+    c.svo.close()
+
+
+def tasks_of(o, d, m):
+    t = np.zeros(len(o), dtype=hip.PICKER_TASK_DTYPE)
+    t["pos"], t["dir"], t["max_dst"] = o, d, m
+    return t
+
+
+def assert_is_picker_result(hits, res):
+    """A vx_ray_hit says what the vx_picker_result of the same ray says."""
+    assert hits["dst"].tobytes() == res["dst"].tobytes()
+    assert hits["inside_voxel"].tobytes() == res["inside_voxel"].tobytes()
+    assert hits["pos"].tobytes() == res["pos"].tobytes()
+    hit = hits["dst"] > 0
+    assert ((hits["face_id"] >= 0) & (hits["face_id"] <= 5)).all()
+    normals = np.where(hit[:, None], hip.FACE_NORMALS[hits["face_id"]], np.float32(0))
+    assert (normals == res["normal"]).all()
+    miss = hits[~hit]
+    assert (miss["dst"] == -1).all() and not miss["value"].any() and not miss["face_id"].any() and not miss["inside_voxel"].any() and not miss["pos"].any()
+    assert not hits["_pad"].any()
+
+
+def to_device(array):
+    import torch
+
+    return torch.from_numpy(np.array(array, order="C")).cuda()  # (a copy: the shared arrays are read-only)
+
+
+def test_the_ray_set_holds_every_kind(case):
+    """The oracle alone: the shared rays hold hits, misses, origins inside voxels, rays cut short by max_dst and axis-parallel rays."""
+    hit = case.oracle["dst"] > 0
+    assert hit.sum() >= 40 and (~hit).sum() >= 40
+    assert (case.oracle["inside_voxel"] != 0).sum() >= 10
+    cut = 0
+    for i in np.flatnonzero(~hit & (case.m > 0)):
+        r, _, _ = case.scene.intersect(case.o[i], case.d[i], -1.0, False)
+        cut += r.t > case.m[i]
+    assert cut >= 10
+    zeros = (case.d == 0).sum(axis=1)
+    assert ((zeros == 1) | (zeros == 2)).sum() >= 10
+    assert len(np.unique(case.oracle["value"][hit])) >= 2 and len(np.unique(case.oracle["face_id"][hit])) >= 3
+
+
+@pytest.mark.parametrize("count", [1, 63, 64, 65, 200, 2112])
+def test_against_the_existing_path(case, count):
+    """1: host arrays through vx_raycast_batch against vx_raycast over the same rays as vx_picker_tasks. 2112 > vx_context::kPickerDirect
+    (2048) repeats the 200 rays, so that both of vx_raycast's routes -- pinned memory and DMA -- are the yardstick."""
+    idx = np.arange(count) % N_RAYS
+    o, d, m = (np.ascontiguousarray(a[idx]) for a in (case.o, case.d, case.m))
+    hits = case.svo.raycast_batch(o, d, m)
+    assert len(hits) == count
+    assert_is_picker_result(hits, case.svo.raycast(tasks_of(o, d, m)))
+    assert hits.tobytes() == case.oracle[idx].tobytes()
+
+
+def test_against_the_oracle(case):
+    """2: dst, value, face_id, inside_voxel and pos are the oracle's, with cast_translucent false and true. The synthetic materials hold
+    no translucent block, so the two casts agree (asserted on the oracle's side); VX_RAYS_TRANSLUCENT still runs a kernel of its own."""
+    hits = case.svo.raycast_batch(case.o, case.d, case.m)
+    assert hits.tobytes() == case.oracle.tobytes()
+    through = oracle_hits(case.scene, case.o, case.d, case.m, True)
+    assert through.tobytes() == case.oracle.tobytes()
+    assert case.svo.raycast_batch(case.o, case.d, case.m, translucent=True).tobytes() == through.tobytes()
+
+
+def test_strides_and_broadcasts(case):
+    """3: the same rays delivered five ways give the bytes of the plain packed call."""
+    svo, n = case.svo, N_RAYS
+    plain = svo.raycast_batch(case.o, case.d, case.m)  # [N,3] at stride 12, distances at stride 4
+    assert plain.tobytes() == case.oracle.tobytes()
+    o4, d4 = np.full((n, 4), 7.0, dtype=np.float32), np.full((n, 5), 7.0, dtype=np.float32)
+    o4[:, :3], d4[:, 1:4] = case.o, case.d
+    assert svo.raycast_batch(o4[:, :3], d4[:, 1:4], case.m).tobytes() == plain.tobytes()  # strides 16 and 20
+    t = tasks_of(case.o, case.d, case.m)
+    assert t["pos"].strides == (48, 4) and t["max_dst"].strides == (48,)
+    assert svo.raycast_batch(t["pos"], t["dir"], t["max_dst"]).tobytes() == plain.tobytes()  # inside vx_picker_task records
+    e = np.zeros(n, dtype=hip.ENTITY_DTYPE)
+    e["position"], e["velocity"] = case.o, 3.0
+    assert hip.entity_positions(e).strides == (64, 4)
+    assert svo.raycast_batch(hip.entity_positions(e), case.d, case.m).tobytes() == plain.tobytes()  # origins inside vx_entity records
+    # one direction and one distance for every ray
+    d0 = unit([0.3, -1.0, 0.2])
+    same = svo.raycast_batch(case.o, np.ascontiguousarray(np.tile(d0, (n, 1))), np.full(n, 8.0, dtype=np.float32))
+    assert svo.raycast_batch(case.o, d0, 8.0).tobytes() == same.tobytes()
+    assert svo.raycast_batch(case.o, d0, np.broadcast_to(np.float32(8.0), (n,))).tobytes() == same.tobytes()  # a distance array at stride 0
+    assert same.tobytes() == oracle_hits(case.scene, case.o, np.tile(d0, (n, 1)), np.full(n, 8.0)).tobytes()
+    assert (same["dst"] > 0).sum() >= 20 and (same["dst"] < 0).sum() >= 20
+    out = np.zeros(n, dtype=hip.RAY_HIT_DTYPE)
+    assert svo.raycast_batch(case.o, case.d, case.m, out=out) is out and out.tobytes() == plain.tobytes()
+
+
+@pytest.mark.parametrize("count", [1, 65, 200])
+def test_device_memory_equals_host_memory(case, count):
+    """4: the hit tensor is read only after vx_sync."""
+    import torch
+
+    o, d, m = case.o[:count], case.d[:count], case.m[:count]
+    exp = case.svo.raycast_batch(o, d, m)
+    hits = case.svo.raycast_batch(to_device(o), to_device(d), to_device(m))
+    d0 = unit([0.3, -1.0, 0.2])
+    one = case.svo.raycast_batch(to_device(o), to_device(d0), 8.0, out=torch.full((count, 8), -7, dtype=torch.int32, device="cuda"))
+    case.svo.sync()
+    assert tuple(hits.shape) == (count, 8)
+    assert hip.ray_hits_to_numpy(hits).tobytes() == exp.tobytes() == case.oracle[:count].tobytes()
+    assert hip.ray_hits_to_numpy(one).tobytes() == case.svo.raycast_batch(o, d0, 8.0).tobytes()
+
+
+def test_ordered_behind_a_physics_step(case):
+    """5a: vx_physics_step(VX_MEM_DEVICE, 8 steps) on 16 entities and, with no synchronisation in between, a batch that reads those
+    records' positions (stride 64) looking down: the hits are those of the stepped entities."""
+    svo = case.svo
+    rows = place_entities(case.scene, np.random.default_rng(5), 16, 8, 120, case.h_max)
+    start = hip.entities_from_rows(rows)
+    ents = to_device(start.view(np.uint8))
+    down = np.float32([0, -1, 0])
+    svo.physics_step(ents, DT, 8)
+    hits = svo.raycast_batch(hip.entity_positions(ents), to_device(down), 20.0)
+    svo.sync()
+    stepped = ents.cpu().numpy().view(hip.ENTITY_DTYPE)
+    assert (stepped["position"] != start["position"]).any(axis=1).all()  # everybody moved
+    exp = svo.raycast_batch(hip.entity_positions(stepped), down, 20.0)
+    assert hip.ray_hits_to_numpy(hits).tobytes() == exp.tobytes()
+    assert exp.tobytes() == oracle_hits(case.scene, stepped["position"], np.tile(down, (16, 1)), np.full(16, 20.0)).tobytes()
+    assert (exp["dst"] > 0).sum() >= 8
+    assert exp.tobytes() != svo.raycast_batch(hip.entity_positions(start), down, 20.0).tobytes()  # (a batch that ran first would say this)
+
+
+def test_a_world_change_between_batches(case):
+    """5b: a device batch, a commit that removes one column of the heightfield, the same batch again, one vx_sync: the first hits are of the
+    old world, the second of the new one, by the oracle's scenes of the two. On a world and a context of its own."""
+    world, scene_old, tex, mats, h_max = heightfield(case.svo_type, 7)
+    svo = make_context(case.svo_type, world, tex, mats)
+    try:
+        # a chunk column whose ground lies in the lowest chunk: 16 rays down over it, 16 over the column beside it
+        cx, cz = next((x, z) for x in range(1, 3) for z in range(1, 3)
+                      if all(surface_under(scene_old, 32 * x + fx, 32 * z + fz, h_max + 4.0)[1] < 31.0 for fx in (4, 16, 28) for fz in (4, 16, 28)))
+        rng = np.random.default_rng(9)
+        o = np.zeros((32, 3), dtype=np.float32)
+        o[:, 0], o[:, 1], o[:, 2] = 32 * cx + rng.uniform(3, 29, 32), h_max + 3.0, 32 * cz + rng.uniform(3, 29, 32)
+        o[16:, 0] -= 32.0
+        d = np.ascontiguousarray(np.tile(unit([0.05, -1.0, 0.02]), (32, 1)))
+        m = np.full(32, -1.0, dtype=np.float32)
+        d_o, d_d, d_m = to_device(o), to_device(d), to_device(m)
+        first = svo.raycast_batch(d_o, d_d, d_m)  # enqueued; the commit below has to wait for it on the device
+        chunk = vra.Chunk(cx, 0, cz, 5)
+        chunk.set_block(0, 0, 0, 1)  # (not quite empty)
+        chunk.compact()
+        world.set_chunk((cx, 0, cz), chunk)
+        world.serialize()
+        svo.update(world)
+        second = svo.raycast_batch(d_o, d_d, d_m)  # enqueued behind the commit's uploads
+        svo.sync()
+        scene_new = orc.OracleScene(case.svo_type, world.frame(), mats.view(orc.MATERIAL_DTYPE), tex, 6)
+        exp_old, exp_new = oracle_hits(scene_old, o, d, m), oracle_hits(scene_new, o, d, m)
+        assert (exp_old["dst"] > 0).all() and (exp_old[:16].tobytes() != exp_new[:16].tobytes()) and exp_old[16:].tobytes() == exp_new[16:].tobytes()
+        assert hip.ray_hits_to_numpy(first).tobytes() == exp_old.tobytes()
+        assert hip.ray_hits_to_numpy(second).tobytes() == exp_new.tobytes()
+    finally:
+        svo.close()
+
+
+def test_errors_leave_the_hits_alone(case):
+    """6: every invalid argument returns VX_ERR_INVALID_ARGUMENT with the field named and writes nothing; a context without a commit
+    returns VX_ERR_STATE. All of it is refused on the host, before any launch."""
+    L, h = hip.lib(), case.svo._h
+    o, d, m = case.o[:8].copy(), case.d[:8].copy(), case.m[:8].copy()
+    hits = np.full(8, 0x5a, dtype=np.uint8).repeat(32).view(hip.RAY_HIT_DTYPE)
+    sentinel = hits.tobytes()
+
+    def batch(**kw):
+        b = hip.RayBatch(o.ctypes.data, d.ctypes.data, m.ctypes.data, 12, 12, 4, -1.0, 0)
+        for k, v in kw.items():
+            setattr(b, k, v)
+        return b
+
+    def refused(ctx, rays, memory, out, word, count=8):
+        rc = L.vx_raycast_batch(ctx, C.byref(rays) if rays is not None else None, count, memory, out)
+        assert rc == 1 and word in L.vx_last_error(), (rc, word, L.vx_last_error())
+        assert hits.tobytes() == sentinel
+
+    out = hits.ctypes.data_as(_vp)
+    refused(None, batch(), hip.VX_MEM_HOST, out, b"null context")
+    refused(h, None, hip.VX_MEM_HOST, out, b"null rays")
+    refused(h, batch(), hip.VX_MEM_HOST, None, b"null hits")
+    refused(h, batch(origin=None), hip.VX_MEM_HOST, out, b"null origin")
+    refused(h, batch(dir=None), hip.VX_MEM_HOST, out, b"null dir")
+    for stride in (0, 8, 14):
+        refused(h, batch(origin_stride=stride), hip.VX_MEM_HOST, out, b"origin_stride")
+    for stride in (4, 8, 13):
+        refused(h, batch(dir_stride=stride), hip.VX_MEM_HOST, out, b"dir_stride")
+    for stride in (2, 6):
+        refused(h, batch(max_dst_stride=stride), hip.VX_MEM_HOST, out, b"max_dst_stride")
+    refused(h, batch(flags=2), hip.VX_MEM_HOST, out, b"flags")
+    refused(h, batch(flags=0x80000001), hip.VX_MEM_DEVICE, out, b"flags")
+    refused(h, batch(), 7, out, b"VX_MEM")
+    # what is allowed: no rays at all, and a stride nobody reads (no distance array)
+    assert L.vx_raycast_batch(h, C.byref(batch()), 0, hip.VX_MEM_HOST, None) == 0 and L.vx_raycast_batch(h, None, 0, hip.VX_MEM_HOST, None) == 0
+    assert L.vx_raycast_batch(h, C.byref(batch(max_dst=None, max_dst_stride=2, max_dst_all=30.0)), 8, hip.VX_MEM_HOST, out) == 0
+    assert hits.tobytes() == case.svo.raycast_batch(o, d, 30.0).tobytes()
+    # the binding refuses what it cannot describe to the library
+    with pytest.raises(TypeError):
+        case.svo.raycast_batch(o.astype(np.float64), d, m)
+    with pytest.raises(TypeError):
+        case.svo.raycast_batch(o, d[:5], m)
+    with pytest.raises(TypeError):
+        case.svo.raycast_batch(o, d[:, ::-1], m)
+    fresh = hip.Svo(case.svo_type, 1 << 20)
+    try:
+        hits[:] = np.full(8, 0x5a, dtype=np.uint8).repeat(32).view(hip.RAY_HIT_DTYPE)
+        assert L.vx_raycast_batch(fresh._h, C.byref(batch()), 8, hip.VX_MEM_HOST, out) == 6 and b"committed" in L.vx_last_error()
+        assert hits.tobytes() == sentinel
+    finally:
+        fresh.close()

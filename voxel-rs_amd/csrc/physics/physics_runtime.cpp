@@ -1,12 +1,13 @@
 // libvoxelhip.so, entity physics: vx_physics_step (include/voxel_hip.h) -- argument checks, the validation of host records, the pinned
-// scratch host records travel through, and the launch of kernels_physics.hip. A second translation unit on the context, like comm.cpp.
+// scratch host records travel through (csrc/vx_pinned_pool.hpp), and the launch of kernels_physics.hip. A second translation unit on the
+// context, like comm.cpp.
 #include <cstring>
-#include <map>
 #include <mutex>
 
 #include "kernels_physics.h"
 #include "vx_context.hpp"
 #include "vx_physics_rules.h"
+#include "vx_pinned_pool.hpp"
 
 using vxrt::fail;
 
@@ -37,44 +38,6 @@ int check_ready(vx_context* ctx) {
     return VX_OK;
 }
 
-// Host records travel through pinned memory the device sees: the kernel reads and writes it directly -- no copy commands, one launch, one
-// wait (runtime.cpp:1285-1288: a synchronous call costs its round trips). vx_context cannot grow, so the scratch is this file's: one
-// grow-only pool per device, shared by that device's contexts, whose mutex a host-memory call holds from its copy in to its copy out.
-// Kept for the life of the process.
-struct Pool {
-    std::mutex mutex;
-    uint8_t* host = nullptr;
-    uint8_t* dev = nullptr;
-    size_t bytes = 0;
-};
-std::mutex g_pools_mutex;
-std::map<int, Pool> g_pools;  // (node-based: a Pool's address is stable)
-
-Pool& pool_of(int device) {
-    std::lock_guard<std::mutex> lock(g_pools_mutex);
-    return g_pools[device];
-}
-
-int pool_reserve(Pool& p, size_t need) {
-    if (p.bytes >= need) return VX_OK;
-    if (p.host) (void)hipHostFree(p.host);  // (nobody's kernel reads it: every use is synchronous, under the pool's mutex)
-    p.host = p.dev = nullptr;
-    p.bytes = 0;
-    size_t cap = size_t(64) << 10;
-    while (cap < need) cap *= 2;
-    void* h = nullptr;
-    HIP_TRY(hipHostMalloc(&h, cap, hipHostMallocMapped));
-    void* d = nullptr;
-    if (const hipError_t e = hipHostGetDevicePointer(&d, h, 0); e != hipSuccess) {
-        (void)hipHostFree(h);
-        HIP_TRY(e);
-    }
-    p.host = static_cast<uint8_t*>(h);
-    p.dev = static_cast<uint8_t*>(d);
-    p.bytes = cap;
-    return VX_OK;
-}
-
 }  // namespace
 
 int vx_physics_step(vx_context* ctx, vx_entity* entities, uint32_t count, int memory, float delta_time, uint32_t steps, vx_aabb_result* contacts) {
@@ -101,9 +64,9 @@ int vx_physics_step(vx_context* ctx, vx_entity* entities, uint32_t count, int me
         if (!vxp::steppable_extents(entities[i].aabb_extents))
             return fail(VX_ERR_INVALID_ARGUMENT, "physics_step: entity " + std::to_string(i) + " cannot be stepped: every extent must be finite, > 0 and <= 8");
     const size_t entity_bytes = size_t(count) * sizeof(vx_entity), contact_bytes = contacts ? size_t(count) * sizeof(vx_aabb_result) : 0;
-    Pool& pool = pool_of(ctx->device);
+    vxrt::PinnedPool& pool = vxrt::pinned_pool_of(ctx->device);
     std::lock_guard<std::mutex> pool_lock(pool.mutex);
-    if (int rc = pool_reserve(pool, entity_bytes + contact_bytes)) return rc;
+    if (int rc = vxrt::pinned_pool_reserve(pool, entity_bytes + contact_bytes)) return rc;
     std::memcpy(pool.host, entities, entity_bytes);
     HIP_TRY(vxk::launch_physics(svo, ctx->stream, scene_of(ctx), reinterpret_cast<vx_entity*>(pool.dev), count, delta_time, steps,
                                 contacts ? reinterpret_cast<vx_aabb_result*>(pool.dev + entity_bytes) : nullptr));

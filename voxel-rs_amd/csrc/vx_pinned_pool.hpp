@@ -1,0 +1,52 @@
+// Pinned scratch for the synchronous, host-memory calls of the modules beside csrc/hip (csrc/physics, csrc/raycast): host records travel
+// through pinned memory the device sees, which the kernel reads and writes directly -- no copy commands, one launch, one wait
+// (runtime.cpp:1285-1288: a synchronous call costs its round trips). vx_context cannot grow, so the scratch lives here: one grow-only pool
+// per device, shared by that device's contexts and by the modules, whose mutex a host-memory call holds from its copy in to its copy out.
+// Kept for the life of the process.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <map>
+#include <mutex>
+
+#include "vx_context.hpp"
+
+namespace vxrt {
+
+struct PinnedPool {
+    std::mutex mutex;
+    uint8_t* host = nullptr;
+    uint8_t* dev = nullptr;
+    size_t bytes = 0;
+};
+
+inline PinnedPool& pinned_pool_of(int device) {
+    static std::mutex pools_mutex;
+    static std::map<int, PinnedPool> pools;  // (node-based: a pool's address is stable)
+    std::lock_guard<std::mutex> lock(pools_mutex);
+    return pools[device];
+}
+
+// at least `need` bytes, under the pool's mutex
+inline int pinned_pool_reserve(PinnedPool& p, size_t need) {
+    if (p.bytes >= need) return VX_OK;
+    if (p.host) (void)hipHostFree(p.host);  // (nobody's kernel reads it: every use is synchronous, under the pool's mutex)
+    p.host = p.dev = nullptr;
+    p.bytes = 0;
+    size_t cap = size_t(64) << 10;
+    while (cap < need) cap *= 2;
+    void* h = nullptr;
+    HIP_TRY(hipHostMalloc(&h, cap, hipHostMallocMapped));
+    void* d = nullptr;
+    if (const hipError_t e = hipHostGetDevicePointer(&d, h, 0); e != hipSuccess) {
+        (void)hipHostFree(h);
+        HIP_TRY(e);
+    }
+    p.host = static_cast<uint8_t*>(h);
+    p.dev = static_cast<uint8_t*>(d);
+    p.bytes = cap;
+    return VX_OK;
+}
+
+}  // namespace vxrt

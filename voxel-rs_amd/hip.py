@@ -31,8 +31,12 @@ ENTITY_DTYPE = np.dtype([("position", "<f4", 3), ("velocity", "<f4", 3), ("aabb_
                          ("max_fall_velocity", "<f4"), ("flags", "<u4"), ("grounded", "<u4")])
 AABB_RESULT_DTYPE = np.dtype([("neg", "<f4", 3), ("pos", "<f4", 3)])
 ENTITY_WALL_CLIP, ENTITY_FLYING = 1, 2
+# vx_ray_hit (vx_raycast_batch): a PickerResult that keeps the block id and names the normal by its face
+RAY_HIT_DTYPE = np.dtype([("dst", "<f4"), ("value", "<u4"), ("face_id", "<i4"), ("inside_voxel", "<u4"), ("pos", "<f4", 3), ("_pad", "<u4")])
+VX_RAYS_TRANSLUCENT = 1
+FACE_NORMALS = np.array([[-1, 0, 0], [1, 0, 0], [0, -1, 0], [0, 1, 0], [0, 0, -1], [0, 0, 1]], dtype=np.float32)  # by face_id
 assert HIT_DTYPE.itemsize == 48 and PICKER_TASK_DTYPE.itemsize == 48 and PICKER_RESULT_DTYPE.itemsize == 48 and FRAME_DTYPE.itemsize == 36
-assert ENTITY_DTYPE.itemsize == 64 and AABB_RESULT_DTYPE.itemsize == 24
+assert ENTITY_DTYPE.itemsize == 64 and AABB_RESULT_DTYPE.itemsize == 24 and RAY_HIT_DTYPE.itemsize == 32
 
 COUNTER_FIELDS = ["rays", "iterations", "pushes", "leaf_tests", "leaf_tests_trilinear", "boundaries", "csvo_header_bytes", "csvo_pointer_bytes",
                   "pixels", "lit_pixels", "shadow_rays", "wave_steps", "services", "refills", "tail_wave_steps", "tail_iterations"]
@@ -50,6 +54,12 @@ class Range(C.Structure):
 class Target(C.Structure):
     _fields_ = [("rgba32f", C.c_void_p), ("hits", C.c_void_p), ("memory", C.c_int32), ("tile_rank", C.c_uint32), ("tile_count", C.c_uint32),
                 ("format", C.c_int32)]
+
+
+class RayBatch(C.Structure):
+    """vx_ray_batch"""
+    _fields_ = [("origin", C.c_void_p), ("dir", C.c_void_p), ("max_dst", C.c_void_p), ("origin_stride", C.c_uint32), ("dir_stride", C.c_uint32),
+                ("max_dst_stride", C.c_uint32), ("max_dst_all", C.c_float), ("flags", C.c_uint32)]
 
 
 class Result(C.Structure):
@@ -84,6 +94,7 @@ SYMBOLS = {
     "vx_get_stats": (_int, [_vp, C.POINTER(Stats)]),
     "vx_render": (_int, [_vp, C.POINTER(Uniforms), _u32, _u32, C.POINTER(Target)]),
     "vx_raycast": (_int, [_vp, _vp, _u32, _vp]),
+    "vx_raycast_batch": (_int, [_vp, C.POINTER(RayBatch), _u32, _int, _vp]),
     "vx_physics_step": (_int, [_vp, _vp, _u32, _int, C.c_float, _u32, _vp]),
     "vx_debug_trace": (_int, [_vp, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.c_float, _int, C.POINTER(Result), _vp, _u32, C.POINTER(_u32)]),
     "vx_sync": (_int, [_vp]),
@@ -226,6 +237,48 @@ def entities_to_rows(entities):
     r[:, 14], r[:, 15] = e["gravity"], e["max_fall_velocity"]
     r[:, 16] = e["grounded"] != 0
     return r
+
+
+def entity_positions(entities):
+    """The positions inside vx_entity records as the origins of a ray batch (Svo.raycast_batch): an (N, 3) float32 view at a stride of 64
+    bytes -- of a NumPy array of ENTITY_DTYPE, or of a contiguous torch tensor whose bytes are vx_entity records. No copy."""
+    if isinstance(entities, np.ndarray):
+        if entities.dtype != ENTITY_DTYPE:
+            raise TypeError("entity_positions: a host array must be of hip.ENTITY_DTYPE")
+        return entities.reshape(-1)["position"]
+    import torch
+
+    nbytes = entities.numel() * entities.element_size()
+    if nbytes % ENTITY_DTYPE.itemsize or not entities.is_contiguous():
+        raise TypeError("entity_positions: a device tensor must be contiguous and hold whole 64-byte vx_entity records")
+    return entities.reshape(-1).view(torch.uint8).view(torch.float32).view(-1, 16)[:, 0:3]
+
+
+def ray_hits_to_numpy(hits):
+    """A device hit tensor of Svo.raycast_batch as RAY_HIT_DTYPE records (copies to the host: synchronise first)."""
+    return hits.cpu().numpy().view(np.uint8).reshape(-1).view(RAY_HIT_DTYPE)
+
+
+def _ray_vectors(name, x, count, width):
+    """(address, stride in bytes) of float32 vectors of `width` adjacent floats in a NumPy array or a torch tensor: `count` of them at the
+    array's own row stride (shape (count, width); (count,) for width 1), or -- width 3 -- a single one (shape (3,)) with stride 0."""
+    is_np = isinstance(x, np.ndarray)
+    if str(x.dtype) not in ("float32", "torch.float32"):
+        raise TypeError(f"raycast_batch: {name} must be float32")
+    shape = tuple(x.shape)
+    strides = tuple(x.strides) if is_np else tuple(4 * st for st in x.stride())
+    ptr = x.ctypes.data if is_np else x.data_ptr()
+    if width > 1 and shape[-1:] == (width,) and strides[-1] != 4:
+        raise TypeError(f"raycast_batch: the components of {name} must be adjacent floats")
+    if width > 1 and shape == (width,):
+        return ptr, 0
+    if shape != ((count, width) if width > 1 else (count,)):
+        raise TypeError(f"raycast_batch: {name} has shape {shape} for {count} rays")
+    if count <= 1:
+        return ptr, 4 * width  # (nobody steps by it)
+    if strides[0] < 0:
+        raise TypeError(f"raycast_batch: {name} has a negative stride")
+    return ptr, strides[0]
 
 
 def _device_ptr(x):
@@ -394,6 +447,45 @@ class Svo:
         tasks = np.ascontiguousarray(tasks, dtype=PICKER_TASK_DTYPE)
         out = np.zeros(tasks.size, dtype=PICKER_RESULT_DTYPE)
         _check(lib().vx_raycast(self._h, tasks.ctypes.data_as(_vp), tasks.size, out.ctypes.data_as(_vp)))
+        return out
+
+    def raycast_batch(self, origins, dirs, max_dst=-1.0, translucent=False, out=None):
+        """vx_raycast_batch: picker.glsl for rays read where they lie; hits keep the block id (RAY_HIT_DTYPE).
+        origins: (N, 3) float32, any row stride (a[:, :3] of an (N, 4) array, tasks["pos"], entity_positions(e)); dirs: (N, 3) or one (3,)
+        for every ray; max_dst: a number for every ray, or (N,) float32 at any stride (tasks["max_dst"]).
+        Host (NumPy arrays): synchronous; returns `out` or a fresh array of RAY_HIT_DTYPE.
+        Device (torch CUDA tensors): returns after enqueueing, without synchronising -- pair with sync(); the hits are `out` or a fresh
+        int32 tensor of shape (N, 8) on the rays' device, whose rows are vx_ray_hit records (ray_hits_to_numpy)."""
+        host = isinstance(origins, np.ndarray)
+        count = int(origins.shape[0]) if len(origins.shape) == 2 else -1
+        if count < 0 or origins.shape[1] != 3:
+            raise TypeError("raycast_batch: origins must have shape (N, 3)")
+        b = RayBatch()
+        per_ray = not isinstance(max_dst, (int, float, np.floating, np.integer))
+        arrays = [origins, dirs] + ([max_dst] if per_ray else [])
+        if any(isinstance(a, np.ndarray) != host for a in arrays) or (not host and not all(getattr(a, "is_cuda", False) for a in arrays)):
+            raise TypeError("raycast_batch: origins, dirs and max_dst must all be NumPy arrays or all be torch CUDA tensors")
+        b.origin, b.origin_stride = _ray_vectors("origins", origins, count, 3)
+        b.dir, b.dir_stride = _ray_vectors("dirs", dirs, count, 3)
+        if per_ray:
+            b.max_dst, b.max_dst_stride = _ray_vectors("max_dst", max_dst, count, 1)
+        else:
+            b.max_dst, b.max_dst_stride, b.max_dst_all = None, 0, float(max_dst)
+        b.flags = VX_RAYS_TRANSLUCENT if translucent else 0
+        if host:
+            if out is None:
+                out = np.zeros(count, dtype=RAY_HIT_DTYPE)
+            elif not isinstance(out, np.ndarray) or out.dtype != RAY_HIT_DTYPE or out.size != count or not out.flags.c_contiguous or not out.flags.writeable:
+                raise TypeError("raycast_batch: out must be a writeable C-contiguous array of N hip.RAY_HIT_DTYPE records")
+            _check(lib().vx_raycast_batch(self._h, C.byref(b), count, VX_MEM_HOST, out.ctypes.data_as(_vp)))
+            return out
+        import torch
+
+        if out is None:
+            out = torch.empty((count, 8), dtype=torch.int32, device=origins.device)
+        elif not out.is_cuda or not out.is_contiguous() or out.numel() * out.element_size() != count * RAY_HIT_DTYPE.itemsize:
+            raise TypeError("raycast_batch: out must be a contiguous CUDA tensor of N x 32 bytes")
+        _check(lib().vx_raycast_batch(self._h, C.byref(b), count, VX_MEM_DEVICE, _vp(out.data_ptr())))
         return out
 
     # -- Physics::step_many (src/systems/physics.rs:122-136), on the device ---------------------------------------

@@ -67,9 +67,9 @@ extern "C" int devhost_tile_numbering(uint32_t tiles_x, uint32_t tiles_y, uint32
 }
 using namespace vxd;
 
-extern "C" void devhost_picker(int svo_type, const uint8_t* world, uint64_t world_bytes, const vx_material* mats, uint32_t n_mats,
-                               const uint8_t* tex, uint32_t tw, uint32_t th, uint32_t layers, uint32_t levels, const uint32_t* level_offset,
-                               const vx_picker_task* tasks, uint32_t n, vx_picker_result* results, int cast_translucent) {
+// The arguments of the scene of a world's own bytes as the entries below are handed it (the caller keeps them alive: a DevScene points into them)
+static SceneArgs bytes_scene_args(const uint8_t* world, uint64_t world_bytes, const vx_material* mats, uint32_t n_mats, const uint8_t* tex, uint32_t tw, uint32_t th,
+                            uint32_t layers, uint32_t levels, const uint32_t* level_offset) {
     SceneArgs sa = {};
     sa.world = world; sa.world_bytes = uint32_t(world_bytes); sa.materials = mats; sa.n_materials = n_mats;
     sa.tex = tex; sa.tex_bytes = 0;
@@ -79,7 +79,12 @@ extern "C" void devhost_picker(int svo_type, const uint8_t* world, uint64_t worl
         const uint32_t w = (tw >> l) ? (tw >> l) : 1, h = (th >> l) ? (th >> l) : 1;
         sa.tex_bytes = level_offset[l] + layers * w * h * 4;
     }
-    const DevScene sc = make_scene(sa);
+    return sa;
+}
+
+// n rays through vxd::intersect on the world's own bytes, one lane's stack: record(i, result) receives each result
+template <class RECORD>
+static void cast_on_bytes(int svo_type, const DevScene& sc, uint32_t n, int cast_translucent, RECORD record) {
     std::vector<unsigned char> lds(Stack<1>::kBytes + 64);
     // Stack<1>::slot0 is "negative" (it is relative to scale 0 of a full-height plane): bias the base so that the sums land in lds
     vx_smem = lds.data();
@@ -87,19 +92,52 @@ extern "C" void devhost_picker(int svo_type, const uint8_t* world, uint64_t worl
     Stack<1> st;
     st.init(0, &spill);
     for (uint32_t i = 0; i < n; ++i) {
+        const float *pos, *dir;
+        float max_dst;
+        record(i, &pos, &dir, &max_dst, nullptr);
         Result res;
         uint32_t steps = 0;
-        if (svo_type == 1) intersect<1, false, false, true>(sc, tasks[i].pos, tasks[i].dir, tasks[i].max_dst, cast_translucent != 0, st, res, steps, nullptr, nullptr);
-        else intersect<2, false, false, true>(sc, tasks[i].pos, tasks[i].dir, tasks[i].max_dst, cast_translucent != 0, st, res, steps, nullptr, nullptr);
+        if (svo_type == 1) intersect<1, false, false, true>(sc, pos, dir, max_dst, cast_translucent != 0, st, res, steps, nullptr, nullptr);
+        else intersect<2, false, false, true>(sc, pos, dir, max_dst, cast_translucent != 0, st, res, steps, nullptr, nullptr);
+        record(i, nullptr, nullptr, nullptr, &res);
+    }
+}
+
+extern "C" void devhost_picker(int svo_type, const uint8_t* world, uint64_t world_bytes, const vx_material* mats, uint32_t n_mats,
+                               const uint8_t* tex, uint32_t tw, uint32_t th, uint32_t layers, uint32_t levels, const uint32_t* level_offset,
+                               const vx_picker_task* tasks, uint32_t n, vx_picker_result* results, int cast_translucent) {
+    const SceneArgs sa = bytes_scene_args(world, world_bytes, mats, n_mats, tex, tw, th, layers, levels, level_offset);
+    const DevScene sc = make_scene(sa);
+    cast_on_bytes(svo_type, sc, n, cast_translucent, [&](uint32_t i, const float** pos, const float** dir, float* max_dst, const Result* res) {
+        if (!res) { *pos = tasks[i].pos; *dir = tasks[i].dir; *max_dst = tasks[i].max_dst; return; }
         vx_picker_result r;
         std::memset(&r, 0, sizeof r);
-        if (res.t > 0.0f) {
-            r.dst = res.t; r.inside_voxel = res.inside_voxel;
-            std::memcpy(r.pos, res.pos, 12);
-            face_vector<0>(uint32_t(res.face_id), r.normal);
+        if (res->t > 0.0f) {
+            r.dst = res->t; r.inside_voxel = res->inside_voxel;
+            std::memcpy(r.pos, res->pos, 12);
+            face_vector<0>(uint32_t(res->face_id), r.normal);
         } else r.dst = -1.0f;
         results[i] = r;
-    }
+    });
+}
+
+// A batch of rays as raycast_batch_kernel (csrc/raycast/kernels_raycast.hip) casts and records them: packed origins and directions (3 floats a
+// ray), one max_dst a ray, vx_ray_hit records out -- the block id and the face id with them.
+extern "C" void devhost_ray_batch(int svo_type, const uint8_t* world, uint64_t world_bytes, const vx_material* mats, uint32_t n_mats,
+                                  const uint8_t* tex, uint32_t tw, uint32_t th, uint32_t layers, uint32_t levels, const uint32_t* level_offset,
+                                  const float* origins, const float* dirs, const float* max_dst, uint32_t n, int cast_translucent, vx_ray_hit* hits) {
+    const SceneArgs sa = bytes_scene_args(world, world_bytes, mats, n_mats, tex, tw, th, layers, levels, level_offset);
+    const DevScene sc = make_scene(sa);
+    cast_on_bytes(svo_type, sc, n, cast_translucent, [&](uint32_t i, const float** pos, const float** dir, float* limit, const Result* res) {
+        if (!res) { *pos = origins + 3 * i; *dir = dirs + 3 * i; *limit = max_dst[i]; return; }
+        vx_ray_hit r;
+        std::memset(&r, 0, sizeof r);
+        if (res->t > 0.0f) {
+            r.dst = res->t; r.value = res->value; r.face_id = res->face_id; r.inside_voxel = res->inside_voxel ? 1u : 0u;
+            std::memcpy(r.pos, res->pos, 12);
+        } else r.dst = -1.0f;
+        hits[i] = r;
+    });
 }
 
 

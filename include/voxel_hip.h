@@ -299,6 +299,31 @@ int vx_raycast(vx_context* ctx, const vx_picker_task* tasks, uint32_t count, vx_
  * origin or dir; a stride that breaks the rules of vx_ray_batch; an unknown bit in flags; an unknown memory kind. count == 0: VX_OK.
  * Before the first commit: VX_ERR_STATE. */
 int vx_raycast_batch(vx_context* ctx, const vx_ray_batch* rays, uint32_t count, int memory, vx_ray_hit* hits);
+/* world.glsl:27-108,132-138 for rays the caller generates itself: per ray i of the batch -- gathered through the strides of `rays` exactly as
+ * vx_raycast_batch gathers it -- trace_ray(ro, rd) (a primary cast with cast_translucent = true, the highlight outline, the normal map, diffuse
+ * and specular light, at most one shadow ray along -light_dir) or, where nothing was hit, get_sky_color(rd). world.glsl's main (:110-129) is
+ * the only part of the shader that knows a camera, and it is the part left out: an orthographic map, a cube map, a distorted or foveated view,
+ * a mirror ray or a sparse set of pixels are batches of rays. One ray a lane on the world's own bytes, a kernel of its own (csrc/trace).
+ * Outputs, at least one of them: `rgba` receives `count` pixels at index i in `format` -- VX_FORMAT_RGBA32F: 16 bytes a ray; VX_FORMAT_RGBA8: the
+ * 4 bytes vx_render's RGBA8 targets hold (clamp to [0,1], round to the nearest of 255 steps, NaN -> 0), with no row flip: a batch has no
+ * rows --; `hits` receives `count` vx_hit records, each exactly what vx_render records for a pixel whose primary ray is that ray (t, value,
+ * face_id, flags, pos, lod, uv, shadow_t, steps = primary + shadow), bit for bit; colours agree with vx_render's to the stated 5e-6.
+ * Uniforms: ambient, light_dir, cam_pos, render_shadows, shadow_distance and highlight_pos are used; view, fovy and aspect are ignored.
+ * cam_pos feeds the specular term only (world.glsl:73) and is independent of the rays' origins.
+ * max_dst limits the PRIMARY cast only -- a ray it ends is a miss and gets the sky --; the shadow ray is never limited, as in the shader.
+ * max_dst = NULL with max_dst_all = -1 is the shader's own behaviour. flags: 0 or VX_RAYS_TRANSLUCENT, and both cast as world.glsl:29 does
+ * (translucent). A ray means what trace_ray's arguments mean and is not validated: the shader passes a normalised rd, and get_sky_color
+ * divides by the length of its horizontal part (rd.x = rd.z = 0 makes the sky term 0/0 there as here).
+ * Memory kinds, ordering and fences are vx_raycast_batch's. VX_MEM_HOST: synchronous; rays, pixels and records travel through pinned memory
+ * the kernel reads and writes; one launch, one wait. VX_MEM_DEVICE: every pointer of `rays`, `rgba` and `hits` are device memory (`uniforms`
+ * and `rays` themselves are read on the host during the call; rgba aligned to a pixel, hits to 16 bytes); enqueued on the context's stream,
+ * returns after enqueueing, ordered behind the commits made so far, an earlier vx_physics_step and an earlier vx_raycast_batch; later commits
+ * wait for it; the fence is vx_sync. rgba and hits must not overlap each other or anything `rays` points to.
+ * VX_ERR_INVALID_ARGUMENT (its message names the field; nothing is written): a null ctx; null uniforms, null rays or both outputs null with
+ * count > 0; vx_ray_batch's stride and null rules; an unknown bit in flags; an unknown memory kind or format; count > 16777216 (2^24).
+ * count == 0: VX_OK. Before the first commit: VX_ERR_STATE. */
+int vx_trace_rays(vx_context* ctx, const vx_uniforms* uniforms, const vx_ray_batch* rays, uint32_t count, int memory, void* rgba, int format,
+                  vx_hit* hits);
 /* Physics::step_many (src/systems/physics.rs:122-136) `steps` times over `count` entities in ONE kernel launch, against the world as last
  * committed: per step and entity the AABB's fan of axis-parallel picker rays (Aabb::generate_picker_tasks, svo_picker.rs:183-243: max_dst
  * 10), folded into six contact distances (parse_picker_results, svo_picker.rs:245-299), then Physics::update_entity and

@@ -16,7 +16,7 @@
 //! hand out what `build_texture_array` / `build_material_buffer` (svo_registry.rs:122-165) compute -- `texture_layers()` and
 //! `material_rows()` below are written against those.
 use std::ops::Deref;
-use std::os::raw::c_int;
+use std::os::raw::{c_int, c_void};
 use std::ptr;
 
 use cgmath::{EuclideanSpace, Matrix4, Point3, SquareMatrix, Vector3};
@@ -228,6 +228,44 @@ impl Svo {
     /// `rays` must describe `count` readable rays and `hits` `count` writable records in device memory, and the two must not overlap.
     pub unsafe fn raycast_batch_device(&self, rays: &vx_ray_batch, count: u32, hits: *mut vx_ray_hit) {
         check(vx_raycast_batch(self.ctx, rays, count, VX_MEM_DEVICE, hits));
+    }
+}
+
+impl Svo {
+    /// Shaded rays the caller generates itself -- a top-down orthographic map, a cube map, a distorted or foveated view, a mirror ray, a sparse
+    /// set of pixels: `pixels[i]` is what world.glsl's `trace_ray(origins[i], dirs[i])` returns (world.glsl:27-90: translucent primary cast,
+    /// highlight outline, normal map, diffuse and specular light, at most one shadow ray) or, where the ray hits nothing, `get_sky_color`
+    /// (world.glsl:92-108) -- RGBA32F. `dirs.len() == 1`: one direction for every ray (parallel rays). `max_dst` ends the primary cast only
+    /// (`-1.0`: no limit, the shader's own behaviour). Of `params` the lighting is used (`ambient_intensity`, `light_dir`, `cam_pos` for the
+    /// specular term, `render_shadows`, `shadow_distance`, `selected_voxel`); the camera's orientation, `fov_y_rad` and `aspect_ratio` are
+    /// not. `hits`, if given, receives the `vx_hit` record `vx_render` keeps of a pixel whose primary ray is that ray. Synchronous: one launch,
+    /// one wait.
+    pub fn trace_rays(&self, params: &RenderParams, origins: &[[f32; 3]], dirs: &[[f32; 3]], max_dst: f32, pixels: &mut [[f32; 4]], hits: Option<&mut [vx_hit]>) {
+        assert!(dirs.len() == origins.len() || dirs.len() == 1);
+        assert!(pixels.len() >= origins.len());
+        let hits = hits.map_or(ptr::null_mut(), |h| {
+            assert!(h.len() >= origins.len());
+            h.as_mut_ptr()
+        });
+        let u = Self::uniforms(params);
+        let rays = vx_ray_batch {
+            origin: origins.as_ptr().cast(), dir: dirs.as_ptr().cast(), max_dst: ptr::null(),
+            origin_stride: 12, dir_stride: if dirs.len() == origins.len() { 12 } else { 0 }, max_dst_stride: 0,
+            max_dst_all: max_dst, flags: VX_RAYS_TRANSLUCENT,
+        };
+        check(unsafe { vx_trace_rays(self.ctx, &u, &rays, origins.len() as u32, VX_MEM_HOST, pixels.as_mut_ptr().cast(), VX_FORMAT_RGBA32F, hits) });
+    }
+
+    /// The raw device form: every pointer of `rays`, `rgba` (`count` pixels in `format`, aligned to a pixel) and `hits` (aligned to 16 bytes) are
+    /// device memory of this context's GPU; either output may be null, not both. Returns after enqueueing, ordered behind everything issued on
+    /// this context before; `vx_sync` is the fence.
+    ///
+    /// # Safety
+    /// `rays` must describe `count` readable rays, `rgba` and `hits` `count` writable pixels and records in device memory, and none of them may
+    /// overlap another.
+    pub unsafe fn trace_rays_device(&self, params: &RenderParams, rays: &vx_ray_batch, count: u32, rgba: *mut c_void, format: c_int, hits: *mut vx_hit) {
+        let u = Self::uniforms(params);
+        check(vx_trace_rays(self.ctx, &u, rays, count, VX_MEM_DEVICE, rgba, format, hits));
     }
 }
 

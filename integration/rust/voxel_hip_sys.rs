@@ -174,6 +174,10 @@ extern "C" {
     pub fn vx_raycast(ctx: *mut vx_context, tasks: *const PickerTask, count: u32, results: *mut PickerResult) -> c_int;
     /// picker.glsl for `count` plain rays (PickerBatch::add_ray) read through the strides of `rays`; `memory`: VX_MEM_HOST / VX_MEM_DEVICE
     pub fn vx_raycast_batch(ctx: *mut vx_context, rays: *const vx_ray_batch, count: u32, memory: c_int, hits: *mut vx_ray_hit) -> c_int;
+    /// world.glsl:27-108,132-138 (trace_ray, or the sky) for `count` rays read through the strides of `rays`: `count` pixels in `format` to `rgba`
+    /// and / or `count` vx_hit records to `hits` (either may be null, not both); `memory`: VX_MEM_HOST / VX_MEM_DEVICE
+    pub fn vx_trace_rays(ctx: *mut vx_context, uniforms: *const vx_uniforms, rays: *const vx_ray_batch, count: u32, memory: c_int, rgba: *mut c_void,
+                         format: c_int, hits: *mut vx_hit) -> c_int;
     /// Physics::step_many (physics.rs:122-136) `steps` times for `count` entities in one launch; `memory`: VX_MEM_HOST / VX_MEM_DEVICE
     pub fn vx_physics_step(ctx: *mut vx_context, entities: *mut vx_entity, count: u32, memory: c_int, delta_time: f32, steps: u32,
                            contacts: *mut vx_aabb_result) -> c_int;

@@ -95,6 +95,7 @@ SYMBOLS = {
     "vx_render": (_int, [_vp, C.POINTER(Uniforms), _u32, _u32, C.POINTER(Target)]),
     "vx_raycast": (_int, [_vp, _vp, _u32, _vp]),
     "vx_raycast_batch": (_int, [_vp, C.POINTER(RayBatch), _u32, _int, _vp]),
+    "vx_trace_rays": (_int, [_vp, C.POINTER(Uniforms), C.POINTER(RayBatch), _u32, _int, _vp, _int, _vp]),
     "vx_physics_step": (_int, [_vp, _vp, _u32, _int, C.c_float, _u32, _vp]),
     "vx_debug_trace": (_int, [_vp, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.c_float, _int, C.POINTER(Result), _vp, _u32, C.POINTER(_u32)]),
     "vx_sync": (_int, [_vp]),
@@ -257,6 +258,11 @@ def entity_positions(entities):
 def ray_hits_to_numpy(hits):
     """A device hit tensor of Svo.raycast_batch as RAY_HIT_DTYPE records (copies to the host: synchronise first)."""
     return hits.cpu().numpy().view(np.uint8).reshape(-1).view(RAY_HIT_DTYPE)
+
+
+def trace_hits_to_numpy(hits):
+    """A device record tensor of Svo.trace_rays as HIT_DTYPE records (copies to the host: synchronise first)."""
+    return hits.cpu().numpy().view(np.uint8).reshape(-1).view(HIT_DTYPE)
 
 
 def _ray_vectors(name, x, count, width):
@@ -456,21 +462,7 @@ class Svo:
         Host (NumPy arrays): synchronous; returns `out` or a fresh array of RAY_HIT_DTYPE.
         Device (torch CUDA tensors): returns after enqueueing, without synchronising -- pair with sync(); the hits are `out` or a fresh
         int32 tensor of shape (N, 8) on the rays' device, whose rows are vx_ray_hit records (ray_hits_to_numpy)."""
-        host = isinstance(origins, np.ndarray)
-        count = int(origins.shape[0]) if len(origins.shape) == 2 else -1
-        if count < 0 or origins.shape[1] != 3:
-            raise TypeError("raycast_batch: origins must have shape (N, 3)")
-        b = RayBatch()
-        per_ray = not isinstance(max_dst, (int, float, np.floating, np.integer))
-        arrays = [origins, dirs] + ([max_dst] if per_ray else [])
-        if any(isinstance(a, np.ndarray) != host for a in arrays) or (not host and not all(getattr(a, "is_cuda", False) for a in arrays)):
-            raise TypeError("raycast_batch: origins, dirs and max_dst must all be NumPy arrays or all be torch CUDA tensors")
-        b.origin, b.origin_stride = _ray_vectors("origins", origins, count, 3)
-        b.dir, b.dir_stride = _ray_vectors("dirs", dirs, count, 3)
-        if per_ray:
-            b.max_dst, b.max_dst_stride = _ray_vectors("max_dst", max_dst, count, 1)
-        else:
-            b.max_dst, b.max_dst_stride, b.max_dst_all = None, 0, float(max_dst)
+        b, count, host = self._ray_batch(origins, dirs, max_dst)
         b.flags = VX_RAYS_TRANSLUCENT if translucent else 0
         if host:
             if out is None:
@@ -487,6 +479,60 @@ class Svo:
             raise TypeError("raycast_batch: out must be a contiguous CUDA tensor of N x 32 bytes")
         _check(lib().vx_raycast_batch(self._h, C.byref(b), count, VX_MEM_DEVICE, _vp(out.data_ptr())))
         return out
+
+    def _ray_batch(self, origins, dirs, max_dst):
+        """(vx_ray_batch, count, host?) of raycast_batch's three ray arguments."""
+        host = isinstance(origins, np.ndarray)
+        count = int(origins.shape[0]) if len(origins.shape) == 2 else -1
+        if count < 0 or origins.shape[1] != 3:
+            raise TypeError("raycast_batch: origins must have shape (N, 3)")
+        b = RayBatch()
+        per_ray = not isinstance(max_dst, (int, float, np.floating, np.integer))
+        arrays = [origins, dirs] + ([max_dst] if per_ray else [])
+        if any(isinstance(a, np.ndarray) != host for a in arrays) or (not host and not all(getattr(a, "is_cuda", False) for a in arrays)):
+            raise TypeError("raycast_batch: origins, dirs and max_dst must all be NumPy arrays or all be torch CUDA tensors")
+        b.origin, b.origin_stride = _ray_vectors("origins", origins, count, 3)
+        b.dir, b.dir_stride = _ray_vectors("dirs", dirs, count, 3)
+        if per_ray:
+            b.max_dst, b.max_dst_stride = _ray_vectors("max_dst", max_dst, count, 1)
+        else:
+            b.max_dst, b.max_dst_stride, b.max_dst_all = None, 0, float(max_dst)
+        return b, count, host
+
+    def trace_rays(self, uniforms, origins, dirs, max_dst=-1.0, want_hits=False, fmt=VX_FORMAT_RGBA32F, out=None, want_rgba=True):
+        """vx_trace_rays: world.glsl's trace_ray, or the sky, for rays read where they lie (the arguments of raycast_batch: NumPy arrays, or
+        torch CUDA tensors). Returns (pixels, records). pixels: (N, 4) float32, or (N, 4) uint8 for fmt RGBA8; None with want_rgba=False.
+        records: vx_hit (HIT_DTYPE) when want_hits, else None. out: (pixels, records) to write into instead of fresh arrays (either may be
+        None to have a fresh one; they may be longer than N).
+        Host: synchronous. Device: returns after enqueueing -- pair with sync(); records are an int32 tensor of shape (N, 12) (trace_hits_to_numpy)."""
+        b, count, host = self._ray_batch(origins, dirs, max_dst)
+        if not want_rgba and not want_hits:
+            raise TypeError("trace_rays: nothing asked for")
+        rgba, hits = out if out is not None else (None, None)
+        px_dt, px_bytes = (np.uint8, 4) if fmt == VX_FORMAT_RGBA8 else (np.float32, 16)
+        if host:
+            if want_rgba and rgba is None:
+                rgba = np.zeros((count, 4), dtype=px_dt)
+            if want_hits and hits is None:
+                hits = np.zeros(count, dtype=HIT_DTYPE)
+            for a, size in ((rgba if want_rgba else None, px_bytes), (hits if want_hits else None, HIT_DTYPE.itemsize)):
+                if a is not None and (not isinstance(a, np.ndarray) or a.nbytes < count * size or not a.flags.c_contiguous or not a.flags.writeable):
+                    raise TypeError("trace_rays: an output must be a writeable C-contiguous array of at least N pixels / records")
+            _check(lib().vx_trace_rays(self._h, C.byref(uniforms), C.byref(b), count, VX_MEM_HOST, rgba.ctypes.data_as(_vp) if want_rgba else None, fmt,
+                                       hits.ctypes.data_as(_vp) if want_hits else None))
+            return (rgba if want_rgba else None), (hits if want_hits else None)
+        import torch
+
+        if want_rgba and rgba is None:
+            rgba = torch.empty((count, 4), dtype=torch.uint8 if fmt == VX_FORMAT_RGBA8 else torch.float32, device=origins.device)
+        if want_hits and hits is None:
+            hits = torch.empty((count, 12), dtype=torch.int32, device=origins.device)
+        for a, size in ((rgba if want_rgba else None, px_bytes), (hits if want_hits else None, HIT_DTYPE.itemsize)):
+            if a is not None and (not a.is_cuda or not a.is_contiguous() or a.numel() * a.element_size() < count * size):
+                raise TypeError("trace_rays: an output must be a contiguous CUDA tensor of at least N pixels / records")
+        _check(lib().vx_trace_rays(self._h, C.byref(uniforms), C.byref(b), count, VX_MEM_DEVICE, _vp(rgba.data_ptr()) if want_rgba else None, fmt,
+                                   _vp(hits.data_ptr()) if want_hits else None))
+        return (rgba if want_rgba else None), (hits if want_hits else None)
 
     # -- Physics::step_many (src/systems/physics.rs:122-136), on the device ---------------------------------------
     def physics_step(self, entities, dt, steps=1, want_contacts=False, count=None, contacts=None):

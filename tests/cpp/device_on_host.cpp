@@ -1,30 +1,7 @@
 // TEST HARNESS ONLY: compiles the DEVICE header (voxel-rs_amd/csrc/hip/vx_device.hpp) for the host with shims for the
-// HIP built-ins, so the device-side logic can be stepped against the oracle without a GPU. Never linked into the
+// HIP built-ins (tests/cpp/shims/hip_on_host.hpp), so the device-side logic can be stepped against the oracle without a GPU. Never linked into the
 // product libraries; the product has no CPU path.
-#include <cmath>
-#include <cstdint>
-#include <cstring>
-#include <vector>
-
-#define __device__
-#define __host__
-#define __forceinline__ inline
-#define __constant__ static const
-#define __restrict__
-struct uint4 { uint32_t x, y, z, w; };
-struct float4 { float x, y, z, w; };
-static inline float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
-struct uint2 { uint32_t x, y; };
-static inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return uint4{x, y, z, w}; }
-static inline uint2 make_uint2(uint32_t x, uint32_t y) { return uint2{x, y}; }
-static inline uint32_t __popc(uint32_t v) { return uint32_t(__builtin_popcount(v)); }
-static inline int __clz(uint32_t v) { return v ? __builtin_clz(v) : 32; }
-static inline uint32_t __float_as_uint(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
-static inline int32_t __float_as_int(float f) { int32_t u; std::memcpy(&u, &f, 4); return u; }
-static inline float __uint_as_float(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
-static inline float __int_as_float(int32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
-#define HIP_INCLUDE_HIP_HIP_RUNTIME_H  // keep <hip/hip_runtime.h> out
-#define VX_DEVICE_ON_HOST 1
+#include "hip_on_host.hpp"
 #include "vx_device.hpp"
 
 namespace vxd { unsigned char* vx_smem = nullptr; }
@@ -66,21 +43,6 @@ extern "C" int devhost_tile_numbering(uint32_t tiles_x, uint32_t tiles_y, uint32
     return 1;
 }
 using namespace vxd;
-
-// The arguments of the scene of a world's own bytes as the entries below are handed it (the caller keeps them alive: a DevScene points into them)
-static SceneArgs bytes_scene_args(const uint8_t* world, uint64_t world_bytes, const vx_material* mats, uint32_t n_mats, const uint8_t* tex, uint32_t tw, uint32_t th,
-                            uint32_t layers, uint32_t levels, const uint32_t* level_offset) {
-    SceneArgs sa = {};
-    sa.world = world; sa.world_bytes = uint32_t(world_bytes); sa.materials = mats; sa.n_materials = n_mats;
-    sa.tex = tex; sa.tex_bytes = 0;
-    sa.width = tw; sa.height = th; sa.layers = layers; sa.levels = levels;
-    for (uint32_t l = 0; l < levels && l < 16; ++l) {
-        sa.level_offset[l] = level_offset[l];
-        const uint32_t w = (tw >> l) ? (tw >> l) : 1, h = (th >> l) ? (th >> l) : 1;
-        sa.tex_bytes = level_offset[l] + layers * w * h * 4;
-    }
-    return sa;
-}
 
 // n rays through vxd::intersect on the world's own bytes, one lane's stack: record(i, result) receives each result
 template <class RECORD>
@@ -259,15 +221,7 @@ extern "C" void devhost_image_cast(int svo_type, int layout, int shallow, int wa
                                    const uint8_t* origin, const vx_material* mats, uint32_t n_mats, const uint8_t* tex, uint32_t tw, uint32_t th,
                                    uint32_t layers, uint32_t levels, const uint32_t* level_offset, const vx_picker_task* tasks, uint32_t n,
                                    int cast_translucent, vx_result* results, uint32_t* steps) {
-    SceneArgs sa = {};
-    sa.world = world; sa.world_bytes = world_bytes; sa.materials = mats; sa.n_materials = n_mats;
-    sa.tex = tex; sa.tex_bytes = 0;
-    sa.width = tw; sa.height = th; sa.layers = layers; sa.levels = levels;
-    for (uint32_t l = 0; l < levels && l < 16; ++l) {
-        sa.level_offset[l] = level_offset[l];
-        const uint32_t w = (tw >> l) ? (tw >> l) : 1, h = (th >> l) ? (th >> l) : 1;
-        sa.tex_bytes = level_offset[l] + layers * w * h * 4;
-    }
+    SceneArgs sa = bytes_scene_args(world, world_bytes, mats, n_mats, tex, tw, th, layers, levels, level_offset);
     sa.image = image; sa.image_bytes = image_bytes; sa.origin = origin;
     const DevScene sc = make_image_scene(sa), sc_bytes = make_scene(sa);
     std::vector<unsigned char> lds(Stack<1, false, false, 16, false>::kBytes + 64);
@@ -301,15 +255,7 @@ extern "C" void devhost_image_cast(int svo_type, int layout, int shallow, int wa
 extern "C" uint32_t devhost_image_shadow_pairs(int svo_type, const uint8_t* world, uint64_t world_bytes, const uint8_t* image, uint64_t image_bytes, const uint8_t* origin,
                                                const vx_material* mats, uint32_t n_mats, const uint8_t* tex, uint32_t tw, uint32_t th, uint32_t layers, uint32_t levels,
                                                const uint32_t* level_offset, const vx_picker_task* tasks, uint32_t n, const float* to_light, vx_result* results, uint32_t* steps) {
-    SceneArgs sa = {};
-    sa.world = world; sa.world_bytes = world_bytes; sa.materials = mats; sa.n_materials = n_mats;
-    sa.tex = tex; sa.tex_bytes = 0;
-    sa.width = tw; sa.height = th; sa.layers = layers; sa.levels = levels;
-    for (uint32_t l = 0; l < levels && l < 16; ++l) {
-        sa.level_offset[l] = level_offset[l];
-        const uint32_t w = (tw >> l) ? (tw >> l) : 1, h = (th >> l) ? (th >> l) : 1;
-        sa.tex_bytes = level_offset[l] + layers * w * h * 4;
-    }
+    SceneArgs sa = bytes_scene_args(world, world_bytes, mats, n_mats, tex, tw, th, layers, levels, level_offset);
     sa.image = image; sa.image_bytes = image_bytes; sa.origin = origin;
     const DevScene sc = make_image_scene(sa), sc_bytes = make_scene(sa);
     std::vector<unsigned char> lds(Stack<1, false, false, 16, false>::kBytes + 64);

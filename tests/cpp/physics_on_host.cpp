@@ -1,31 +1,8 @@
 // TEST HARNESS ONLY: compiles the DEVICE physics header (voxel-rs_amd/csrc/physics/vx_physics.hpp) together with the device traversal
-// (voxel-rs_amd/csrc/hip/vx_device.hpp) for the host, with the shims of tests/cpp/device_on_host.cpp, so that the fan, the update and a
+// (voxel-rs_amd/csrc/hip/vx_device.hpp) for the host, with the shims of tests/cpp/shims/hip_on_host.hpp, so that the fan, the update and a
 // whole step can be checked against the host mirror and the oracle without a GPU. Never linked into the product libraries; the product
 // has no CPU path.
-#include <cmath>
-#include <cstdint>
-#include <cstring>
-#include <vector>
-
-#define __device__
-#define __host__
-#define __forceinline__ inline
-#define __constant__ static const
-#define __restrict__
-struct uint4 { uint32_t x, y, z, w; };
-struct float4 { float x, y, z, w; };
-static inline float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
-struct uint2 { uint32_t x, y; };
-static inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return uint4{x, y, z, w}; }
-static inline uint2 make_uint2(uint32_t x, uint32_t y) { return uint2{x, y}; }
-static inline uint32_t __popc(uint32_t v) { return uint32_t(__builtin_popcount(v)); }
-static inline int __clz(uint32_t v) { return v ? __builtin_clz(v) : 32; }
-static inline uint32_t __float_as_uint(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
-static inline int32_t __float_as_int(float f) { int32_t u; std::memcpy(&u, &f, 4); return u; }
-static inline float __uint_as_float(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
-static inline float __int_as_float(int32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
-#define HIP_INCLUDE_HIP_HIP_RUNTIME_H  // keep <hip/hip_runtime.h> out
-#define VX_DEVICE_ON_HOST 1
+#include "hip_on_host.hpp"
 #include "vx_physics.hpp"
 
 namespace vxd { unsigned char* vx_smem = nullptr; }
@@ -68,15 +45,7 @@ extern "C" void physhost_update(float delta_time, vx_entity* entities, const vx_
 extern "C" void physhost_step(int svo_type, const uint8_t* world, uint64_t world_bytes, const vx_material* mats, uint32_t n_mats, const uint8_t* tex,
                               uint32_t tw, uint32_t th, uint32_t layers, uint32_t levels, const uint32_t* level_offset, vx_entity* entities, uint32_t n,
                               float delta_time, uint32_t steps, vx_aabb_result* contacts) {
-    SceneArgs sa = {};
-    sa.world = world; sa.world_bytes = world_bytes; sa.materials = mats; sa.n_materials = n_mats;
-    sa.tex = tex; sa.tex_bytes = 0;
-    sa.width = tw; sa.height = th; sa.layers = layers; sa.levels = levels;
-    for (uint32_t l = 0; l < levels && l < 16; ++l) {
-        sa.level_offset[l] = level_offset[l];
-        const uint32_t w = (tw >> l) ? (tw >> l) : 1, h = (th >> l) ? (th >> l) : 1;
-        sa.tex_bytes = level_offset[l] + layers * w * h * 4;
-    }
+    const SceneArgs sa = bytes_scene_args(world, world_bytes, mats, n_mats, tex, tw, th, layers, levels, level_offset);
     const DevScene sc = make_scene(sa);
     std::vector<unsigned char> lds(Stack<1>::kBytes + 64);
     vx_smem = lds.data();

@@ -1,7 +1,8 @@
 // Everything of the product that runs on HOST THREADS, driven hard under the sanitizers (make -C voxel-rs_amd sanitize; CPU build only -- the
 // GPU boxes run no sanitizer): the scene builder's workers, the chunk streamer's background workers feeding pump(), the traversal image's
-// Workers (whole-world build and incremental WorldImage::update at 1 / 4 / 16 threads), and the device header's traversal (vx_device.hpp
-// behind the plain-C++ platform shims, tests/cpp/device_on_host.cpp) walking what they built. Test infrastructure: nothing of the product
+// Workers (whole-world build and incremental WorldImage::update at 1 / 4 / 16 threads), the device header's traversal (vx_device.hpp
+// behind the plain-C++ platform shims, tests/cpp/device_on_host.cpp) walking what they built, and a ray batch packed and gathered again
+// (vx_ray_batch.hpp, tests/cpp/batch_on_host.cpp) on buffers that end with their last value. Test infrastructure: nothing of the product
 // links against it. What the reference's design relies on (src/systems/worldsvo.rs:90-151): worker threads only BUILD chunks, the caller's
 // thread owns the buffer -- a data race or a stray write here is a bug in that hand-over.
 //
@@ -23,6 +24,7 @@
 #include "scene.hpp"
 #include "stream.hpp"
 #include "traversal_image.hpp"
+#include "vx_ray_batch.hpp"
 
 // the streamer's device half is never reached here (pump(nullptr, ..)): symbols for the linker, an abort for a caller
 extern "C" {
@@ -36,6 +38,10 @@ void devhost_picker(int svo_type, const uint8_t* world, uint64_t world_bytes, co
 void devhost_image_cast(int svo_type, int layout, int shallow, int walk_mode, const uint8_t* world, uint64_t world_bytes, const uint8_t* image, uint64_t image_bytes,
                         const uint8_t* origin, const vx_material* mats, uint32_t n_mats, const uint8_t* tex, uint32_t tw, uint32_t th, uint32_t layers, uint32_t levels,
                         const uint32_t* level_offset, const vx_picker_task* tasks, uint32_t n, int cast_translucent, vx_result* results, uint32_t* steps);
+// tests/cpp/batch_on_host.cpp, compiled into this binary
+void batchhost_pack(const vx_ray_batch* rays, uint32_t n, uint8_t* scratch, vxk::RayBatchArgs* out);
+void batchhost_in_place(const vx_ray_batch* rays, vxk::RayBatchArgs* out);
+void batchhost_gather(const vxk::RayBatchArgs* a, uint32_t i, float out[7]);
 }
 
 using namespace vx;
@@ -218,11 +224,51 @@ void stream_and_update(const char* name, int svo_type, size_t header, uint32_t s
                 moves, (unsigned long long)events, commits, streamer_threads, streamer.resident_chunks());
 }
 
+// A ray batch packed the way the host-memory calls pack it and gathered the way the kernels gather it, against the gather over the arrays in place: every
+// buffer is a heap block of exactly (n - 1) * stride + width bytes (the scratch: the plan's end), so a reader or writer of whole strides runs off its end.
+void ray_batch_rounds() {
+    const uint32_t origin_strides[] = {12, 16, 48, 64}, dir_strides[] = {0, 12, 20, 48};
+    const int dst_strides[] = {-1, 0, 4, 48};  // (-1: no array)
+    size_t rounds = 0;
+    for (uint32_t n : {1u, 3u, 65u})
+        for (uint32_t os : origin_strides)
+            for (uint32_t ds : dir_strides)
+                for (int ms : dst_strides) {
+                    const auto exact = [n](uint32_t stride, uint32_t width) {
+                        const size_t bytes = size_t(stride ? n - 1 : 0) * stride + width;
+                        std::unique_ptr<uint8_t[]> b(new uint8_t[bytes]);
+                        for (size_t i = 0; i < bytes; ++i) b[i] = uint8_t(rnd());
+                        return b;
+                    };
+                    const std::unique_ptr<uint8_t[]> o = exact(os, 12), d = exact(ds, 12), m = exact(ms > 0 ? uint32_t(ms) : 0u, 4);
+                    vx_ray_batch b = {};
+                    b.origin = o.get(); b.dir = d.get(); b.max_dst = ms < 0 ? nullptr : m.get();
+                    b.origin_stride = os; b.dir_stride = ds; b.max_dst_stride = ms < 0 ? 0u : uint32_t(ms);
+                    b.max_dst_all = 7.5f;
+                    const vxrt::RayPlan plan = vxrt::plan_rays(b, n);
+                    std::unique_ptr<uint8_t[]> scratch(new uint8_t[plan.end]);
+                    vxk::RayBatchArgs packed, in_place;
+                    batchhost_pack(&b, n, scratch.get(), &packed);
+                    batchhost_in_place(&b, &in_place);
+                    size_t differ = 0;
+                    for (uint32_t i = 0; i < n; ++i) {
+                        float p[7], q[7];
+                        batchhost_gather(&packed, i, p);
+                        batchhost_gather(&in_place, i, q);
+                        differ += std::memcmp(p, q, 28) != 0;
+                    }
+                    CHECK(differ == 0, "ray batch: %zu of %u rays differ packed and in place (strides %u %u %d)", differ, n, os, ds, ms);
+                    ++rounds;
+                }
+    std::printf("ray batches: %zu stride sets packed and gathered, none out of bounds\n", rounds);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
     const int steps = argc > 1 ? std::atoi(argv[1]) : 200;
     const Look look;
+    ray_batch_rounds();
     {
         Esvo<EsvoSerializedChunk> world;
         const SceneStats st = build_heightfield_scene(world, 8, 0x5EED0001u, 4);

@@ -22,8 +22,8 @@ def devhost():
     src = Path(ROOT) / "tests" / "cpp" / "device_on_host.cpp"
     hdr = Path(ROOT) / "voxel-rs_amd" / "csrc" / "hip" / "vx_device.hpp"
     args_hdr = Path(ROOT) / "voxel-rs_amd" / "csrc" / "hip" / "vx_args.hpp"
-    shim = Path(ROOT) / "tests" / "cpp" / "shims" / "vx_platform.hpp"
-    if not so.exists() or so.stat().st_mtime < max(src.stat().st_mtime, hdr.stat().st_mtime, args_hdr.stat().st_mtime, shim.stat().st_mtime):
+    shims = sorted((Path(ROOT) / "tests" / "cpp" / "shims").glob("*.hpp"))  # (vx_platform.hpp, hip_on_host.hpp)
+    if not so.exists() or so.stat().st_mtime < max(p.stat().st_mtime for p in [src, hdr, args_hdr] + shims):
         # tests/cpp/shims comes first: its vx_platform.hpp (plain C++) is found instead of the product's (gfx950 built-ins)
         cmd = ["g++", "-std=c++17", "-O1", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", f"-I{ROOT}/include", f"-I{ROOT}/tests/cpp/shims",
                f"-I{ROOT}/voxel-rs_amd/csrc/hip", str(src), "-o", str(so)]

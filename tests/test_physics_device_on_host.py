@@ -1,5 +1,5 @@
 """vx_physics_step without a GPU: the DEVICE physics header (voxel-rs_amd/csrc/physics/vx_physics.hpp) compiled for the host by a test-only
-harness (tests/cpp/physics_on_host.cpp, the shims of tests/cpp/device_on_host.cpp) -- the fan's slots against PickerBatch::serialize_tasks,
+harness (tests/cpp/physics_on_host.cpp, the shims of tests/cpp/shims/hip_on_host.hpp) -- the fan's slots against PickerBatch::serialize_tasks,
 the update against Physics::update_entity, whole steps against the oracle-backed step -- and the entry point's argument checks. Every
 comparison is byte for byte."""
 import ctypes as C
@@ -24,7 +24,8 @@ def physhost():
     deps = [Path(ROOT) / "tests" / "cpp" / "physics_on_host.cpp", Path(ROOT) / "voxel-rs_amd" / "csrc" / "physics" / "vx_physics.hpp",
             Path(ROOT) / "voxel-rs_amd" / "csrc" / "physics" / "vx_physics_rules.h",
             Path(ROOT) / "voxel-rs_amd" / "csrc" / "hip" / "vx_device.hpp", Path(ROOT) / "voxel-rs_amd" / "csrc" / "hip" / "vx_args.hpp",
-            Path(ROOT) / "tests" / "cpp" / "shims" / "vx_platform.hpp", Path(ROOT) / "include" / "voxel_hip.h"]
+            Path(ROOT) / "tests" / "cpp" / "shims" / "vx_platform.hpp", Path(ROOT) / "tests" / "cpp" / "shims" / "hip_on_host.hpp",
+            Path(ROOT) / "include" / "voxel_hip.h"]
     if not so.exists() or so.stat().st_mtime < max(d.stat().st_mtime for d in deps):
         # tests/cpp/shims comes first: its vx_platform.hpp (plain C++) is found instead of the product's (gfx950 built-ins)
         cmd = ["g++", "-std=c++17", "-O1", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", f"-I{ROOT}/include", f"-I{ROOT}/tests/cpp/shims",

@@ -198,6 +198,33 @@ def test_ordered_behind_a_physics_step(free):
     assert before.tobytes() != exp_hits.tobytes()  # (a batch that ran first would say this)
 
 
+def test_one_batch_through_both_entry_points(free):
+    """4h: one vx_ray_batch in device memory -- 65 origins at stride 64 inside entity records, one direction for all, max_dst an array of stride 0
+    (one value for all) -- to vx_trace_rays (records only) and to vx_raycast_batch (translucent): both gather it through vx_ray_batch.hpp, so the
+    same rays hit, with t, value, face_id and pos bit-equal. 2 blocks along (0.3, -0.9, 0.2) from 0.5 to 3 blocks above the ground: by the oracle
+    29 rays hit and 36 end in the air; the last ray, the second wave's only lane, is one that hits."""
+    c, svo, _ = free
+    rows = place_entities(c.scene, np.random.default_rng(65), 65, 8, 120, float(c.region[1][1] - 1.0))
+    rows[[62, 64]] = rows[[64, 62]]  # (62 hits, 64 does not)
+    records = hip.entities_from_rows(rows)
+    look, reach = tc.unit([0.3, -0.9, 0.2]), 2.0
+    by_oracle = np.array([c.scene.intersect(p, look, reach, True)[0].t > 0 for p in np.ascontiguousarray(records["position"])])
+    assert by_oracle.sum() >= 10 and (~by_oracle).sum() >= 10 and by_oracle[64]
+    ents = to_device(records.view(np.uint8))
+    origins, one_dir, one_dst = hip.entity_positions(ents), to_device(look), to_device(np.float32([reach])).expand(65)
+    assert hip._ray_vectors("origins", origins, 65, 3)[1] == 64 and hip._ray_vectors("dirs", one_dir, 65, 3)[1] == 0
+    assert hip._ray_vectors("max_dst", one_dst, 65, 1) == (one_dst.data_ptr(), 0)
+    _, traced = svo.trace_rays(c.u, origins, one_dir, one_dst, want_hits=True, want_rgba=False)
+    cast = svo.raycast_batch(origins, one_dir, one_dst, translucent=True)
+    svo.sync()
+    traced, cast = hip.trace_hits_to_numpy(traced), hip.ray_hits_to_numpy(cast)
+    hit = traced["t"] > 0
+    assert (hit == (cast["dst"] > 0)).all() and (hit == by_oracle).all()
+    assert hit.sum() >= 10 and (~hit).sum() >= 10 and hit[64]
+    assert traced["t"][hit].tobytes() == cast["dst"][hit].tobytes() and traced["pos"][hit].tobytes() == cast["pos"][hit].tobytes()
+    assert (traced["value"][hit] == cast["value"][hit]).all() and (traced["face_id"][hit] == cast["face_id"][hit]).all()
+
+
 @pytest.mark.parametrize("fmt", ["esvo", "csvo"])
 def test_state(fmt):
     """5: before the first commit VX_ERR_STATE; count = 0 is VX_OK and writes nothing; what a call with a context lacks is refused with the

@@ -25,7 +25,8 @@ def tracehost():
     so = BUILD / "libtrace_on_host.so"
     csrc = Path(ROOT) / "voxel-rs_amd" / "csrc"
     deps = [Path(ROOT) / "tests" / "cpp" / "trace_on_host.cpp", csrc / "trace" / "vx_trace.hpp", csrc / "hip" / "vx_device.hpp", csrc / "hip" / "vx_args.hpp",
-            Path(ROOT) / "tests" / "cpp" / "shims" / "vx_platform.hpp", Path(ROOT) / "include" / "voxel_hip.h"]
+            Path(ROOT) / "tests" / "cpp" / "shims" / "vx_platform.hpp", Path(ROOT) / "tests" / "cpp" / "shims" / "hip_on_host.hpp",
+            Path(ROOT) / "include" / "voxel_hip.h"]
     if not so.exists() or so.stat().st_mtime < max(p.stat().st_mtime for p in deps):
         # tests/cpp/shims comes first: its vx_platform.hpp (plain C++) is found instead of the product's (gfx950 built-ins)
         cmd = ["g++", "-std=c++17", "-O1", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", f"-I{ROOT}/include", f"-I{ROOT}/tests/cpp/shims",

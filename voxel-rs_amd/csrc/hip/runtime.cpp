@@ -18,8 +18,10 @@
 
 using namespace vxd;
 using namespace vxk;
+using vxrt::check_ready;
 using vxrt::fail;
 using vxrt::g_last_error;
+using vxrt::kWorldPad;
 using vxrt::ProfiledLaunch;
 
 namespace vxrt {
@@ -27,6 +29,32 @@ thread_local std::string g_last_error;
 int fail(int code, const std::string& msg) {
     g_last_error = msg;
     return code;
+}
+
+SceneArgs scene_on_bytes(const vx_context* c) {
+    SceneArgs s = {};
+    s.world = c->d_world;
+    s.world_bytes = uint64_t(c->capacity) + kWorldPad;
+    s.materials = c->d_materials;
+    s.n_materials = c->n_materials;
+    s.tex = c->d_tex;
+    s.tex_bytes = c->tex_bytes;
+    s.width = c->tex.width; s.height = c->tex.height; s.layers = c->tex.layers; s.levels = c->tex.levels;
+    for (int l = 0; l < 16; ++l) s.level_offset[l] = c->tex.level_offset[l];
+    return s;
+}
+
+int check_ready(vx_context* ctx) {
+    if (!ctx) return fail(VX_ERR_INVALID_ARGUMENT, "null context");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!ctx->committed) return fail(VX_ERR_STATE, "no SVO committed yet (call vx_commit / vx_commit_all first)");
+    return VX_OK;
+}
+
+int mark_world_read(vx_context* ctx) {
+    HIP_TRY(hipEventRecord(ctx->render_done, ctx->stream));
+    ctx->render_recorded = true;
+    return VX_OK;
 }
 }  // namespace vxrt
 
@@ -38,22 +66,13 @@ void stop_commit_worker(vx_context* ctx);
 
 namespace {
 
-constexpr size_t kWorldPad = 16;
 constexpr size_t kImagePad = 64;  // zero bytes behind the image: an 8-byte entry load at the last octant's last child stays inside
 constexpr size_t kStagingSlack = 64;
 
 uint32_t header_bytes(const vx_context* c) { return c->svo_type == VX_SVO_ESVO ? 20u : 4u; }
 
 SceneArgs scene_of(const vx_context* c) {
-    SceneArgs s = {};
-    s.world = c->d_world;
-    s.world_bytes = uint64_t(c->capacity) + kWorldPad;
-    s.materials = c->d_materials;
-    s.n_materials = c->n_materials;
-    s.tex = c->d_tex;
-    s.tex_bytes = c->tex_bytes;
-    s.width = c->tex.width; s.height = c->tex.height; s.layers = c->tex.layers; s.levels = c->tex.levels;
-    for (int l = 0; l < 16; ++l) s.level_offset[l] = c->tex.level_offset[l];
+    SceneArgs s = vxrt::scene_on_bytes(c);
     s.image = c->image_ok ? c->d_image : nullptr;
     s.image_bytes = c->image_ok ? c->pub.frame_bytes + kImagePad : 0u;
     // (images of CSVO worlds: where a voxel-parent octant comes from in the world's bytes is in the image itself, the unit in front of its values)
@@ -173,13 +192,6 @@ int ensure(void** p, size_t* have, size_t need) {
     *have = 0;
     HIP_TRY(hipMalloc(p, need));
     *have = need;
-    return VX_OK;
-}
-
-int check_ready(vx_context* ctx) {
-    if (!ctx) return fail(VX_ERR_INVALID_ARGUMENT, "null context");
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (!ctx->committed) return fail(VX_ERR_STATE, "no SVO committed yet (call vx_commit / vx_commit_all first)");
     return VX_OK;
 }
 

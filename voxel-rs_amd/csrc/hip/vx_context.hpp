@@ -1,4 +1,5 @@
-// Internal to the library's host side (runtime.cpp, comm.cpp): the render context behind the opaque vx_context of include/voxel_hip.h.
+// Internal to the library's host side (runtime.cpp, comm.cpp and the modules beside csrc/hip): the render context behind the opaque vx_context of
+// include/voxel_hip.h, and what runtime.cpp defines once for every translation unit on it.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -38,6 +39,15 @@ struct ProfiledLaunch {
 struct vx_context;
 namespace vxrt {
 void comm_release(vx_context* c);  // comm.cpp: the context's communicator, if it has one, is destroyed (vx_destroy)
+
+// runtime.cpp, for every entry point that launches a kernel on the context:
+constexpr size_t kWorldPad = 16;  // zero bytes a context keeps behind the world buffer, inside what a kernel may read
+// the SceneArgs of a walk on the world's OWN bytes: the image fields are null, the traversal image is never read
+vxd::SceneArgs scene_on_bytes(const vx_context* c);
+// not null, its device current, a world committed; else the code, with the message set
+int check_ready(vx_context* ctx);
+// a kernel just queued on ctx->stream reads the world: a later commit's uploads wait for it like for a frame in flight (vx_commit)
+int mark_world_read(vx_context* ctx);
 }
 
 struct vx_context {

@@ -1,5 +1,5 @@
 // vx_raycast_batch's kernel (gfx950): picker.glsl:30-51 for a batch of rays read where they lie -- origins, directions and distances
-// gathered through byte strides (PickerBatch::add_ray's rays without the std430 PickerTask around them) -- and answered with 32-byte hits
+// gathered through byte strides (vx_ray_batch.hpp's gather_ray: PickerBatch::add_ray's rays without the std430 PickerTask around them) -- and answered with 32-byte hits
 // that keep OctreeResult.value (svo.glsl:31-40), the block id. 64 lanes a workgroup, one ray a lane, each through vxd::intersect on the
 // world's own bytes exactly as picker_kernel casts it (kernels_aux.hip). The world is read-only for the whole launch.
 #include <hip/hip_runtime.h>
@@ -10,14 +10,6 @@
 using namespace vxd;
 
 namespace {
-
-// A float[3] at base + i * stride: three dword loads in the source (a record only has to be 4-byte aligned). The pointers are kernel arguments of
-// their own, so the loads address global memory (no flat aperture check). A stride of 0 never comes here: it is decided on the kernel
-// argument, and that branch reads one address in every lane -- a wave-uniform load.
-__device__ __forceinline__ void load3(const uint8_t* __restrict__ base, uint32_t stride, uint32_t i, float out[3]) {
-    const float* p = reinterpret_cast<const float*>(base + size_t(i) * stride);
-    out[0] = p[0]; out[1] = p[1]; out[2] = p[2];
-}
 
 // TRANSLUCENT is part of the kernel's type: the opaque cast then compiles to picker_kernel's walk (no texture sampling in the leaf test,
 // about half the vector registers), and that is the cast nearly every batch asks for.
@@ -32,17 +24,8 @@ __global__ __launch_bounds__(64) void raycast_batch_kernel(SceneArgs sa, const u
     st.init(threadIdx.x, &spill);
     const uint32_t i = blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
-    float ro[3], rd[3];
-    load3(origin, origin_stride, i, ro);
-    if (dir_stride) {
-        load3(dir, dir_stride, i, rd);
-    } else {  // one direction for every ray
-        const float* d = reinterpret_cast<const float*>(dir);
-        rd[0] = d[0]; rd[1] = d[1]; rd[2] = d[2];
-    }
-    float limit = max_dst_all;
-    if (has_max_dst)  // (a kernel argument, like the strides: no lane branches on a pointer)
-        limit = max_dst_stride ? *reinterpret_cast<const float*>(max_dst + size_t(i) * max_dst_stride) : *reinterpret_cast<const float*>(max_dst);
+    float ro[3], rd[3], limit;
+    vxk::gather_ray(origin, dir, max_dst, origin_stride, dir_stride, max_dst_stride, max_dst_all, has_max_dst, i, ro, rd, limit);
     // picker.glsl:30-51, cast_translucent as the batch asks
     Result res;
     uint32_t steps = 0;

@@ -1,5 +1,5 @@
 // vx_trace_rays' kernel (gfx950): world.glsl:132-138 -- trace_ray, or the sky -- for a batch of rays read where they lie, gathered through byte
-// strides exactly as raycast_batch_kernel gathers them (csrc/raycast/kernels_raycast.hip), and answered with a pixel and / or the vx_hit
+// strides exactly as raycast_batch_kernel gathers them (csrc/raycast/vx_ray_batch.hpp: gather_ray), and answered with a pixel and / or the vx_hit
 // record vx_render keeps of a pixel. 64 lanes a workgroup, one ray a lane, on the world's own bytes like the picker path and render_kernel;
 // the per-ray code is vx_trace.hpp's. The world is read-only for the whole launch.
 #include <hip/hip_runtime.h>
@@ -10,12 +10,6 @@
 using namespace vxd;
 
 namespace {
-
-// (kernels_raycast.hip's load3: three dword loads, the record only has to be 4-byte aligned)
-__device__ __forceinline__ void load3(const uint8_t* __restrict__ base, uint32_t stride, uint32_t i, float out[3]) {
-    const float* p = reinterpret_cast<const float*>(base + size_t(i) * stride);
-    out[0] = p[0]; out[1] = p[1]; out[2] = p[2];
-}
 
 // What is written is decided on kernel arguments (out_rgba: 0 none, 1 RGBA32F, 2 RGBA8; out_hits), like the strides: scalar branches, no lane
 // looks at a pointer.
@@ -31,17 +25,8 @@ __global__ __launch_bounds__(64) void trace_rays_kernel(SceneArgs sa, vx_uniform
     st.init(threadIdx.x, &spill);
     const uint32_t i = blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
-    float ro[3], rd[3];
-    load3(origin, origin_stride, i, ro);
-    if (dir_stride) {
-        load3(dir, dir_stride, i, rd);
-    } else {  // one direction for every ray
-        const float* d = reinterpret_cast<const float*>(dir);
-        rd[0] = d[0]; rd[1] = d[1]; rd[2] = d[2];
-    }
-    float limit = max_dst_all;
-    if (has_max_dst)
-        limit = max_dst_stride ? *reinterpret_cast<const float*>(max_dst + size_t(i) * max_dst_stride) : *reinterpret_cast<const float*>(max_dst);
+    float ro[3], rd[3], limit;
+    vxk::gather_ray(origin, dir, max_dst, origin_stride, dir_stride, max_dst_stride, max_dst_all, has_max_dst, i, ro, rd, limit);
 
     vxt::Traced r;
     vxt::cast_primary<SVO>(sc, ro, rd, limit, st, r);  // 1: every lane

@@ -1,6 +1,6 @@
-// Pinned scratch for the synchronous, host-memory calls of the modules beside csrc/hip (csrc/physics, csrc/raycast): host records travel
+// Pinned scratch for the synchronous, host-memory calls of the modules beside csrc/hip (csrc/physics, csrc/raycast, csrc/trace): host records travel
 // through pinned memory the device sees, which the kernel reads and writes directly -- no copy commands, one launch, one wait
-// (runtime.cpp:1285-1288: a synchronous call costs its round trips). vx_context cannot grow, so the scratch lives here: one grow-only pool
+// (vx_raycast in runtime.cpp: a synchronous call costs its round trips). vx_context cannot grow, so the scratch lives here: one grow-only pool
 // per device, shared by that device's contexts and by the modules, whose mutex a host-memory call holds from its copy in to its copy out.
 // Kept for the life of the process.
 #pragma once

@@ -324,6 +324,29 @@ int vx_raycast_batch(vx_context* ctx, const vx_ray_batch* rays, uint32_t count, 
  * count == 0: VX_OK. Before the first commit: VX_ERR_STATE. */
 int vx_trace_rays(vx_context* ctx, const vx_uniforms* uniforms, const vx_ray_batch* rays, uint32_t count, int memory, void* rgba, int format,
                   vx_hit* hits);
+/* Svo::render (svo.rs:196-229) = world.glsl's main (world.glsl:110-141) for every pixel of `count` SMALL views in ONE launch: the eyes of a few
+ * hundred entities, the six faces of a cube map, a handful of probes -- where a vx_render per view pays a launch (and, for host targets, a wait) per
+ * view for a grid a 64 x 64 image cannot fill. main is the part vx_trace_rays leaves out; this call puts it back, per view: the pixel's primary
+ * ray from the view's `view`, `fovy` and `aspect`, then trace_ray or the sky as vx_trace_rays runs them, shaded with the view's own ambient,
+ * light_dir, cam_pos, render_shadows, shadow_distance and highlight_pos. One pixel a lane on the world's own bytes, a workgroup an 8 x 8 tile of
+ * one view, a kernel of its own (csrc/trace); it walks no traversal image, so deep worlds and textures whose height is no power of two behave as
+ * they do for vx_trace_rays and the picker.
+ * `views`: `count` vx_uniforms records in HOST memory whatever `memory` says; they are read during the call (the tangent of fovy / 2 and the
+ * ray origin are evaluated on the host, as vx_render evaluates them, or the rays would not be vx_render's bit for bit) and may be overwritten
+ * as soon as it returns. All views share width, height and format.
+ * Outputs, at least one of them: view k's image lies at pixel k * width * height of `rgba`, its records at the same index of `hits`; inside a
+ * view every pixel and record lies where vx_render puts it for a whole-image target of that format -- VX_FORMAT_RGBA32F: row 0 = bottom;
+ * VX_FORMAT_RGBA8: the top row first, for the records too. View k's records are bit for bit those of vx_render(ctx, &views[k], width, height,
+ * {hits}); its colours agree with vx_render's to the stated 5e-6, and RGBA8 is the packing of those colours.
+ * memory is the kind of rgba and hits. VX_MEM_HOST: synchronous; the table of views, pixels and records travel through pinned memory the kernel
+ * reads and writes; one launch, one wait. VX_MEM_DEVICE (rgba aligned to a pixel, hits to 16 bytes): enqueued on the context's stream, returns
+ * after enqueueing, ordered behind the commits made so far and an earlier vx_physics_step, vx_raycast_batch or vx_trace_rays; later commits wait
+ * for it; the fence is vx_sync. rgba and hits must not overlap.
+ * VX_ERR_INVALID_ARGUMENT (its message names the field; nothing is written): an unknown memory kind or format; width or height of 0 or above
+ * 8192; count * width * height > 16777216 (2^24); null views or both outputs null with count > 0; a misaligned device output; a null ctx.
+ * count == 0: VX_OK. Before the first commit: VX_ERR_STATE. */
+int vx_trace_views(vx_context* ctx, const vx_uniforms* views, uint32_t count, uint32_t width, uint32_t height, int memory, void* rgba, int format,
+                   vx_hit* hits);
 /* Physics::step_many (src/systems/physics.rs:122-136) `steps` times over `count` entities in ONE kernel launch, against the world as last
  * committed: per step and entity the AABB's fan of axis-parallel picker rays (Aabb::generate_picker_tasks, svo_picker.rs:183-243: max_dst
  * 10), folded into six contact distances (parse_picker_results, svo_picker.rs:245-299), then Physics::update_entity and

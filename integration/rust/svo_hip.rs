@@ -269,6 +269,36 @@ impl Svo {
     }
 }
 
+impl Svo {
+    /// Many small cameras in one launch -- an eye per entity, the six faces of a cube map, a handful of probes: `Svo::render` (svo.rs:196-229,
+    /// world.glsl:110-141) for each of `views`, all `width` x `height`, each with its own camera, light, shadow switch, shadow distance and
+    /// selected voxel. View k's image is `pixels[k * width * height ..]`, RGBA32F with row 0 at the bottom like the framebuffer's texture;
+    /// `hits`, if given, receives the `vx_hit` records in the same order. Pixel for pixel what `render` gives for that view (records bit for
+    /// bit, colours within 5e-6), for one launch and one wait instead of one of each per view. Synchronous.
+    pub fn trace_views(&self, views: &[RenderParams], width: u32, height: u32, pixels: &mut [[f32; 4]], hits: Option<&mut [vx_hit]>) {
+        let n = views.len() * (width * height) as usize;
+        assert!(pixels.len() >= n);
+        let hits = hits.map_or(ptr::null_mut(), |h| {
+            assert!(h.len() >= n);
+            h.as_mut_ptr()
+        });
+        let u: Vec<vx_uniforms> = views.iter().map(Self::uniforms).collect();
+        check(unsafe { vx_trace_views(self.ctx, u.as_ptr(), u.len() as u32, width, height, VX_MEM_HOST, pixels.as_mut_ptr().cast(), VX_FORMAT_RGBA32F, hits) });
+    }
+
+    /// The raw device form: `rgba` (`views.len() * width * height` pixels in `format`, aligned to a pixel; RGBA8 has each view's top row first)
+    /// and `hits` (aligned to 16 bytes) are device memory of this context's GPU; either may be null, not both. `views` stays host memory and
+    /// may be dropped as soon as the call returns. Returns after enqueueing, ordered behind everything issued on this context before;
+    /// `vx_sync` is the fence.
+    ///
+    /// # Safety
+    /// `rgba` and `hits` must be writable for that many pixels and records in device memory and must not overlap.
+    pub unsafe fn trace_views_device(&self, views: &[RenderParams], width: u32, height: u32, rgba: *mut c_void, format: c_int, hits: *mut vx_hit) {
+        let u: Vec<vx_uniforms> = views.iter().map(Self::uniforms).collect();
+        check(vx_trace_views(self.ctx, u.as_ptr(), u.len() as u32, width, height, VX_MEM_DEVICE, rgba, format, hits));
+    }
+}
+
 impl Drop for Svo {
     fn drop(&mut self) {
         unsafe { vx_destroy(self.ctx) }

@@ -178,6 +178,11 @@ extern "C" {
     /// and / or `count` vx_hit records to `hits` (either may be null, not both); `memory`: VX_MEM_HOST / VX_MEM_DEVICE
     pub fn vx_trace_rays(ctx: *mut vx_context, uniforms: *const vx_uniforms, rays: *const vx_ray_batch, count: u32, memory: c_int, rgba: *mut c_void,
                          format: c_int, hits: *mut vx_hit) -> c_int;
+    /// world.glsl:110-141 (main) for every pixel of `count` views of width x height in one launch; `views`: host memory always; view k's pixels
+    /// (in `format`) and vx_hit records at index k * width * height of `rgba` / `hits` (either may be null, not both); `memory` (of the outputs):
+    /// VX_MEM_HOST / VX_MEM_DEVICE
+    pub fn vx_trace_views(ctx: *mut vx_context, views: *const vx_uniforms, count: u32, width: u32, height: u32, memory: c_int, rgba: *mut c_void,
+                          format: c_int, hits: *mut vx_hit) -> c_int;
     /// Physics::step_many (physics.rs:122-136) `steps` times for `count` entities in one launch; `memory`: VX_MEM_HOST / VX_MEM_DEVICE
     pub fn vx_physics_step(ctx: *mut vx_context, entities: *mut vx_entity, count: u32, memory: c_int, delta_time: f32, steps: u32,
                            contacts: *mut vx_aabb_result) -> c_int;

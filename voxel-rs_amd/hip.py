@@ -96,6 +96,7 @@ SYMBOLS = {
     "vx_raycast": (_int, [_vp, _vp, _u32, _vp]),
     "vx_raycast_batch": (_int, [_vp, C.POINTER(RayBatch), _u32, _int, _vp]),
     "vx_trace_rays": (_int, [_vp, C.POINTER(Uniforms), C.POINTER(RayBatch), _u32, _int, _vp, _int, _vp]),
+    "vx_trace_views": (_int, [_vp, C.POINTER(Uniforms), _u32, _u32, _u32, _int, _vp, _int, _vp]),
     "vx_physics_step": (_int, [_vp, _vp, _u32, _int, C.c_float, _u32, _vp]),
     "vx_debug_trace": (_int, [_vp, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.c_float, _int, C.POINTER(Result), _vp, _u32, C.POINTER(_u32)]),
     "vx_sync": (_int, [_vp]),
@@ -532,6 +533,50 @@ class Svo:
                 raise TypeError("trace_rays: an output must be a contiguous CUDA tensor of at least N pixels / records")
         _check(lib().vx_trace_rays(self._h, C.byref(uniforms), C.byref(b), count, VX_MEM_DEVICE, _vp(rgba.data_ptr()) if want_rgba else None, fmt,
                                    _vp(hits.data_ptr()) if want_hits else None))
+        return (rgba if want_rgba else None), (hits if want_hits else None)
+
+    def trace_views(self, views, width, height, want_hits=False, want_rgba=True, fmt=VX_FORMAT_RGBA32F, out=None, device=False):
+        """vx_trace_views: world.glsl's main for every pixel of many small views in one launch. views: a list of Uniforms or a ctypes array of
+        them (host memory always; free to change once the call returns). Returns (pixels, records). pixels: (count, H, W, 4) float32 with row 0
+        at the bottom, or uint8 with the top row first for fmt RGBA8; None with want_rgba=False. records: (count, H * W) vx_hit (HIT_DTYPE) in
+        the row order of that format when want_hits, else None. out: (pixels, records) to write into instead of fresh arrays (either may be None
+        to have a fresh one; they may be longer than needed).
+        Host: synchronous. Device (torch CUDA tensors in `out`, or device=True): returns after enqueueing -- pair with sync(); records are an int32
+        tensor of shape (count, H * W, 12) (trace_hits_to_numpy)."""
+        if not want_rgba and not want_hits:
+            raise TypeError("trace_views: nothing asked for")
+        table = views if isinstance(views, C.Array) else (Uniforms * max(len(views), 1))(*views)
+        count = len(views)
+        n = count * width * height
+        rgba, hits = out if out is not None else (None, None)
+        px_dt, px_bytes = (np.uint8, 4) if fmt == VX_FORMAT_RGBA8 else (np.float32, 16)
+        given = [a for a in (rgba, hits) if a is not None]
+        if given and any(isinstance(a, np.ndarray) != isinstance(given[0], np.ndarray) for a in given):
+            raise TypeError("trace_views: the outputs must both be NumPy arrays or both be torch CUDA tensors")
+        if given:
+            device = not isinstance(given[0], np.ndarray)
+        if not device:
+            if want_rgba and rgba is None:
+                rgba = np.zeros((count, height, width, 4), dtype=px_dt)
+            if want_hits and hits is None:
+                hits = np.zeros((count, height * width), dtype=HIT_DTYPE)
+            for a, size in ((rgba if want_rgba else None, px_bytes), (hits if want_hits else None, HIT_DTYPE.itemsize)):
+                if a is not None and (not isinstance(a, np.ndarray) or a.nbytes < n * size or not a.flags.c_contiguous or not a.flags.writeable):
+                    raise TypeError("trace_views: an output must be a writeable C-contiguous array of at least count * H * W pixels / records")
+            _check(lib().vx_trace_views(self._h, table, count, width, height, VX_MEM_HOST, rgba.ctypes.data_as(_vp) if want_rgba else None, fmt,
+                                        hits.ctypes.data_as(_vp) if want_hits else None))
+            return (rgba if want_rgba else None), (hits if want_hits else None)
+        import torch
+
+        if want_rgba and rgba is None:
+            rgba = torch.empty((count, height, width, 4), dtype=torch.uint8 if fmt == VX_FORMAT_RGBA8 else torch.float32, device="cuda")
+        if want_hits and hits is None:
+            hits = torch.empty((count, height * width, 12), dtype=torch.int32, device="cuda")
+        for a, size in ((rgba if want_rgba else None, px_bytes), (hits if want_hits else None, HIT_DTYPE.itemsize)):
+            if a is not None and (not a.is_cuda or not a.is_contiguous() or a.numel() * a.element_size() < n * size):
+                raise TypeError("trace_views: an output must be a contiguous CUDA tensor of at least count * H * W pixels / records")
+        _check(lib().vx_trace_views(self._h, table, count, width, height, VX_MEM_DEVICE, _vp(rgba.data_ptr()) if want_rgba else None, fmt,
+                                    _vp(hits.data_ptr()) if want_hits else None))
         return (rgba if want_rgba else None), (hits if want_hits else None)
 
     # -- Physics::step_many (src/systems/physics.rs:122-136), on the device ---------------------------------------

@@ -146,6 +146,15 @@ typedef struct vx_ray_hit {
     uint32_t _pad;                /* written 0 */
 } vx_ray_hit;
 
+/* The leaf (or the empty cell) that holds a point (vx_block_points); 8 bytes. */
+typedef struct vx_block_cell {
+    uint32_t value;               /* BlockId stored in the leaf whose cell contains floor(p); 0 = no block there */
+    uint32_t cell_log2;           /* the answering cell is the cube of side 2^cell_log2 aligned to its size that contains floor(p): 0 for a
+                                     full-detail block, 2 for a voxel of a LOD-3 chunk, and for value 0 the size of the empty cell at which
+                                     the descent ended; VX_CELL_OUTSIDE for a point outside [0, 2^depth)^3 */
+} vx_block_cell;
+#define VX_CELL_OUTSIDE 0xFFFFFFFFu
+
 /* Optional per-pixel record of what trace_ray saw (world.glsl:27-90) -- the "hit position, depth" outputs
  * used for parity checks; not part of the reference's surface. */
 typedef struct vx_hit {
@@ -347,6 +356,36 @@ int vx_trace_rays(vx_context* ctx, const vx_uniforms* uniforms, const vx_ray_bat
  * count == 0: VX_OK. Before the first commit: VX_ERR_STATE. */
 int vx_trace_views(vx_context* ctx, const vx_uniforms* views, uint32_t count, uint32_t width, uint32_t height, int memory, void* rgba, int format,
                    vx_hit* hits);
+/* Which block is at each of `count` positions: get_block(floor(pos)) (gameplay.rs:161-201), which the reference asks of its host world, asked
+ * of the world the device holds -- for callers whose positions lie in device memory and who keep no host world. A float[3] is read at
+ * pos + i*pos_stride (pos 4-byte aligned; the stride a multiple of 4 and >= 12): packed [N,3] arrays, vx_entity.position (stride 64) and
+ * vx_ray_hit.pos (pos = &hits[0].pos, stride 32) are read in place, behind an earlier vx_physics_step or vx_raycast_batch on the stream.
+ * out[i] = the leaf, or the empty cell, that holds floor(p): a pure lookup, the descent from the root by the bits of floor(p) through the
+ * world's OWN bytes (ESVO: the child descriptor words get_octant_ptr reads, svo.esvo.glsl:168-173; CSVO: read_next_ptr and read_leaf,
+ * svo.csvo.glsl:53-133, across the chunk boundary with its material section) -- so it holds for deep worlds, worlds beyond 4 GiB, worlds
+ * without a traversal image and LOD chunks, and has none of a ray's start-inside-a-voxel quirks. A component that is NaN, infinite, below
+ * 0 or at or above 2^depth gives {0, VX_CELL_OUTSIDE}; -0.0f is 0. One point a lane.
+ * Memory kinds, ordering and fences are vx_raycast_batch's. VX_MEM_HOST: synchronous; positions and records travel through pinned memory the
+ * kernel reads and writes; one launch, one wait. VX_MEM_DEVICE (out aligned to 8 bytes): enqueued on the context's stream, returns after
+ * enqueueing, ordered behind the commits made so far and earlier batch calls; later commits wait for it; the fence is vx_sync. out must not
+ * overlap pos.
+ * VX_ERR_INVALID_ARGUMENT (its message names the field; nothing is written): a null ctx; an unknown memory kind; null pos or out with
+ * count > 0; a stride that breaks the rule, or a misaligned pos; count > 16777216 (2^24); a misaligned device out. count == 0: VX_OK,
+ * whatever pos, pos_stride and out are (nothing is read or written).
+ * Before the first commit: VX_ERR_STATE. */
+int vx_block_points(vx_context* ctx, const void* pos, uint32_t pos_stride, uint32_t count, int memory, vx_block_cell* out);
+/* The block ids of the box [lo, lo + size) in integer SVO coordinates as a dense array, x fastest: out[((z - lo[2]) * size[1] + (y - lo[1])) *
+ * size[0] + (x - lo[0])] -- a navigation grid, a minimap slice, or the check that the device's world equals a dense array after a run of
+ * commits; the reference would loop get_block (gameplay.rs:161-201) over its host world. Every voxel's value is exactly vx_block_points'
+ * value for that voxel's centre. Cells outside the world are 0: lo may be negative and the box may overhang the world. A workgroup reads one
+ * brick of 8 x 8 x 8 voxels aligned to the world grid: the levels above it once, the last three per voxel.
+ * Memory kinds, ordering and fences are vx_raycast_batch's. VX_MEM_HOST: synchronous, through pinned memory; one launch, one wait.
+ * VX_MEM_DEVICE (out aligned to 4 bytes): enqueued on the context's stream, returns after enqueueing, ordered behind the commits made so far
+ * and earlier batch calls; later commits wait for it; the fence is vx_sync. lo and size themselves are read during the call.
+ * VX_ERR_INVALID_ARGUMENT (its message names the field; nothing is written): a null ctx; an unknown memory kind; null lo or size; size[0] *
+ * size[1] * size[2] > 16777216 (2^24: a 256^3 box; callers tile larger ones); a null out for a box that holds a voxel; a misaligned device
+ * out. Any size component 0: VX_OK. Before the first commit: VX_ERR_STATE. */
+int vx_read_region(vx_context* ctx, const int32_t lo[3], const uint32_t size[3], int memory, uint32_t* out);
 /* Physics::step_many (src/systems/physics.rs:122-136) `steps` times over `count` entities in ONE kernel launch, against the world as last
  * committed: per step and entity the AABB's fan of axis-parallel picker rays (Aabb::generate_picker_tasks, svo_picker.rs:183-243: max_dst
  * 10), folded into six contact distances (parse_picker_results, svo_picker.rs:245-299), then Physics::update_entity and

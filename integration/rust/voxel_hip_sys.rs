@@ -123,6 +123,17 @@ pub struct vx_ray_hit {
     pub _pad: u32,
 }
 
+/// The leaf, or the empty cell, that holds a point (`vx_block_points`): the block id (0 = no block) and log2 of the answering cell's side
+/// (0: a full-detail block), or `VX_CELL_OUTSIDE` for a point outside the world.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct vx_block_cell {
+    pub value: u32,
+    pub cell_log2: u32,
+}
+/// `vx_block_cell::cell_log2` of a point outside [0, 2^depth)^3 (the header's VX_CELL_OUTSIDE)
+pub const VX_CELL_OUTSIDE: u32 = u32::MAX;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct vx_stats {
@@ -149,6 +160,7 @@ const _: () = assert!(std::mem::size_of::<vx_entity>() == 64);
 const _: () = assert!(std::mem::size_of::<vx_aabb_result>() == 24);
 const _: () = assert!(std::mem::size_of::<vx_ray_batch>() == 48);
 const _: () = assert!(std::mem::size_of::<vx_ray_hit>() == 32);
+const _: () = assert!(std::mem::size_of::<vx_block_cell>() == 8);
 const _: () = assert!(std::mem::size_of::<MaterialInstance>() == 32); // svo_registry.rs:29-40 is #[repr(C)]
 const _: () = assert!(std::mem::size_of::<PickerTask>() == 48 && std::mem::size_of::<PickerResult>() == 48); // svo_picker.rs:13-32
 
@@ -183,6 +195,11 @@ extern "C" {
     /// VX_MEM_HOST / VX_MEM_DEVICE
     pub fn vx_trace_views(ctx: *mut vx_context, views: *const vx_uniforms, count: u32, width: u32, height: u32, memory: c_int, rgba: *mut c_void,
                           format: c_int, hits: *mut vx_hit) -> c_int;
+    /// get_block(floor(pos)) (gameplay.rs:161-201) asked of the world the device holds, for `count` positions (a float[3] at pos + i * pos_stride,
+    /// e.g. inside vx_entity or vx_ray_hit records); `memory`: VX_MEM_HOST / VX_MEM_DEVICE
+    pub fn vx_block_points(ctx: *mut vx_context, pos: *const c_void, pos_stride: u32, count: u32, memory: c_int, out: *mut vx_block_cell) -> c_int;
+    /// the block ids of the box [lo, lo + size) as a dense array, x fastest, 0 outside the world; at most 2^24 voxels; `memory`: VX_MEM_HOST / VX_MEM_DEVICE
+    pub fn vx_read_region(ctx: *mut vx_context, lo: *const [i32; 3], size: *const [u32; 3], memory: c_int, out: *mut u32) -> c_int;
     /// Physics::step_many (physics.rs:122-136) `steps` times for `count` entities in one launch; `memory`: VX_MEM_HOST / VX_MEM_DEVICE
     pub fn vx_physics_step(ctx: *mut vx_context, entities: *mut vx_entity, count: u32, memory: c_int, delta_time: f32, steps: u32,
                            contacts: *mut vx_aabb_result) -> c_int;

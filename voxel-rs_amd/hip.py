@@ -34,6 +34,9 @@ ENTITY_WALL_CLIP, ENTITY_FLYING = 1, 2
 # vx_ray_hit (vx_raycast_batch): a PickerResult that keeps the block id and names the normal by its face
 RAY_HIT_DTYPE = np.dtype([("dst", "<f4"), ("value", "<u4"), ("face_id", "<i4"), ("inside_voxel", "<u4"), ("pos", "<f4", 3), ("_pad", "<u4")])
 VX_RAYS_TRANSLUCENT = 1
+# vx_block_cell (vx_block_points): the leaf, or the empty cell, that holds a point
+BLOCK_CELL_DTYPE = np.dtype([("value", "<u4"), ("cell_log2", "<u4")])
+VX_CELL_OUTSIDE = 0xFFFFFFFF
 FACE_NORMALS = np.array([[-1, 0, 0], [1, 0, 0], [0, -1, 0], [0, 1, 0], [0, 0, -1], [0, 0, 1]], dtype=np.float32)  # by face_id
 assert HIT_DTYPE.itemsize == 48 and PICKER_TASK_DTYPE.itemsize == 48 and PICKER_RESULT_DTYPE.itemsize == 48 and FRAME_DTYPE.itemsize == 36
 assert ENTITY_DTYPE.itemsize == 64 and AABB_RESULT_DTYPE.itemsize == 24 and RAY_HIT_DTYPE.itemsize == 32
@@ -97,6 +100,8 @@ SYMBOLS = {
     "vx_raycast_batch": (_int, [_vp, C.POINTER(RayBatch), _u32, _int, _vp]),
     "vx_trace_rays": (_int, [_vp, C.POINTER(Uniforms), C.POINTER(RayBatch), _u32, _int, _vp, _int, _vp]),
     "vx_trace_views": (_int, [_vp, C.POINTER(Uniforms), _u32, _u32, _u32, _int, _vp, _int, _vp]),
+    "vx_block_points": (_int, [_vp, _vp, _u32, _u32, _int, _vp]),
+    "vx_read_region": (_int, [_vp, C.POINTER(C.c_int32 * 3), C.POINTER(_u32 * 3), _int, _vp]),
     "vx_physics_step": (_int, [_vp, _vp, _u32, _int, C.c_float, _u32, _vp]),
     "vx_debug_trace": (_int, [_vp, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.c_float, _int, C.POINTER(Result), _vp, _u32, C.POINTER(_u32)]),
     "vx_sync": (_int, [_vp]),
@@ -264,6 +269,26 @@ def ray_hits_to_numpy(hits):
 def trace_hits_to_numpy(hits):
     """A device record tensor of Svo.trace_rays as HIT_DTYPE records (copies to the host: synchronise first)."""
     return hits.cpu().numpy().view(np.uint8).reshape(-1).view(HIT_DTYPE)
+
+
+def ray_hit_positions(hits):
+    """The positions inside vx_ray_hit records as the points of Svo.block_points: an (N, 3) float32 view at a stride of 32 bytes -- of a
+    NumPy array of RAY_HIT_DTYPE, or of a device hit tensor of Svo.raycast_batch. No copy."""
+    if isinstance(hits, np.ndarray):
+        if hits.dtype != RAY_HIT_DTYPE:
+            raise TypeError("ray_hit_positions: a host array must be of hip.RAY_HIT_DTYPE")
+        return hits.reshape(-1)["pos"]
+    import torch
+
+    nbytes = hits.numel() * hits.element_size()
+    if nbytes % RAY_HIT_DTYPE.itemsize or not hits.is_contiguous():
+        raise TypeError("ray_hit_positions: a device tensor must be contiguous and hold whole 32-byte vx_ray_hit records")
+    return hits.reshape(-1).view(torch.uint8).view(torch.float32).view(-1, 8)[:, 4:7]
+
+
+def block_cells_to_numpy(cells):
+    """A device record tensor of Svo.block_points as BLOCK_CELL_DTYPE records (copies to the host: synchronise first)."""
+    return cells.cpu().numpy().view(np.uint8).reshape(-1).view(BLOCK_CELL_DTYPE)
 
 
 def _ray_vectors(name, x, count, width):
@@ -578,6 +603,61 @@ class Svo:
         _check(lib().vx_trace_views(self._h, table, count, width, height, VX_MEM_DEVICE, _vp(rgba.data_ptr()) if want_rgba else None, fmt,
                                     _vp(hits.data_ptr()) if want_hits else None))
         return (rgba if want_rgba else None), (hits if want_hits else None)
+
+    # -- block ids read from the device (gameplay.rs:161-201: get_block(floor(pos)), asked of the world the device holds) -----------------------
+    def block_points(self, positions, out=None):
+        """vx_block_points: the leaf, or the empty cell, that holds each position (BLOCK_CELL_DTYPE: value, cell_log2).
+        positions: (N, 3) float32 at any row stride (a[:, :3] of an (N, 4) array, entity_positions(e), ray_hit_positions(hits)).
+        Host (a NumPy array): synchronous; returns `out` or a fresh array of BLOCK_CELL_DTYPE.
+        Device (a torch CUDA tensor): returns after enqueueing, without synchronising -- pair with sync(); the records are `out` or a fresh
+        int32 tensor of shape (N, 2) on the positions' device (block_cells_to_numpy)."""
+        host = isinstance(positions, np.ndarray)
+        if len(positions.shape) != 2 or positions.shape[1] != 3:
+            raise TypeError("block_points: positions must have shape (N, 3)")
+        count = int(positions.shape[0])
+        if not host and not getattr(positions, "is_cuda", False):
+            raise TypeError("block_points: positions must be a NumPy array or a torch CUDA tensor")
+        ptr, stride = _ray_vectors("positions", positions, count, 3)
+        if host:
+            if out is None:
+                out = np.zeros(count, dtype=BLOCK_CELL_DTYPE)
+            elif not isinstance(out, np.ndarray) or out.dtype != BLOCK_CELL_DTYPE or out.size != count or not out.flags.c_contiguous or not out.flags.writeable:
+                raise TypeError("block_points: out must be a writeable C-contiguous array of N hip.BLOCK_CELL_DTYPE records")
+            _check(lib().vx_block_points(self._h, _vp(ptr), stride, count, VX_MEM_HOST, out.ctypes.data_as(_vp)))
+            return out
+        import torch
+
+        if out is None:
+            out = torch.empty((count, 2), dtype=torch.int32, device=positions.device)
+        elif not out.is_cuda or not out.is_contiguous() or out.numel() * out.element_size() != count * BLOCK_CELL_DTYPE.itemsize:
+            raise TypeError("block_points: out must be a contiguous CUDA tensor of N x 8 bytes")
+        _check(lib().vx_block_points(self._h, _vp(ptr), stride, count, VX_MEM_DEVICE, _vp(out.data_ptr())))
+        return out
+
+    def read_region(self, lo, size, out=None, device=False):
+        """vx_read_region: the block ids of the box [lo, lo + size) in integer SVO coordinates, 0 outside the world, as a dense uint32 array
+        indexed [z - lo.z][y - lo.y][x - lo.x] (x fastest). At most 2^24 voxels a call.
+        Host (default): synchronous; returns `out` or a fresh NumPy array of shape (size.z, size.y, size.x).
+        Device (device=True, or `out` a torch CUDA tensor): returns after enqueueing, without synchronising -- pair with sync(); the ids
+        are `out` or a fresh int32 tensor of that shape (the bits of the uint32 ids)."""
+        lo3, size3 = (C.c_int32 * 3)(*(int(v) for v in lo)), (_u32 * 3)(*(int(v) for v in size))
+        shape = (int(size[2]), int(size[1]), int(size[0]))
+        voxels = shape[0] * shape[1] * shape[2]
+        if not device and (out is None or isinstance(out, np.ndarray)):
+            if out is None:
+                out = np.zeros(shape, dtype=np.uint32)
+            elif out.dtype != np.uint32 or out.size != voxels or not out.flags.c_contiguous or not out.flags.writeable:
+                raise TypeError("read_region: out must be a writeable C-contiguous uint32 array of size.x * size.y * size.z values")
+            _check(lib().vx_read_region(self._h, C.byref(lo3), C.byref(size3), VX_MEM_HOST, out.ctypes.data_as(_vp)))
+            return out
+        import torch
+
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32, device="cuda")
+        elif not getattr(out, "is_cuda", False) or not out.is_contiguous() or out.numel() * out.element_size() != voxels * 4:
+            raise TypeError("read_region: out must be a contiguous CUDA tensor of size.x * size.y * size.z x 4 bytes")
+        _check(lib().vx_read_region(self._h, C.byref(lo3), C.byref(size3), VX_MEM_DEVICE, _vp(out.data_ptr())))
+        return out
 
     # -- Physics::step_many (src/systems/physics.rs:122-136), on the device ---------------------------------------
     def physics_step(self, entities, dt, steps=1, want_contacts=False, count=None, contacts=None):

@@ -21,16 +21,28 @@ REGIONS = {"glasshouse": ((-3, -3, -3), (70, 70, 70)),  # the whole world and a 
 BUILD = Path(ROOT) / "tests" / "_build"
 
 
+def pick_octants(a):
+    """One level of pick_leaf_for_lod over a dense [x][y][z] array of even sides: per 2 x 2 x 2 cell the first non-zero child in LOD_ORDER."""
+    v = a.reshape(a.shape[0] // 2, 2, a.shape[1] // 2, 2, a.shape[2] // 2, 2)
+    out = np.zeros((a.shape[0] // 2, a.shape[1] // 2, a.shape[2] // 2), dtype=a.dtype)
+    for c in reversed(LOD_ORDER):  # (the first in the order is written last)
+        child = v[:, c & 1, :, (c >> 1) & 1, :, c >> 2]
+        out = np.where(child != 0, child, out)
+    return out
+
+
+def lod_voxels(cell, levels):
+    """What a cell of side 2^levels shows as one voxel, and every aligned cell of that side of a larger array: pick_leaf_for_lod applied
+    recursively -- the first sub-octant, in LOD_ORDER, that holds a block, and so on inside it."""
+    for _ in range(levels):
+        cell = pick_octants(cell)
+    return cell
+
+
 def lod_voxel(cell):
     """The id a 4 x 4 x 4 cell ([x][y][z]) of a LOD-3 chunk shows: the first 2^3 sub-octant, in LOD_ORDER, that holds a block, and in it the
-    first block in the same order; 0 for a cell of air."""
-    for c in LOD_ORDER:
-        sub = cell[2 * (c & 1):2 * (c & 1) + 2, 2 * ((c >> 1) & 1):2 * ((c >> 1) & 1) + 2, 2 * (c >> 2):2 * (c >> 2) + 2]
-        if sub.any():
-            for k in LOD_ORDER:
-                if sub[k & 1, (k >> 1) & 1, k >> 2]:
-                    return int(sub[k & 1, (k >> 1) & 1, k >> 2])
-    return 0
+    first block in the same order; 0 for a cell of air. (The LOD-3 case of lod_voxels.)"""
+    return int(lod_voxels(np.asarray(cell), 2)[0, 0, 0])
 
 
 def truth_of(info):

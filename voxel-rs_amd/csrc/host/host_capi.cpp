@@ -143,6 +143,11 @@ uint64_t vxh_scene_build_heightfield(void* wp, uint32_t depth, uint32_t seed, ui
 }
 
 uint32_t vxh_scene_height(uint32_t depth, uint32_t seed, uint32_t x, uint32_t z) { return heightfield_height(depth, seed, x, z); }
+// The heights of the rectangle [x0, x0 + nx) x [z0, z0 + nz) at once: out[iz * nx + ix] (one call instead of one per column).
+void vxh_scene_heights(uint32_t depth, uint32_t seed, uint32_t x0, uint32_t z0, uint32_t nx, uint32_t nz, uint32_t* out) {
+    for (uint32_t iz = 0; iz < nz; ++iz)
+        for (uint32_t ix = 0; ix < nx; ++ix) out[size_t(iz) * nx + ix] = heightfield_height(depth, seed, x0 + ix, z0 + iz);
+}
 uint32_t vxh_scene_hash32(uint32_t seed, uint32_t o, uint32_t i, uint32_t j) { return scene_hash32(seed, o, i, j); }
 
 // ---- picker batches (src/graphics/svo_picker.rs) --------------------------------------------------------------------

@@ -23,6 +23,9 @@ size_t round16(size_t v) { return (v + 15) & ~size_t(15); }
 // each guarded by an event (like vx_commit's packed uploads, vx_context::DeltaSlot). A call fills the next slot's host buffer -- after waiting for
 // the launch that last read the slot, four calls ago --, queues the copy to its twin and the launch behind it on the context's stream, and records the
 // slot's event there. vx_context cannot grow (vx_pinned_pool.hpp), so the ring lives here: one per device, kept for the life of the process.
+// A slot outlives the context that used it, and an event may not be waited for once the stream it was recorded on is destroyed (the runtime looks
+// at that stream: a later context's call failed in hipEventSynchronize with whatever the freed stream's memory held by then). So the slot's event is
+// recorded on a stream of the ring's own, which is never destroyed and waits for the launch through an event that lives for the call alone.
 struct TableSlot {
     uint8_t* host = nullptr;
     uint8_t* dev = nullptr;
@@ -35,6 +38,7 @@ struct TableRing {
     std::mutex mutex;
     TableSlot slot[kSlots];
     unsigned next = 0;
+    hipStream_t fence = nullptr;  // carries the slots' events; no work of its own
 };
 
 TableRing& table_ring_of(int device) {
@@ -69,6 +73,24 @@ int table_slot_acquire(TableRing& ring, size_t need, TableSlot** out) {
     }
     *out = &s;
     return VX_OK;
+}
+
+// slot.done follows everything queued on `stream` so far, without belonging to it
+hipError_t table_slot_guard(TableRing& ring, TableSlot& slot, hipStream_t stream) {
+    if (!ring.fence)
+        if (const hipError_t e = hipStreamCreateWithFlags(&ring.fence, hipStreamNonBlocking); e != hipSuccess) return e;
+    hipEvent_t queued = nullptr;
+    if (const hipError_t e = hipEventCreateWithFlags(&queued, hipEventDisableTiming); e != hipSuccess) return e;
+    hipError_t e = hipEventRecord(queued, stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(ring.fence, queued, 0);
+    if (e == hipSuccess) e = hipEventRecord(slot.done, ring.fence);
+    (void)hipEventDestroy(queued);  // (released once it has happened)
+    if (e != hipSuccess) {
+        // no guard: the slot may not be handed out again before the launch is through with it
+        (void)hipStreamSynchronize(stream);
+        slot.used = false;
+    }
+    return e;
 }
 
 void fill_table(const vx_uniforms* views, uint32_t count, uint8_t* at) {
@@ -111,7 +133,7 @@ int vx_trace_views(vx_context* ctx, const vx_uniforms* views, uint32_t count, ui
         slot->used = true;  // (from here on the stream may hold work that reads the slot)
         const hipError_t launched = vxk::launch_trace_views(svo, ctx->stream, vxrt::scene_on_bytes(ctx), reinterpret_cast<const ViewParams*>(slot->dev), count,
                                                             width, height, rgba, format, hits);
-        HIP_TRY(hipEventRecord(slot->done, ctx->stream));
+        HIP_TRY(table_slot_guard(ring, *slot, ctx->stream));
         HIP_TRY(launched);
         return vxrt::mark_world_read(ctx);
     }

@@ -65,6 +65,7 @@ def lib():
             "vxh_reference_render_test": (C.c_int, [C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_double), C.c_char_p, sz]),
             "vxh_mapper_raycast_test": (C.c_int, [C.c_int, u32, vp, vp, u32, vp, vp, u32, C.c_float, vp, vp, C.c_char_p, sz]),
             "vxh_scene_height": (u32, [u32, u32, u32, u32]),
+            "vxh_scene_heights": (None, [u32, u32, u32, u32, u32, u32, vp]),
             "vxh_scene_hash32": (u32, [u32, u32, u32, u32]),
         }
         for name, (res, args) in sig.items():
@@ -194,6 +195,13 @@ class World:
 
 def scene_height(depth, seed, x, z):
     return lib().vxh_scene_height(depth, seed, x, z)
+
+
+def scene_heights(depth, seed, x0, z0, nx, nz):
+    """scene_height of every column of the rectangle [x0, x0 + nx) x [z0, z0 + nz) in one call: uint32 [z - z0][x - x0]."""
+    out = np.zeros((nz, nx), dtype=np.uint32)
+    lib().vxh_scene_heights(depth, seed, x0, z0, nx, nz, out.ctypes.data_as(C.c_void_p))
+    return out
 
 
 PICKER_TASK_DTYPE = np.dtype([("max_dst", "<f4"), ("_p0", "<f4", 3), ("pos", "<f4", 3), ("_p1", "<f4"), ("dir", "<f4", 3), ("_p2", "<f4")])

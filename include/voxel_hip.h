@@ -155,6 +155,26 @@ typedef struct vx_block_cell {
 } vx_block_cell;
 #define VX_CELL_OUTSIDE 0xFFFFFFFFu
 
+/* directions of travel of a scan (vx_scan_points, vx_scan_columns), numbered like face_id */
+#define VX_DIR_NEG_X 0
+#define VX_DIR_POS_X 1
+#define VX_DIR_NEG_Y 2            /* downwards: a heightmap */
+#define VX_DIR_POS_Y 3
+#define VX_DIR_NEG_Z 4
+#define VX_DIR_POS_Z 5
+#define VX_SCAN_NONE ((int32_t)0x80000000) /* vx_scan_hit.coord when no block was found */
+#define VX_SCAN_TO_EDGE 0xFFFFFFFFu        /* reach: as far as the world goes */
+
+/* The first voxel holding a block along an axis (vx_scan_points, vx_scan_columns); 16 bytes. */
+typedef struct vx_scan_hit {
+    int32_t coord;                /* its coordinate ALONG THE SCAN AXIS (the other two are the column's); VX_SCAN_NONE: none */
+    uint32_t value;               /* its BlockId; 0 = none */
+    uint32_t cell_log2;           /* the answering leaf is the aligned cube of side 2^cell_log2 holding that voxel (0 full detail, 2 a voxel
+                                     of a LOD-3 chunk, ...); 0 for none; VX_CELL_OUTSIDE for a position that is no position (a NaN or
+                                     infinite component; points only) */
+    uint32_t _pad;                /* written 0 */
+} vx_scan_hit;
+
 /* Optional per-pixel record of what trace_ray saw (world.glsl:27-90) -- the "hit position, depth" outputs
  * used for parity checks; not part of the reference's surface. */
 typedef struct vx_hit {
@@ -386,6 +406,35 @@ int vx_block_points(vx_context* ctx, const void* pos, uint32_t pos_stride, uint3
  * size[1] * size[2] > 16777216 (2^24: a 256^3 box; callers tile larger ones); a null out for a box that holds a voxel; a misaligned device
  * out. Any size component 0: VX_OK. Before the first commit: VX_ERR_STATE. */
 int vx_read_region(vx_context* ctx, const int32_t lo[3], const uint32_t size[3], int memory, uint32_t* out);
+/* The first block below (above, beside) each of `count` positions: get_block (gameplay.rs:161-201) looped along an axis, asked of the world
+ * the device holds -- the ground under every entity, the ceiling over it, which positions see the sky. Positions are gathered exactly as
+ * vx_block_points gathers them (packed arrays, vx_entity.position, vx_ray_hit.pos in place). start = floor(p) per component, saturated to
+ * int32; the scan visits the voxels start, start +- 1, ... along the axis of `direction` (VX_DIR_*), `reach` of them at the most (start
+ * included; VX_SCAN_TO_EDGE: up to the world's far edge), and answers with the first whose value -- vx_block_points' value for the voxel's
+ * centre; air outside [0, 2^depth)^3 -- is not 0: its coordinate on that axis, the value, and the leaf's cell_log2. The start voxel
+ * counts: a scan that starts inside a block or a LOD voxel answers coord = start. A LOD voxel entered from outside answers with its near
+ * face in travel order. No block: {VX_SCAN_NONE, 0, 0, 0}. A NaN or infinite component: {VX_SCAN_NONE, 0, VX_CELL_OUTSIDE, 0}. A finite
+ * position outside the world is a valid start (the scan may enter the world). Integer-only and exact like vx_block_points; empty space is
+ * stepped over a whole empty cell of the octree at a time, so a scan from the top of a deep world takes a few dozen descents, not one a
+ * voxel. One column a lane.
+ * Memory kinds, ordering and fences are vx_block_points'. VX_MEM_DEVICE: out aligned to 16 bytes. out must not overlap pos.
+ * VX_ERR_INVALID_ARGUMENT (its message names the field; nothing is written): a null ctx; an unknown memory kind; a direction outside
+ * 0..5; with count > 0: vx_block_points' stride, alignment and null rules, count > 16777216 (2^24), reach == 0, a misaligned device out.
+ * count == 0: VX_OK. Before the first commit: VX_ERR_STATE. */
+int vx_scan_points(vx_context* ctx, const void* pos, uint32_t pos_stride, uint32_t count, int direction, uint32_t reach, int memory,
+                   vx_scan_hit* out);
+/* The same scan for every column of the box [lo, lo + size) in integer SVO coordinates (as in vx_read_region: lo may be negative, the box
+ * may overhang the world), as a dense array: a heightmap, a sky mask, an orthographic elevation along any axis. With a the axis of
+ * `direction` and u < v the two other axes in x, y, z order there is one column per (u, v) of the box; it scans the box's extent along a
+ * from the face it enters (start = lo[a] + size[a] - 1 for a negative direction, lo[a] for a positive one) and its record goes to
+ * out[(v - lo[v]) * size[u] + (u - lo[u])]: a top-down heightmap (VX_DIR_NEG_Y) is [z][x]. A wave owns a tile of 8 x 8 columns aligned to
+ * the world grid and walks the bricks along the axis: the levels above a brick once for the whole wave, empty cells stepped over by the whole
+ * wave, the last three levels per lane.
+ * Memory kinds, ordering and fences are vx_block_points'. VX_MEM_DEVICE: out aligned to 16 bytes.
+ * VX_ERR_INVALID_ARGUMENT (its message names the field; nothing is written): a null ctx; an unknown memory kind; a direction outside
+ * 0..5; null lo or size; size[u] * size[v] > 16777216 (2^24) columns; size[a] > 16777216; a null out for a box that holds a voxel; a
+ * misaligned device out. Any size component 0: VX_OK. Before the first commit: VX_ERR_STATE. */
+int vx_scan_columns(vx_context* ctx, const int32_t lo[3], const uint32_t size[3], int direction, int memory, vx_scan_hit* out);
 /* Physics::step_many (src/systems/physics.rs:122-136) `steps` times over `count` entities in ONE kernel launch, against the world as last
  * committed: per step and entity the AABB's fan of axis-parallel picker rays (Aabb::generate_picker_tasks, svo_picker.rs:183-243: max_dst
  * 10), folded into six contact distances (parse_picker_results, svo_picker.rs:245-299), then Physics::update_entity and

@@ -134,6 +134,28 @@ pub struct vx_block_cell {
 /// `vx_block_cell::cell_log2` of a point outside [0, 2^depth)^3 (the header's VX_CELL_OUTSIDE)
 pub const VX_CELL_OUTSIDE: u32 = u32::MAX;
 
+/// The first voxel holding a block along an axis (`vx_scan_points`, `vx_scan_columns`): its coordinate along the scan axis (`VX_SCAN_NONE`:
+/// no block), its block id and log2 of the answering leaf's side (`VX_CELL_OUTSIDE`: a position with a NaN or infinite component).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct vx_scan_hit {
+    pub coord: i32,
+    pub value: u32,
+    pub cell_log2: u32,
+    pub _pad: u32,
+}
+/// directions of travel of a scan, numbered like `face_id`
+pub const VX_DIR_NEG_X: c_int = 0;
+pub const VX_DIR_POS_X: c_int = 1;
+pub const VX_DIR_NEG_Y: c_int = 2;
+pub const VX_DIR_POS_Y: c_int = 3;
+pub const VX_DIR_NEG_Z: c_int = 4;
+pub const VX_DIR_POS_Z: c_int = 5;
+/// `vx_scan_hit::coord` when no block was found (the header's VX_SCAN_NONE)
+pub const VX_SCAN_NONE: i32 = i32::MIN;
+/// `reach`: as far as the world goes (the header's VX_SCAN_TO_EDGE)
+pub const VX_SCAN_TO_EDGE: u32 = u32::MAX;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct vx_stats {
@@ -161,6 +183,7 @@ const _: () = assert!(std::mem::size_of::<vx_aabb_result>() == 24);
 const _: () = assert!(std::mem::size_of::<vx_ray_batch>() == 48);
 const _: () = assert!(std::mem::size_of::<vx_ray_hit>() == 32);
 const _: () = assert!(std::mem::size_of::<vx_block_cell>() == 8);
+const _: () = assert!(std::mem::size_of::<vx_scan_hit>() == 16);
 const _: () = assert!(std::mem::size_of::<MaterialInstance>() == 32); // svo_registry.rs:29-40 is #[repr(C)]
 const _: () = assert!(std::mem::size_of::<PickerTask>() == 48 && std::mem::size_of::<PickerResult>() == 48); // svo_picker.rs:13-32
 
@@ -200,6 +223,13 @@ extern "C" {
     pub fn vx_block_points(ctx: *mut vx_context, pos: *const c_void, pos_stride: u32, count: u32, memory: c_int, out: *mut vx_block_cell) -> c_int;
     /// the block ids of the box [lo, lo + size) as a dense array, x fastest, 0 outside the world; at most 2^24 voxels; `memory`: VX_MEM_HOST / VX_MEM_DEVICE
     pub fn vx_read_region(ctx: *mut vx_context, lo: *const [i32; 3], size: *const [u32; 3], memory: c_int, out: *mut u32) -> c_int;
+    /// the first block from floor(pos) on along `direction` (VX_DIR_*), at most `reach` voxels on (the start counts; VX_SCAN_TO_EDGE: to the
+    /// world's edge), for `count` positions read as vx_block_points reads them; `memory`: VX_MEM_HOST / VX_MEM_DEVICE
+    pub fn vx_scan_points(ctx: *mut vx_context, pos: *const c_void, pos_stride: u32, count: u32, direction: c_int, reach: u32, memory: c_int,
+                          out: *mut vx_scan_hit) -> c_int;
+    /// the same scan for every column of the box [lo, lo + size) across the axis of `direction`, from the face it enters, as a dense array
+    /// [v - lo[v]][u - lo[u]] (u < v the two other axes; VX_DIR_NEG_Y: a heightmap [z][x]); `memory`: VX_MEM_HOST / VX_MEM_DEVICE
+    pub fn vx_scan_columns(ctx: *mut vx_context, lo: *const [i32; 3], size: *const [u32; 3], direction: c_int, memory: c_int, out: *mut vx_scan_hit) -> c_int;
     /// Physics::step_many (physics.rs:122-136) `steps` times for `count` entities in one launch; `memory`: VX_MEM_HOST / VX_MEM_DEVICE
     pub fn vx_physics_step(ctx: *mut vx_context, entities: *mut vx_entity, count: u32, memory: c_int, delta_time: f32, steps: u32,
                            contacts: *mut vx_aabb_result) -> c_int;

@@ -17,24 +17,14 @@
 #include "kernels_blocks.h"
 #include "vx_device.hpp"
 #include "vx_ray_batch.hpp"
+#include "vx_world_bytes.hpp"
 
 using namespace vxd;
 
 namespace {
 
-// vx_blocks.hpp's reader on a DevScene: VX_SVO_ESVO and VX_SVO_CSVO through the buffer resource (range-checked by the hardware),
-// VX_SVO_ESVO_BIG through Trav's 64-bit address with its explicit check
-template <int SVO>
-struct WorldBytes {
-    DevScene sc;
-    __device__ __forceinline__ uint32_t head() const { return __float_as_uint(sc.octree_scale); }
-    __device__ __forceinline__ uint32_t root_ptr() const { return sc.root_ptr; }
-    __device__ __forceinline__ uint32_t word(uint32_t i) const { return Trav<SVO>::word(sc, i); }
-    __device__ __forceinline__ uint32_t c32(uint32_t p) const { return csvo_u32(sc, p); }
-    __device__ __forceinline__ uint32_t c8(uint32_t p) const { return csvo_u8(sc, p); }
-};
-template <int SVO>
-constexpr int kFormat = SVO == VX_SVO_CSVO ? vxb::kCsvo : vxb::kEsvo;
+using vxk::kFormat;
+using vxk::WorldBytes;  // (vx_world_bytes.hpp: vx_blocks.hpp's reader on a DevScene)
 
 template <int SVO>
 __global__ __launch_bounds__(64) void block_points_kernel(SceneArgs sa, const uint8_t* __restrict__ pos, uint32_t pos_stride, uint32_t n,

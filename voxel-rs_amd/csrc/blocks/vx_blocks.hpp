@@ -195,18 +195,24 @@ struct Brick {
     Cursor at;           // where the descent stands at the brick's cell, or where it ended above it
 };
 
+// the brick at `corner`: the descent from the root to its cell, or to where it ends above it
 template <int FMT, class W>
-VXB_FN Brick enter_brick(const W& w, const Region& r, uint32_t brick) {
+VXB_FN Brick enter_brick_at(const W& w, uint32_t cx, uint32_t cy, uint32_t cz) {
     Brick b;
-    const uint32_t bx = brick % r.count[0], byz = brick / r.count[0];
-    b.corner[0] = r.first[0] + bx * kBrick;
-    b.corner[1] = r.first[1] + (byz % r.count[1]) * kBrick;
-    b.corner[2] = r.first[2] + (byz / r.count[1]) * kBrick;
+    b.corner[0] = cx;
+    b.corner[1] = cy;
+    b.corner[2] = cz;
     b.at = root<FMT>(w);
     const uint32_t edge = 1u << b.at.level;
     b.inside = (b.corner[0] < edge && b.corner[1] < edge && b.corner[2] < edge) ? 1u : 0u;
     if (b.inside) descend<FMT>(w, b.at, b.corner[0], b.corner[1], b.corner[2], kBrickLog2);
     return b;
+}
+
+template <int FMT, class W>
+VXB_FN Brick enter_brick(const W& w, const Region& r, uint32_t brick) {
+    const uint32_t bx = brick % r.count[0], byz = brick / r.count[0];
+    return enter_brick_at<FMT>(w, r.first[0] + bx * kBrick, r.first[1] + (byz % r.count[1]) * kBrick, r.first[2] + (byz / r.count[1]) * kBrick);
 }
 
 // Where in `out` voxel (i, j, k) of the brick, 0..7 each, belongs; false: it lies outside the box.
@@ -224,29 +230,60 @@ VXB_FN Cursor step_live(const W& w, const Cursor& c, uint32_t idx) {
     return c.done ? c : n;
 }
 
+// A column of a brick runs along `axis`; its lane's (i, j) lie on the two other axes u < v in x, y, z order (axis 2: the (x, y) of
+// vx_read_region). The child index x | y << 1 | z << 2 of the column's step h along the axis at one level, uv = u's bit | v's bit << 1:
+VXB_FN uint32_t column_child(uint32_t axis, uint32_t uv, uint32_t h) {
+    const uint32_t below = (1u << axis) - 1u;
+    return (uv & below) | (h << axis) | ((uv & ~below) << 1);
+}
+// ... and the voxel (u, v, a) of such a column as (x, y, z)
+VXB_FN void column_xyz(uint32_t axis, uint32_t u, uint32_t v, uint32_t a, uint32_t& x, uint32_t& y, uint32_t& z) {
+    x = axis == 0 ? a : u;
+    y = axis == 1 ? a : (axis == 0 ? u : v);
+    z = axis == 2 ? a : v;
+}
+
 // The eight voxels (i, j, 0..7) of the brick, a lane's share: the last three levels of the descent, level by level -- the column's two
 // cells of 4, its four cells of 2, its eight voxels: 14 steps, those of a level independent of one another -- or none of it where the
-// brick's own descent ended above it (empty space, a LOD voxel of 8 and more, outside the world).
-template <int FMT, class W>
-VXB_FN void brick_column(const W& w, const Brick& b, uint32_t i, uint32_t j, uint32_t value[kBrick]) {
+// brick's own descent ended above it (empty space, a LOD voxel of 8 and more, outside the world). KEEP_LEVEL: `level` receives log2 of the
+// leaf, or of the empty cell, that answers for each voxel (vx_scan.hpp); without it `level` is not touched.
+template <int FMT, bool KEEP_LEVEL, class W>
+VXB_FN void brick_column_along(const W& w, const Brick& b, uint32_t axis, uint32_t i, uint32_t j, uint32_t value[kBrick], uint32_t* level) {
     // (wave-uniform: the brick is the wave's) outside the world, or the brick's own descent ended above it: the fill, with no load
     const uint32_t fill = (b.inside && b.at.done) ? b.at.value : 0u;
-    for (uint32_t k = 0; k < kBrick; ++k) value[k] = fill;
+    for (uint32_t k = 0; k < kBrick; ++k) {
+        value[k] = fill;
+        if (KEEP_LEVEL) level[k] = b.at.level;
+    }
     if (!b.inside || b.at.done) return;
     if (b.at.level < kBrickLog2) {  // a world smaller than a brick: voxel by voxel, those that lie in it
-        const uint32_t x = b.corner[0] + i, y = b.corner[1] + j, world = 1u << b.at.level;
+        const uint32_t world = 1u << b.at.level;
         for (uint32_t k = 0; k < kBrick; ++k) {
+            uint32_t o[3];
+            column_xyz(axis, i, j, k, o[0], o[1], o[2]);
+            const uint32_t x = b.corner[0] + o[0], y = b.corner[1] + o[1], z = b.corner[2] + o[2];
             Cursor c = b.at;
-            if (x < world && y < world && b.corner[2] + k < world) descend<FMT>(w, c, x, y, b.corner[2] + k, 0);
+            if (x < world && y < world && z < world) descend<FMT>(w, c, x, y, z, 0);
             value[k] = c.value;
+            if (KEEP_LEVEL) level[k] = c.level;
         }
         return;
     }
-    const uint32_t xy2 = ((i >> 2) & 1u) | (((j >> 2) & 1u) << 1), xy1 = ((i >> 1) & 1u) | (((j >> 1) & 1u) << 1), xy0 = (i & 1u) | ((j & 1u) << 1);
+    const uint32_t uv2 = ((i >> 2) & 1u) | (((j >> 2) & 1u) << 1), uv1 = ((i >> 1) & 1u) | (((j >> 1) & 1u) << 1), uv0 = (i & 1u) | ((j & 1u) << 1);
     Cursor c2[2], c1[4];
-    for (uint32_t h = 0; h < 2; ++h) c2[h] = step_live<FMT>(w, b.at, xy2 | (h << 2));
-    for (uint32_t q = 0; q < 4; ++q) c1[q] = step_live<FMT>(w, c2[q >> 1], xy1 | ((q & 1u) << 2));
-    for (uint32_t k = 0; k < kBrick; ++k) value[k] = step_live<FMT>(w, c1[k >> 1], xy0 | ((k & 1u) << 2)).value;  // (no leaf at a single voxel: 0)
+    for (uint32_t h = 0; h < 2; ++h) c2[h] = step_live<FMT>(w, b.at, column_child(axis, uv2, h));
+    for (uint32_t q = 0; q < 4; ++q) c1[q] = step_live<FMT>(w, c2[q >> 1], column_child(axis, uv1, q & 1u));
+    for (uint32_t k = 0; k < kBrick; ++k) {
+        const Cursor c0 = step_live<FMT>(w, c1[k >> 1], column_child(axis, uv0, k & 1u));
+        value[k] = c0.value;  // (no leaf at a single voxel: 0)
+        if (KEEP_LEVEL) level[k] = c0.level;
+    }
+}
+
+// vx_read_region's columns run along z
+template <int FMT, class W>
+VXB_FN void brick_column(const W& w, const Brick& b, uint32_t i, uint32_t j, uint32_t value[kBrick]) {
+    brick_column_along<FMT, false>(w, b, 2u, i, j, value, nullptr);
 }
 
 // the whole region on one thread: what the kernel's lanes do, brick by brick (the host test harness)

@@ -37,9 +37,14 @@ VX_RAYS_TRANSLUCENT = 1
 # vx_block_cell (vx_block_points): the leaf, or the empty cell, that holds a point
 BLOCK_CELL_DTYPE = np.dtype([("value", "<u4"), ("cell_log2", "<u4")])
 VX_CELL_OUTSIDE = 0xFFFFFFFF
+# vx_scan_hit (vx_scan_points, vx_scan_columns): the first voxel holding a block along an axis; directions numbered like face_id
+SCAN_HIT_DTYPE = np.dtype([("coord", "<i4"), ("value", "<u4"), ("cell_log2", "<u4"), ("_pad", "<u4")])
+VX_DIR_NEG_X, VX_DIR_POS_X, VX_DIR_NEG_Y, VX_DIR_POS_Y, VX_DIR_NEG_Z, VX_DIR_POS_Z = range(6)
+VX_SCAN_NONE = -0x80000000
+VX_SCAN_TO_EDGE = 0xFFFFFFFF
 FACE_NORMALS = np.array([[-1, 0, 0], [1, 0, 0], [0, -1, 0], [0, 1, 0], [0, 0, -1], [0, 0, 1]], dtype=np.float32)  # by face_id
 assert HIT_DTYPE.itemsize == 48 and PICKER_TASK_DTYPE.itemsize == 48 and PICKER_RESULT_DTYPE.itemsize == 48 and FRAME_DTYPE.itemsize == 36
-assert ENTITY_DTYPE.itemsize == 64 and AABB_RESULT_DTYPE.itemsize == 24 and RAY_HIT_DTYPE.itemsize == 32
+assert ENTITY_DTYPE.itemsize == 64 and AABB_RESULT_DTYPE.itemsize == 24 and RAY_HIT_DTYPE.itemsize == 32 and SCAN_HIT_DTYPE.itemsize == 16
 
 COUNTER_FIELDS = ["rays", "iterations", "pushes", "leaf_tests", "leaf_tests_trilinear", "boundaries", "csvo_header_bytes", "csvo_pointer_bytes",
                   "pixels", "lit_pixels", "shadow_rays", "wave_steps", "services", "refills", "tail_wave_steps", "tail_iterations"]
@@ -102,6 +107,8 @@ SYMBOLS = {
     "vx_trace_views": (_int, [_vp, C.POINTER(Uniforms), _u32, _u32, _u32, _int, _vp, _int, _vp]),
     "vx_block_points": (_int, [_vp, _vp, _u32, _u32, _int, _vp]),
     "vx_read_region": (_int, [_vp, C.POINTER(C.c_int32 * 3), C.POINTER(_u32 * 3), _int, _vp]),
+    "vx_scan_points": (_int, [_vp, _vp, _u32, _u32, _int, _u32, _int, _vp]),
+    "vx_scan_columns": (_int, [_vp, C.POINTER(C.c_int32 * 3), C.POINTER(_u32 * 3), _int, _int, _vp]),
     "vx_physics_step": (_int, [_vp, _vp, _u32, _int, C.c_float, _u32, _vp]),
     "vx_debug_trace": (_int, [_vp, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.c_float, _int, C.POINTER(Result), _vp, _u32, C.POINTER(_u32)]),
     "vx_sync": (_int, [_vp]),
@@ -289,6 +296,12 @@ def ray_hit_positions(hits):
 def block_cells_to_numpy(cells):
     """A device record tensor of Svo.block_points as BLOCK_CELL_DTYPE records (copies to the host: synchronise first)."""
     return cells.cpu().numpy().view(np.uint8).reshape(-1).view(BLOCK_CELL_DTYPE)
+
+
+def scan_hits_to_numpy(hits):
+    """A device record tensor of Svo.scan_points or Svo.scan_columns as SCAN_HIT_DTYPE records, in the tensor's shape without its last axis
+    (copies to the host: synchronise first)."""
+    return hits.cpu().numpy().view(np.uint8).reshape(-1).view(SCAN_HIT_DTYPE).reshape(tuple(hits.shape[:-1]))
 
 
 def _ray_vectors(name, x, count, width):
@@ -657,6 +670,64 @@ class Svo:
         elif not getattr(out, "is_cuda", False) or not out.is_contiguous() or out.numel() * out.element_size() != voxels * 4:
             raise TypeError("read_region: out must be a contiguous CUDA tensor of size.x * size.y * size.z x 4 bytes")
         _check(lib().vx_read_region(self._h, C.byref(lo3), C.byref(size3), VX_MEM_DEVICE, _vp(out.data_ptr())))
+        return out
+
+    # -- the first block along an axis (get_block, gameplay.rs:161-201, looped along it) ----------------------------------------------------------
+    def scan_points(self, positions, direction, reach=VX_SCAN_TO_EDGE, out=None):
+        """vx_scan_points: the first block from floor(position) on along `direction` (VX_DIR_*), at most `reach` voxels on, the start included
+        (SCAN_HIT_DTYPE: coord along the axis or VX_SCAN_NONE, value, cell_log2). positions: as block_points takes them.
+        Host (a NumPy array): synchronous; returns `out` or a fresh array of SCAN_HIT_DTYPE.
+        Device (a torch CUDA tensor): returns after enqueueing, without synchronising -- pair with sync(); the records are `out` or a fresh
+        int32 tensor of shape (N, 4) on the positions' device (scan_hits_to_numpy)."""
+        host = isinstance(positions, np.ndarray)
+        if len(positions.shape) != 2 or positions.shape[1] != 3:
+            raise TypeError("scan_points: positions must have shape (N, 3)")
+        count = int(positions.shape[0])
+        if not host and not getattr(positions, "is_cuda", False):
+            raise TypeError("scan_points: positions must be a NumPy array or a torch CUDA tensor")
+        ptr, stride = _ray_vectors("positions", positions, count, 3)
+        if host:
+            if out is None:
+                out = np.zeros(count, dtype=SCAN_HIT_DTYPE)
+            elif not isinstance(out, np.ndarray) or out.dtype != SCAN_HIT_DTYPE or out.size != count or not out.flags.c_contiguous or not out.flags.writeable:
+                raise TypeError("scan_points: out must be a writeable C-contiguous array of N hip.SCAN_HIT_DTYPE records")
+            _check(lib().vx_scan_points(self._h, _vp(ptr), stride, count, int(direction), int(reach), VX_MEM_HOST, out.ctypes.data_as(_vp)))
+            return out
+        import torch
+
+        if out is None:
+            out = torch.empty((count, 4), dtype=torch.int32, device=positions.device)
+        elif not out.is_cuda or not out.is_contiguous() or out.numel() * out.element_size() != count * SCAN_HIT_DTYPE.itemsize:
+            raise TypeError("scan_points: out must be a contiguous CUDA tensor of N x 16 bytes")
+        _check(lib().vx_scan_points(self._h, _vp(ptr), stride, count, int(direction), int(reach), VX_MEM_DEVICE, _vp(out.data_ptr())))
+        return out
+
+    def scan_columns(self, lo, size, direction, out=None, device=False):
+        """vx_scan_columns: per column of the box [lo, lo + size) across the axis of `direction` (VX_DIR_*), the first block from the face the
+        scan enters, as a dense array of SCAN_HIT_DTYPE indexed [v - lo.v][u - lo.u], u < v the two other axes (VX_DIR_NEG_Y: a heightmap
+        [z][x]). At most 2^24 columns a call.
+        Host (default): synchronous; returns `out` or a fresh NumPy array of shape (size.v, size.u).
+        Device (device=True, or `out` a torch CUDA tensor): returns after enqueueing, without synchronising -- pair with sync(); the records
+        are `out` or a fresh int32 tensor of shape (size.v, size.u, 4) (scan_hits_to_numpy)."""
+        lo3, size3 = (C.c_int32 * 3)(*(int(v) for v in lo)), (_u32 * 3)(*(int(v) for v in size))
+        a = int(direction) >> 1
+        u, v = (1 if a == 0 else 0), (1 if a == 2 else 2)
+        shape = (int(size[v]), int(size[u])) if 0 <= a <= 2 else (0, 0)
+        columns = shape[0] * shape[1] if all(int(n) for n in size) else 0
+        if not device and (out is None or isinstance(out, np.ndarray)):
+            if out is None:
+                out = np.zeros(shape if columns else (0, 0), dtype=SCAN_HIT_DTYPE)
+            elif out.dtype != SCAN_HIT_DTYPE or out.size != columns or not out.flags.c_contiguous or not out.flags.writeable:
+                raise TypeError("scan_columns: out must be a writeable C-contiguous array of size.u * size.v hip.SCAN_HIT_DTYPE records")
+            _check(lib().vx_scan_columns(self._h, C.byref(lo3), C.byref(size3), int(direction), VX_MEM_HOST, out.ctypes.data_as(_vp)))
+            return out
+        import torch
+
+        if out is None:
+            out = torch.empty((shape if columns else (0, 0)) + (4,), dtype=torch.int32, device="cuda")
+        elif not getattr(out, "is_cuda", False) or not out.is_contiguous() or out.numel() * out.element_size() != columns * SCAN_HIT_DTYPE.itemsize:
+            raise TypeError("scan_columns: out must be a contiguous CUDA tensor of size.u * size.v x 16 bytes")
+        _check(lib().vx_scan_columns(self._h, C.byref(lo3), C.byref(size3), int(direction), VX_MEM_DEVICE, _vp(out.data_ptr())))
         return out
 
     # -- Physics::step_many (src/systems/physics.rs:122-136), on the device ---------------------------------------

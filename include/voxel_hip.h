@@ -406,6 +406,43 @@ int vx_block_points(vx_context* ctx, const void* pos, uint32_t pos_stride, uint3
  * size[1] * size[2] > 16777216 (2^24: a 256^3 box; callers tile larger ones); a null out for a box that holds a voxel; a misaligned device
  * out. Any size component 0: VX_OK. Before the first commit: VX_ERR_STATE. */
 int vx_read_region(vx_context* ctx, const int32_t lo[3], const uint32_t size[3], int memory, uint32_t* out);
+/* The blocks the box [lo, lo + size) actually holds, as a compact list, with the faces of each that touch air: what a caller builds a collision
+ * or render mesh from, exports a selection with, scatters particles on, or removes in an explosion -- the reference would loop get_block
+ * (gameplay.rs:161-201) over the box, and over each block's six neighbours. A dense vx_read_region of terrain is almost all air and buried
+ * rock; this is its non-zero voxels only, or -- VX_LIST_EXPOSED -- only those that can be seen.
+ * Which voxels: a record for every voxel of the box whose vx_read_region value is not 0; under VX_LIST_EXPOSED only those of them with a
+ * face bit set. A LOD voxel of side 2^k gives one record per fine voxel of it inside the box, as vx_read_region does; its inner voxels have
+ * no open face.
+ * Faces: a neighbour is judged by the world -- vx_block_points' value at that voxel's centre, and air outside [0, 2^depth)^3 -- whether or
+ * not it lies in the box: the lists of two boxes that tile a larger one are the larger one's list with `where` re-based. Translucent blocks
+ * count as blocks.
+ * Order: fixed and reproducible, ascending by (z >> 3, y >> 3, x >> 3, z, y, x) in world coordinates: brick by brick of the 8 x 8 x 8 grid
+ * vx_read_region's workgroups own, x fastest, and inside a brick in dense-index order.
+ * total and capacity: *total receives the number of records the box has under `flags`, whatever `capacity` is; the first min(total, capacity)
+ * records in that order are written to `out`, and nothing beyond them. capacity == 0 only counts; out may then be null.
+ * Three launches on the context's stream, one wave a brick in the first and the last: the records of each brick counted, the counts summed
+ * into offsets (no kernel waits for another workgroup), the records written.
+ * `memory` is the kind of `out` and `total`; ordering and fences are vx_read_region's. VX_MEM_HOST: synchronous, through pinned memory; only
+ * the records written are copied back. VX_MEM_DEVICE (out aligned to 8 bytes, total to 4): enqueued on the context's stream, returns after
+ * enqueueing; later commits wait for it; the fence is vx_sync. lo and size themselves are read during the call.
+ * VX_ERR_INVALID_ARGUMENT (its message names the field; nothing is written): a null ctx; an unknown memory kind; an unknown bit in flags;
+ * null lo or size; size[0] * size[1] * size[2] > 16777216 (2^24, vx_read_region's limit: 24 bits hold the index); a null total for a box
+ * that holds a voxel; a null out with capacity > 0 for such a box; a misaligned device out or total. Any size component 0: VX_OK, *total = 0
+ * is written if total is not null, out is not touched. Before the first commit: VX_ERR_STATE. */
+#define VX_LIST_FACES   1u  /* fill each record's face bits */
+#define VX_LIST_EXPOSED 2u  /* keep only blocks with at least one face bit set; implies VX_LIST_FACES */
+/* One block of a box; 8 bytes. */
+typedef struct vx_block_at {
+    uint32_t where;  /* bits 0..23: the voxel's index in vx_read_region's dense array for the same box,
+                        ((z-lo[2])*size[1] + (y-lo[1]))*size[0] + (x-lo[0]);
+                        bits 24..29: faces, bit f (numbered like face_id: -x,+x,-y,+y,-z,+z) set when the neighbouring voxel
+                        on that side holds no block; 0 without VX_LIST_FACES; bits 30..31: 0 */
+    uint32_t value;  /* its BlockId, never 0 */
+} vx_block_at;
+#define VX_AT_INDEX(where) ((where) & 0xFFFFFFu)
+#define VX_AT_FACES(where) (((where) >> 24) & 0x3Fu)
+int vx_list_region(vx_context* ctx, const int32_t lo[3], const uint32_t size[3], uint32_t flags, int memory,
+                   vx_block_at* out, uint32_t capacity, uint32_t* total);
 /* The first block below (above, beside) each of `count` positions: get_block (gameplay.rs:161-201) looped along an axis, asked of the world
  * the device holds -- the ground under every entity, the ceiling over it, which positions see the sky. Positions are gathered exactly as
  * vx_block_points gathers them (packed arrays, vx_entity.position, vx_ray_hit.pos in place). start = floor(p) per component, saturated to

@@ -134,6 +134,21 @@ pub struct vx_block_cell {
 /// `vx_block_cell::cell_log2` of a point outside [0, 2^depth)^3 (the header's VX_CELL_OUTSIDE)
 pub const VX_CELL_OUTSIDE: u32 = u32::MAX;
 
+/// One block of a box (`vx_list_region`). `where`: bits 0..23 the voxel's index in `vx_read_region`'s dense array of the same box, bits 24..29
+/// its open faces (bit f, numbered like `face_id`, set when the neighbour on that side holds no block; 0 without `VX_LIST_FACES`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct vx_block_at {
+    pub r#where: u32,
+    pub value: u32,
+}
+/// `vx_list_region` flags (the header's VX_LIST_FACES, VX_LIST_EXPOSED): fill the face bits; keep only blocks with an open face
+pub const VX_LIST_FACES: u32 = 0x1;
+pub const VX_LIST_EXPOSED: u32 = 0x2;
+/// the header's VX_AT_INDEX and VX_AT_FACES
+pub const fn vx_at_index(at: u32) -> u32 { at & 0xFF_FFFF }
+pub const fn vx_at_faces(at: u32) -> u32 { (at >> 24) & 0x3F }
+
 /// The first voxel holding a block along an axis (`vx_scan_points`, `vx_scan_columns`): its coordinate along the scan axis (`VX_SCAN_NONE`:
 /// no block), its block id and log2 of the answering leaf's side (`VX_CELL_OUTSIDE`: a position with a NaN or infinite component).
 #[repr(C)]
@@ -183,6 +198,7 @@ const _: () = assert!(std::mem::size_of::<vx_aabb_result>() == 24);
 const _: () = assert!(std::mem::size_of::<vx_ray_batch>() == 48);
 const _: () = assert!(std::mem::size_of::<vx_ray_hit>() == 32);
 const _: () = assert!(std::mem::size_of::<vx_block_cell>() == 8);
+const _: () = assert!(std::mem::size_of::<vx_block_at>() == 8);
 const _: () = assert!(std::mem::size_of::<vx_scan_hit>() == 16);
 const _: () = assert!(std::mem::size_of::<MaterialInstance>() == 32); // svo_registry.rs:29-40 is #[repr(C)]
 const _: () = assert!(std::mem::size_of::<PickerTask>() == 48 && std::mem::size_of::<PickerResult>() == 48); // svo_picker.rs:13-32
@@ -223,6 +239,11 @@ extern "C" {
     pub fn vx_block_points(ctx: *mut vx_context, pos: *const c_void, pos_stride: u32, count: u32, memory: c_int, out: *mut vx_block_cell) -> c_int;
     /// the block ids of the box [lo, lo + size) as a dense array, x fastest, 0 outside the world; at most 2^24 voxels; `memory`: VX_MEM_HOST / VX_MEM_DEVICE
     pub fn vx_read_region(ctx: *mut vx_context, lo: *const [i32; 3], size: *const [u32; 3], memory: c_int, out: *mut u32) -> c_int;
+    /// the blocks the box [lo, lo + size) holds as a compact list in a fixed order (brick by brick, dense-index order inside a brick), with the
+    /// faces that touch air under `flags` (VX_LIST_*); `*total`: the records the box has, of which the first min(total, capacity) are written
+    /// to `out` (capacity 0: only counted); `memory` (of `out` and `total`): VX_MEM_HOST / VX_MEM_DEVICE
+    pub fn vx_list_region(ctx: *mut vx_context, lo: *const [i32; 3], size: *const [u32; 3], flags: u32, memory: c_int, out: *mut vx_block_at,
+                          capacity: u32, total: *mut u32) -> c_int;
     /// the first block from floor(pos) on along `direction` (VX_DIR_*), at most `reach` voxels on (the start counts; VX_SCAN_TO_EDGE: to the
     /// world's edge), for `count` positions read as vx_block_points reads them; `memory`: VX_MEM_HOST / VX_MEM_DEVICE
     pub fn vx_scan_points(ctx: *mut vx_context, pos: *const c_void, pos_stride: u32, count: u32, direction: c_int, reach: u32, memory: c_int,

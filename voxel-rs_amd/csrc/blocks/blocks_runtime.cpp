@@ -1,9 +1,12 @@
-// libvoxelhip.so, block ids read from the device: vx_block_points and vx_read_region, and the first block along an axis: vx_scan_points and
-// vx_scan_columns (include/voxel_hip.h) -- argument checks (vx_blocks.hpp's and vx_scan.hpp's rules), the pinned scratch the host-memory calls
-// read and write through (csrc/vx_pinned_pool.hpp), and the launches of kernels_blocks.hip and kernels_scan.hip.
+// libvoxelhip.so, block ids read from the device: vx_block_points and vx_read_region, the first block along an axis: vx_scan_points and
+// vx_scan_columns, and the blocks of a box as a list: vx_list_region (include/voxel_hip.h) -- argument checks (vx_blocks.hpp's, vx_scan.hpp's and
+// vx_list.hpp's rules), the pinned scratch the host-memory calls read and write through (csrc/vx_pinned_pool.hpp), and the launches of
+// kernels_blocks.hip, kernels_scan.hip and kernels_list.hip.
 // A further translation unit on the context, like raycast_runtime.cpp: what it needs of the context is vx_context.hpp's (runtime.cpp).
 #include <cstring>
+#include <map>
 #include <mutex>
+#include <utility>
 
 #include "kernels_blocks.h"
 #include "vx_context.hpp"
@@ -15,6 +18,41 @@ namespace {
 
 inline size_t round16(size_t v) { return (v + 15) & ~size_t(15); }
 inline int kernel_variant(const vx_context* ctx) { return ctx->big ? VX_SVO_ESVO_BIG : ctx->svo_type; }  // as vx_raycast picks it
+
+// vx_list_region's workspace: a dword a brick of the box and one more, the records counted and then the offset of each brick's first record.
+// It belongs to a context's stream -- every launch that uses it is queued there, so two calls never hold it at once -- but not to vx_context,
+// which cannot grow (vx_pinned_pool.hpp): the table lives here, keyed by device and stream, under a mutex, and is kept for the life of the
+// process like the pinned pool. vx_destroy drains and destroys the stream and leaves the entry: nothing can still be running on it, and a
+// later context whose stream receives the same handle takes the buffer over. At most 4 bytes a brick of the largest box a stream has
+// listed (fewer than 2^22 bricks in 2^24 voxels: 16 MiB, for the worst box of 1 x 1 x 2^24; 128 KiB for 256^3).
+struct ListScratch {
+    uint32_t* counts = nullptr;
+    size_t entries = 0;
+};
+
+// At least `entries` dwords for the stream of `ctx`, under the context's lock. The buffer only grows; before the old one is freed the
+// stream is waited for, so that no queued launch of an earlier call loses it (hipFree would wait as well: the wait is spelled out). A
+// caller pays that wait only when a box has more bricks than any the stream has listed before.
+int reserve_list_counts(vx_context* ctx, size_t entries, uint32_t** counts) {
+    static std::mutex table_mutex;
+    static std::map<std::pair<int, hipStream_t>, ListScratch> table;
+    std::lock_guard<std::mutex> lock(table_mutex);
+    ListScratch& s = table[{ctx->device, ctx->stream}];
+    if (s.entries < entries) {
+        if (s.counts) {
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            (void)hipFree(s.counts);
+            s.counts = nullptr;
+            s.entries = 0;
+        }
+        size_t cap = 4096;
+        while (cap < entries) cap *= 2;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s.counts), cap * sizeof(uint32_t)));
+        s.entries = cap;
+    }
+    *counts = s.counts;
+    return VX_OK;
+}
 
 }  // namespace
 
@@ -71,6 +109,56 @@ int vx_read_region(vx_context* ctx, const int32_t lo[3], const uint32_t size[3],
     HIP_TRY(vxk::launch_read_region(kernel_variant(ctx), ctx->stream, vxrt::scene_on_bytes(ctx), r, reinterpret_cast<uint32_t*>(pool.dev)));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     std::memcpy(out, pool.host, voxels * 4);
+    return VX_OK;
+}
+
+int vx_list_region(vx_context* ctx, const int32_t lo[3], const uint32_t size[3], uint32_t flags, int memory, vx_block_at* out, uint32_t capacity,
+                   uint32_t* total) {
+    static_assert(sizeof(vx_block_at) == 8, "the ABI's record size");
+    if (memory != VX_MEM_HOST && memory != VX_MEM_DEVICE) return fail(VX_ERR_INVALID_ARGUMENT, "list_region: memory is neither VX_MEM_HOST nor VX_MEM_DEVICE");
+    if (const char* what = vxb::check_list(lo, size, flags, out, capacity, total)) return fail(VX_ERR_INVALID_ARGUMENT, std::string("list_region: ") + what);
+    if (memory == VX_MEM_DEVICE && reinterpret_cast<uintptr_t>(out) % 8) return fail(VX_ERR_INVALID_ARGUMENT, "list_region: out in device memory must be aligned to 8 bytes");
+    if (memory == VX_MEM_DEVICE && reinterpret_cast<uintptr_t>(total) % 4) return fail(VX_ERR_INVALID_ARGUMENT, "list_region: total in device memory must be aligned to 4 bytes");
+    if (!ctx) return fail(VX_ERR_INVALID_ARGUMENT, "null context");
+    if (int rc = vxrt::check_ready(ctx)) return rc;
+    VX_LOCK(ctx);
+    const size_t voxels = size_t(size[0]) * size[1] * size[2];  // (at most 2^24, or 0)
+    if (voxels == 0) {  // no record: only the count is written
+        if (total && memory == VX_MEM_DEVICE) HIP_TRY(hipMemsetAsync(total, 0, sizeof(uint32_t), ctx->stream));
+        else if (total) *total = 0;
+        return VX_OK;
+    }
+    const vxb::Region r = vxb::plan_region(lo, size);
+    const uint32_t bricks = uint32_t(vxb::region_bricks(r));  // (fewer than 2^24)
+    uint32_t* counts = nullptr;
+    if (int rc = reserve_list_counts(ctx, size_t(bricks) + 1, &counts)) return rc;
+    const int variant = kernel_variant(ctx);
+    const vxd::SceneArgs scene = vxrt::scene_on_bytes(ctx);
+
+    if (memory == VX_MEM_DEVICE) {
+        HIP_TRY(vxk::launch_list_count(variant, ctx->stream, scene, r, flags, counts));
+        HIP_TRY(vxk::launch_list_offsets(ctx->stream, counts, bricks, total));
+        if (capacity) HIP_TRY(vxk::launch_list_write(variant, ctx->stream, scene, r, flags, counts, out, capacity));
+        return vxrt::mark_world_read(ctx);
+    }
+
+    // the total (16 bytes) | the records. Two waits: the total decides how many records the pool has to hold and the host copies back
+    vxrt::PinnedPool& pool = vxrt::pinned_pool_of(ctx->device);
+    std::lock_guard<std::mutex> pool_lock(pool.mutex);
+    if (int rc = vxrt::pinned_pool_reserve(pool, 16)) return rc;
+    HIP_TRY(vxk::launch_list_count(variant, ctx->stream, scene, r, flags, counts));
+    HIP_TRY(vxk::launch_list_offsets(ctx->stream, counts, bricks, reinterpret_cast<uint32_t*>(pool.dev)));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    uint32_t found = 0;
+    std::memcpy(&found, pool.host, sizeof found);
+    const uint32_t written = found < capacity ? found : capacity;
+    if (written) {
+        if (int rc = vxrt::pinned_pool_reserve(pool, 16 + size_t(written) * sizeof(vx_block_at))) return rc;
+        HIP_TRY(vxk::launch_list_write(variant, ctx->stream, scene, r, flags, counts, reinterpret_cast<vx_block_at*>(pool.dev + 16), written));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        std::memcpy(out, pool.host + 16, size_t(written) * sizeof(vx_block_at));
+    }
+    *total = found;
     return VX_OK;
 }
 

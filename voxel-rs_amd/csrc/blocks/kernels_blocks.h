@@ -1,10 +1,12 @@
-// What blocks_runtime.cpp knows of the block lookup kernels (kernels_blocks.hip) and of the scans along an axis (kernels_scan.hip).
+// What blocks_runtime.cpp knows of the block lookup kernels (kernels_blocks.hip), of the scans along an axis (kernels_scan.hip) and of the
+// list of a box's blocks (kernels_list.hip).
 #pragma once
 
 #include <hip/hip_runtime_api.h>
 
 #include "vx_args.hpp"
 #include "vx_blocks.hpp"
+#include "vx_list.hpp"
 #include "vx_scan.hpp"
 
 namespace vxk {
@@ -25,5 +27,17 @@ hipError_t launch_scan_points(int svo, hipStream_t stream, const vxd::SceneArgs&
 // one workgroup of one wave a tile of `p` (vxb::plan_columns of a box that holds a voxel, at most 2^24 columns); out: the footprint's
 // records, u fastest, in device-visible memory, 16-byte aligned
 hipError_t launch_scan_columns(int svo, hipStream_t stream, const vxd::SceneArgs& sc, const vxb::Columns& p, vx_scan_hit* out);
+
+// vx_list_region's three launches (kernels_list.hip), in this order on one stream. `r`: vxb::plan_region of a box of at least one and at most
+// 2^24 voxels; counts: vxb::region_bricks(r) + 1 dwords of device memory, 16-byte aligned, which the three launches own from the first
+// one's start to the last one's end.
+//   count: one workgroup of one wave a brick; counts[brick] = the records the brick gives under `flags`
+//   offsets: one workgroup; an exclusive prefix sum over counts[0..bricks) in place, counts[bricks] = *total = the sum (total: device-visible)
+//   write: one workgroup of one wave a brick; the brick's records to out[counts[brick]...], those below `capacity`; out: device-visible,
+//   8-byte aligned
+hipError_t launch_list_count(int svo, hipStream_t stream, const vxd::SceneArgs& sc, const vxb::Region& r, uint32_t flags, uint32_t* counts);
+hipError_t launch_list_offsets(hipStream_t stream, uint32_t* counts, uint32_t bricks, uint32_t* total);
+hipError_t launch_list_write(int svo, hipStream_t stream, const vxd::SceneArgs& sc, const vxb::Region& r, uint32_t flags, uint32_t* counts, vx_block_at* out,
+                             uint32_t capacity);
 
 }  // namespace vxk

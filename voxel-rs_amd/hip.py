@@ -37,6 +37,10 @@ VX_RAYS_TRANSLUCENT = 1
 # vx_block_cell (vx_block_points): the leaf, or the empty cell, that holds a point
 BLOCK_CELL_DTYPE = np.dtype([("value", "<u4"), ("cell_log2", "<u4")])
 VX_CELL_OUTSIDE = 0xFFFFFFFF
+# vx_block_at (vx_list_region): one block of a box -- `where`: the voxel's index in read_region's dense array (bits 0..23) and its open faces (bits
+# 24..29, numbered like face_id); split_where takes it apart
+BLOCK_AT_DTYPE = np.dtype([("where", "<u4"), ("value", "<u4")])
+VX_LIST_FACES, VX_LIST_EXPOSED = 1, 2
 # vx_scan_hit (vx_scan_points, vx_scan_columns): the first voxel holding a block along an axis; directions numbered like face_id
 SCAN_HIT_DTYPE = np.dtype([("coord", "<i4"), ("value", "<u4"), ("cell_log2", "<u4"), ("_pad", "<u4")])
 VX_DIR_NEG_X, VX_DIR_POS_X, VX_DIR_NEG_Y, VX_DIR_POS_Y, VX_DIR_NEG_Z, VX_DIR_POS_Z = range(6)
@@ -45,6 +49,7 @@ VX_SCAN_TO_EDGE = 0xFFFFFFFF
 FACE_NORMALS = np.array([[-1, 0, 0], [1, 0, 0], [0, -1, 0], [0, 1, 0], [0, 0, -1], [0, 0, 1]], dtype=np.float32)  # by face_id
 assert HIT_DTYPE.itemsize == 48 and PICKER_TASK_DTYPE.itemsize == 48 and PICKER_RESULT_DTYPE.itemsize == 48 and FRAME_DTYPE.itemsize == 36
 assert ENTITY_DTYPE.itemsize == 64 and AABB_RESULT_DTYPE.itemsize == 24 and RAY_HIT_DTYPE.itemsize == 32 and SCAN_HIT_DTYPE.itemsize == 16
+assert BLOCK_AT_DTYPE.itemsize == 8
 
 COUNTER_FIELDS = ["rays", "iterations", "pushes", "leaf_tests", "leaf_tests_trilinear", "boundaries", "csvo_header_bytes", "csvo_pointer_bytes",
                   "pixels", "lit_pixels", "shadow_rays", "wave_steps", "services", "refills", "tail_wave_steps", "tail_iterations"]
@@ -107,6 +112,7 @@ SYMBOLS = {
     "vx_trace_views": (_int, [_vp, C.POINTER(Uniforms), _u32, _u32, _u32, _int, _vp, _int, _vp]),
     "vx_block_points": (_int, [_vp, _vp, _u32, _u32, _int, _vp]),
     "vx_read_region": (_int, [_vp, C.POINTER(C.c_int32 * 3), C.POINTER(_u32 * 3), _int, _vp]),
+    "vx_list_region": (_int, [_vp, C.POINTER(C.c_int32 * 3), C.POINTER(_u32 * 3), _u32, _int, _vp, _u32, _vp]),
     "vx_scan_points": (_int, [_vp, _vp, _u32, _u32, _int, _u32, _int, _vp]),
     "vx_scan_columns": (_int, [_vp, C.POINTER(C.c_int32 * 3), C.POINTER(_u32 * 3), _int, _int, _vp]),
     "vx_physics_step": (_int, [_vp, _vp, _u32, _int, C.c_float, _u32, _vp]),
@@ -296,6 +302,17 @@ def ray_hit_positions(hits):
 def block_cells_to_numpy(cells):
     """A device record tensor of Svo.block_points as BLOCK_CELL_DTYPE records (copies to the host: synchronise first)."""
     return cells.cpu().numpy().view(np.uint8).reshape(-1).view(BLOCK_CELL_DTYPE)
+
+
+def block_ats_to_numpy(records):
+    """A device record tensor of Svo.list_region as BLOCK_AT_DTYPE records (copies to the host: synchronise first)."""
+    return records.cpu().numpy().view(np.uint8).reshape(-1).view(BLOCK_AT_DTYPE)
+
+
+def split_where(where):
+    """(index, faces) of vx_block_at.where values (VX_AT_INDEX, VX_AT_FACES): the voxel's index in read_region's dense array of the same box,
+    and its open faces, bit f numbered like face_id. NumPy arrays, torch tensors and plain ints alike."""
+    return where & 0xFFFFFF, (where >> 24) & 0x3F
 
 
 def scan_hits_to_numpy(hits):
@@ -671,6 +688,48 @@ class Svo:
             raise TypeError("read_region: out must be a contiguous CUDA tensor of size.x * size.y * size.z x 4 bytes")
         _check(lib().vx_read_region(self._h, C.byref(lo3), C.byref(size3), VX_MEM_DEVICE, _vp(out.data_ptr())))
         return out
+
+    def list_region(self, lo, size, flags=0, capacity=None, out=None, device=False):
+        """vx_list_region: the blocks the box [lo, lo + size) holds as a compact list of BLOCK_AT_DTYPE records (where: read_region's index and
+        the open faces, split_where; value), ascending by (z >> 3, y >> 3, x >> 3, z, y, x). flags: VX_LIST_FACES fills the face bits,
+        VX_LIST_EXPOSED keeps only blocks with an open face. capacity: the most records to write (default: what `out` holds, or the box's
+        voxels); 0 only counts. Returns (records, total): total is the number of records the box has, whatever the capacity.
+        Host (default): synchronous; the records are the first min(total, capacity) of `out`, or a fresh array of that many; total an int.
+        Device (device=True, or `out` a torch CUDA tensor): returns after enqueueing, without synchronising -- pair with sync(); the records
+        are `out` or a fresh int32 tensor of shape (capacity, 2), of which the first min(total, capacity) rows are written
+        (block_ats_to_numpy); total is an int32 tensor of one element on the device."""
+        lo3, size3 = (C.c_int32 * 3)(*(int(v) for v in lo)), (_u32 * 3)(*(int(v) for v in size))
+        voxels = int(size[0]) * int(size[1]) * int(size[2])
+        if not device and (out is None or isinstance(out, np.ndarray)):
+            if out is not None and (out.dtype != BLOCK_AT_DTYPE or not out.flags.c_contiguous or not out.flags.writeable):
+                raise TypeError("list_region: out must be a writeable C-contiguous array of hip.BLOCK_AT_DTYPE records")
+            total = _u32(0)
+            if out is None:
+                if capacity is None:  # count first: the array is as long as the list
+                    _check(lib().vx_list_region(self._h, C.byref(lo3), C.byref(size3), int(flags), VX_MEM_HOST, None, 0, C.byref(total)))
+                    capacity = total.value
+                capacity = min(int(capacity), voxels)  # (a box has no more records than voxels)
+                out = np.zeros(capacity, dtype=BLOCK_AT_DTYPE)
+            capacity = out.size if capacity is None else int(capacity)
+            if capacity > out.size:
+                raise TypeError("list_region: out holds fewer than `capacity` records")
+            _check(lib().vx_list_region(self._h, C.byref(lo3), C.byref(size3), int(flags), VX_MEM_HOST, out.ctypes.data_as(_vp) if capacity else None,
+                                        capacity, C.byref(total)))
+            return out.reshape(-1)[:min(total.value, capacity)], total.value
+        import torch
+
+        if out is None:
+            out = torch.empty((voxels if capacity is None else int(capacity), 2), dtype=torch.int32, device="cuda")
+        elif not getattr(out, "is_cuda", False) or not out.is_contiguous() or (out.numel() * out.element_size()) % BLOCK_AT_DTYPE.itemsize:
+            raise TypeError("list_region: out must be a contiguous CUDA tensor of whole 8-byte records")
+        held = out.numel() * out.element_size() // BLOCK_AT_DTYPE.itemsize
+        capacity = held if capacity is None else int(capacity)
+        if capacity > held:
+            raise TypeError("list_region: out holds fewer than `capacity` records")
+        total = torch.zeros(1, dtype=torch.int32, device=out.device)
+        _check(lib().vx_list_region(self._h, C.byref(lo3), C.byref(size3), int(flags), VX_MEM_DEVICE, _vp(out.data_ptr()) if capacity else None, capacity,
+                                    _vp(total.data_ptr())))
+        return out, total
 
     # -- the first block along an axis (get_block, gameplay.rs:161-201, looped along it) ----------------------------------------------------------
     def scan_points(self, positions, direction, reach=VX_SCAN_TO_EDGE, out=None):

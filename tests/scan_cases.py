@@ -358,6 +358,33 @@ def host_scan_columns(exe, c, lo, size, direction):
         return np.fromfile(d / "out.bin", dtype=hip.SCAN_HIT_DTYPE).reshape(size[v], size[u]), np.fromfile(d / "trips.bin", dtype=np.uint32)
 
 
+class HostScans:
+    """The harness on one world for many calls (a streamed frame of several MB): the frame is written once, every call is a run of the program.
+    The records of host_scan_points and host_scan_columns, without the trips."""
+
+    def __init__(self, exe, c):
+        self.exe, self.c = exe, c
+        self.dir = tempfile.TemporaryDirectory()
+        self.world = Path(self.dir.name) / "world.bin"
+        c.frame.tofile(self.world)
+
+    def points(self, pts, direction, reach):
+        d = Path(self.dir.name)
+        pts = np.ascontiguousarray(pts, dtype=np.float32)
+        pts.view(np.uint8).tofile(d / "points.bin")
+        _run(self.exe, [self.c.svo_type, self.world, "points", d / "points.bin", 12, len(pts), direction, reach, d / "out.bin", d / "trips.bin"])
+        return np.fromfile(d / "out.bin", dtype=hip.SCAN_HIT_DTYPE)
+
+    def columns(self, lo, size, direction):
+        _, u, v, _ = axes_of(direction)
+        d = Path(self.dir.name)
+        _run(self.exe, [self.c.svo_type, self.world, "columns", *lo, *size, direction, d / "out.bin", d / "trips.bin"])
+        return np.fromfile(d / "out.bin", dtype=hip.SCAN_HIT_DTYPE).reshape(size[v], size[u])
+
+    def close(self):
+        self.dir.cleanup()
+
+
 def differing(got, exp):
     """A message naming the first differing record of two SCAN_HIT_DTYPE arrays, or None. (Equal bytes: the padding too.)"""
     if got.shape != exp.shape:

@@ -4,13 +4,17 @@ ranges are reused and the window re-bases twice in x / z and once in y alone.
 
 The ground truth is restated here from the scene's heights and four rules -- the shell of generate_heightfield_chunk (stream.hpp), the residency
 rule of ChunkLoader::update and calculate_lod (chunkloader.hpp), and pick_leaf_for_lod (octree.hpp) applied recursively --, and the seeded input
-sets (points, regions, rays, entities, views) are made per settled state in WORLD coordinates and shifted by svo_offset, so that they follow the
-window as it re-bases. What the sets hold is counted from the truth and the oracle alone. Nothing of the code under test is used."""
+sets (points, regions, rays, entities, views; the boxes of the lists and of the scans) are made per settled state in WORLD coordinates and
+shifted by svo_offset, so that they follow the window as it re-bases. What the sets hold is counted from the truth and the oracle alone. Nothing
+of the code under test is used. For vx_scan_points, vx_scan_columns and vx_list_region a settled state is handed to scan_cases.py and
+list_cases.py as one of their cases (Case), so that their numpy truths and their host harnesses serve here unchanged."""
 import functools
 import math
 
 import numpy as np
 
+import list_cases as lc
+import scan_cases as scn
 import trace_cases as tc
 from batch_cases import first_difference, oracle_hits, oracle_run, unit  # noqa: F401
 from blocks_cases import LOD_ORDER, lod_voxels, pick_octants  # noqa: F401
@@ -34,7 +38,16 @@ STEPS = 8
 # the settled states' chunk counts: total and per LOD 5 / 4 / 3 / 2 (the same for both formats)
 CHUNKS = {(0, 0): (645, 69, 161, 298, 117), (3, 2): (830, 137, 202, 368, 123)}
 MIN_PITCH = 0.05  # the least |d.y| of a ray (build_rays)
-SET_SEED = 7100  # + the state's index
+SET_SEED = 7100  # + the state's index (anything random for a set added later: a generator of its own, SET_SEED + 100 + the index)
+SIZE = 1 << SVO_DEPTH
+LIST_BOXES = ("under_eye", "lod5_lod4", "lod4_lod3", "lod2", "rim", "domain_edge")  # the boxes vx_list_region is asked for
+SEAM_BOXES = ("lod5_lod4", "lod4_lod3")
+SCAN_FOOTPRINTS = LIST_BOXES + ("half_outside",)  # (half_outside holds no block: the domain starts near 600)
+EXPOSED_FACES = lc.EXPOSED | lc.FACES
+CUT_BOX, CUT = "lod4_lod3", 1000  # the list that a capacity of 1,000 records cuts
+REACHES = (1, 7, scn.TO_EDGE)
+SETTLED_SCANS = tuple((d, r) for d in scn.DIRECTIONS for r in REACHES)  # (direction, reach) of vx_scan_points at a settled state
+MID_SCANS = ((hip.VX_DIR_NEG_Y, scn.TO_EDGE), (hip.VX_DIR_POS_X, scn.TO_EDGE))  # and at a checkpoint in mid-stream
 
 
 def centre_of(eye):
@@ -254,18 +267,27 @@ def point_counts(t, lod, off, pts):
     return c
 
 
+def _odd(v):
+    return int(v) | 1
+
+
+def _across(cz, boundary_chunk):
+    """A 45 x 40 x 45 box over the boundary at x = 32 * boundary_chunk, in the eye's row of chunks, in WORLD coordinates (its height from the
+    boundary's column, clamped into the domain)."""
+    h = heights()
+    bx, z0 = 32 * boundary_chunk, 32 * cz + 3
+    return (_odd(bx - 22), _odd(int(h[min(max(bx, 0), N - 1), z0 + 20]) - 20), _odd(z0)), (45, 40, 45)
+
+
 def build_regions(t, lod, off, eye, centre):
     """name -> (lo, size) in SVO coordinates."""
     h = heights()
     cx, _, cz = centre
     ex, ez = int(math.floor(eye[0])), int(math.floor(eye[2]))
+    odd = _odd
 
-    def odd(v):
-        return int(v) | 1
-
-    def across(boundary_chunk):  # a 45 x 40 x 45 box over the boundary at x = 32 * boundary_chunk, in the eye's row of chunks
-        bx, z0 = 32 * boundary_chunk, 32 * cz + 3
-        return (odd(bx - 22), odd(int(h[bx, z0 + 20]) - 20), odd(z0)), (45, 40, 45)
+    def across(boundary_chunk):
+        return _across(cz, boundary_chunk)
 
     x2, z2 = 32 * (cx + 20) + 5, 32 * cz + 3
     regions = {
@@ -496,6 +518,101 @@ def view_counts(lod, off, hits):
     return out
 
 
+# ---- the boxes of the lists and the scans, and a state as a case of scan_cases.py / list_cases.py ------------------------------------------------
+
+
+def build_list_boxes(regions, off, centre):
+    """name -> (lo, size) in SVO coordinates: the four regions that hold blocks; `rim`, the box over the boundary at chunk cx + 23, where the
+    resident chunks end (LOD-2 voxels face no chunk); `domain_edge`, the box over x = 0 of the scene (inside the octree: the scene's own edge)."""
+    cx, _, cz = centre
+    boxes = {name: regions[name] for name in LIST_BOXES[:4]}
+    for name, chunk in (("rim", cx + 23), ("domain_edge", 0)):
+        lo, size = _across(cz, chunk)
+        boxes[name] = (tuple(int(v) for v in np.asarray(lo) + off), size)
+    return boxes
+
+
+def build_scan_boxes(list_boxes, regions):
+    """(name, direction) -> (lo, size): the footprint of every list box and of `half_outside`, stretched along the direction's axis over the
+    whole octree and 5 voxels beyond it on either side."""
+    out = {}
+    for name in SCAN_FOOTPRINTS:
+        lo, size = list_boxes[name] if name in list_boxes else regions[name]
+        for d in scn.DIRECTIONS:
+            blo, bsize = list(lo), list(size)
+            blo[d >> 1], bsize[d >> 1] = -5, SIZE + 10
+            out[name, d] = (tuple(blo), tuple(bsize))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def cells(centre_chunk):
+    """Per voxel of truth(centre_chunk): log2 of the side of the cells its chunk shows, 5 - lod; 0 where there is no chunk."""
+    _, lod = truth(centre_chunk)
+    k = np.where(lod != 0, 5 - lod.astype(np.int16), 0).astype(np.uint8)
+    c = k.repeat(32, 0).repeat(32, 1).repeat(32, 2)
+    c.setflags(write=False)
+    return c
+
+
+class Case:
+    """What scan_cases.py and list_cases.py want of a case, for one frame of the streamed world; the truth only at a settled state."""
+
+    def __init__(self, scene, centre=None, off=None):
+        self.fmt, self.svo_type, self.frame, self.size = scene.fmt, scene.svo_type, scene.frame, SIZE
+        if centre is not None:
+            self.truth, self.cell = truth(centre)[0], cells(centre)
+            lo = np.asarray(off, dtype=np.int64)
+            self.info = dict(lo=lo, hi=lo + np.asarray(self.truth.shape), size=float(SIZE))
+
+
+class BlockTruth:
+    """By the dense truth alone: points[direction, reach] and columns[name, direction] (SCAN_HIT_DTYPE), lists[name, flags] (BLOCK_AT_DTYPE)."""
+
+
+_block_truths = {}
+
+
+def block_truth(case, inp):
+    """The numpy truths of scan_cases.py and list_cases.py for a settled state's sets; once per state (the formats share the truth)."""
+    key = (inp.index, inp.pts.tobytes())
+    if key not in _block_truths:
+        b = BlockTruth()
+        b.points = {(d, r): scn.points_truth(case, inp.pts, d, r) for d, r in SETTLED_SCANS}
+        b.columns = {(name, d): scn.columns_truth(case, lo, size, d) for (name, d), (lo, size) in inp.scan_boxes.items()}
+        b.lists = {(name, flags): lc.expected_list(case, lo, size, flags) for name, (lo, size) in inp.list_boxes.items() for flags in lc.FLAG_SETS}
+        for a in list(b.points.values()) + list(b.columns.values()) + list(b.lists.values()):
+            a.setflags(write=False)
+        _block_truths[key] = b
+    return _block_truths[key]
+
+
+def list_counts(case, lod, off, boxes):
+    """Per list box, from the truth: its records, how many of them have an open face, how many have none (the inner voxels of LOD cells and
+    of the ground), how many show their -x / +x face, and the LODs of the chunks that hold them."""
+    c = {}
+    for name, (lo, size) in boxes.items():
+        x, y, z, _, faces, _ = lc.expected_parts(case, lo, size, lc.FACES)
+        exposed = int((faces != 0).sum())
+        c[name] = dict(records=len(faces), exposed=exposed, hidden=len(faces) - exposed, open_neg_x=int((faces & 1 != 0).sum()),
+                       open_pos_x=int((faces & 2 != 0).sum()), lods=sorted(int(v) for v in np.unique(lod_at(lod, off, np.stack([x, y, z], axis=1)))))
+    return c
+
+
+def scan_counts(columns):
+    """From the truth's columns: the cell sizes (log2) that answer the top-down heightmap of each seam box, and under_eye over all six
+    directions together and in the direction that sees most; the directions in which half_outside has a column that hits, and none."""
+    def sizes(keys):
+        return sorted({int(v) for k in keys for v in np.unique(columns[k]["cell_log2"][columns[k]["coord"] != scn.NONE])})
+
+    c = {f"{name}_down": sizes([(name, hip.VX_DIR_NEG_Y)]) for name in SEAM_BOXES}
+    c["under_eye"] = sizes([("under_eye", d) for d in scn.DIRECTIONS])
+    c["under_eye_most_in_one"] = max(len(sizes([("under_eye", d)])) for d in scn.DIRECTIONS)
+    hit = [d for d in scn.DIRECTIONS if (columns["half_outside", d]["coord"] != scn.NONE).any()]
+    c["half_outside_hit"], c["half_outside_none"] = hit, [d for d in scn.DIRECTIONS if d not in hit]
+    return c
+
+
 # ---- what the oracle says of a set on one frame ------------------------------------------------------------------------------------------------
 
 
@@ -556,6 +673,8 @@ def make_inputs(fmt, index, eye, centre, off, scene):
     inp.rows, inp.roles = build_entities(t, lod, off, eye, centre, scene.oracle, rng)
     inp.views = build_views(t, lod, off, eye, centre)
     inp.free_u = tc.free_uniforms()
+    inp.list_boxes = build_list_boxes(inp.regions, off, centre)
+    inp.scan_boxes = build_scan_boxes(inp.list_boxes, inp.regions)
     for a in (inp.pts, inp.o, inp.d, inp.m, inp.rows):
         a.setflags(write=False)
     return inp
@@ -565,7 +684,8 @@ def kind_counts(inp, exp):
     t, lod = truth(inp.centre)
     return dict(points=point_counts(t, lod, inp.off, inp.pts), regions=region_counts(t, lod, inp.off, inp.regions),
                 rays=ray_counts(t, lod, inp.off, inp.o, inp.d, inp.m, inp.kinds, exp.hits, exp.scene.oracle),
-                entities=entity_counts(t, lod, inp.off, inp.rows, inp.roles, exp.run), views=view_counts(lod, inp.off, exp.view_hits))
+                entities=entity_counts(t, lod, inp.off, inp.rows, inp.roles, exp.run), views=view_counts(lod, inp.off, exp.view_hits),
+                lists=list_counts(exp.case, lod, inp.off, inp.list_boxes), scans=scan_counts(exp.blocks.columns))
 
 
 def assert_kinds(k):
@@ -589,6 +709,17 @@ def assert_kinds(k):
     v = k["views"]
     assert all(v[0][f"lod{level}"] >= 20 for level in LODS) and v[0]["sky"] >= 100 and v[0]["shadow"] >= 20 and v[0]["lit"] >= 100, v[0]
     assert v[1]["lod5"] >= 300 and v[1]["lod4"] >= 300 and v[1]["shadow"] >= 20, v[1]
+    b = k["lists"]
+    assert b["under_eye"]["records"] >= 1500, b["under_eye"]
+    assert b["lod5_lod4"]["records"] >= 3000 and b["lod5_lod4"]["hidden"] >= 300, b["lod5_lod4"]
+    assert b["lod4_lod3"]["records"] >= 8000 and b["lod4_lod3"]["hidden"] >= 3000, b["lod4_lod3"]
+    assert b["lod2"]["records"] >= 20000 and b["lod2"]["hidden"] >= 15000, b["lod2"]
+    assert b["rim"]["lods"] == [2] and b["rim"]["exposed"] >= 1500 and b["rim"]["open_pos_x"] >= 400, b["rim"]
+    assert b["domain_edge"]["records"] >= 1000 and b["domain_edge"]["open_neg_x"] >= 300, b["domain_edge"]
+    s = k["scans"]
+    assert len(s["lod5_lod4_down"]) == 2 and len(s["lod4_lod3_down"]) == 2, s  # the heightmaps over the seams answer with two cell sizes each
+    assert s["under_eye"] == [0, 1, 2, 3], s  # side elevations from under the eye cross every ring
+    assert s["half_outside_hit"] and s["half_outside_none"], s
 
 
 # ---- the stream ---------------------------------------------------------------------------------------------------------------------
@@ -626,6 +757,8 @@ def dry_run(fmt):
         x.inputs = make_inputs(fmt, index, eye, x.centre, x.off, x.scene)
         x.expected = expected(x.scene, x.inputs)
         x.expected.scene = x.scene
+        x.case = x.expected.case = Case(x.scene, x.centre, x.off)
+        x.blocks = x.expected.blocks = block_truth(x.case, x.inputs)
         x.counts = kind_counts(x.inputs, x.expected)
         states.append(x)
     return states

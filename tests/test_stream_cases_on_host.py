@@ -1,14 +1,16 @@
 """The streamed world of tests/stream_cases.py without a GPU: the path streamed with pump(None, 400), both formats, and at each of its four
 settled states -- that the resident chunks are the restated truth's (645 = 69 / 161 / 298 / 117 and 830 = 137 / 202 / 368 / 123 at LOD 5 / 4 / 3
 / 2), that every input set holds every kind it was specified to hold (by the truth and the oracle alone), that the host harness's points and
-regions on the streamer's frame equal the dense truth, and that the device headers compiled for the host (batch, trace, views, physics) agree
-with the oracle on that frame for the ray, view and entity sets. test_stream_batch.py runs the same sets through the six entry points on the GPU,
-between ranged commits."""
+regions, its scans (tests/cpp/scan_on_host.cpp) and its lists (tests/cpp/list_on_host.cpp) on the streamer's frame equal the dense truth, and
+that the device headers compiled for the host (batch, trace, views, physics) agree with the oracle on that frame for the ray, view and entity
+sets. test_stream_batch.py runs the same sets through the nine entry points on the GPU, between ranged commits."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import list_cases as lc
+import scan_cases as scn
 import stream_cases as sc
 import trace_cases as tc
 from batch_cases import first_difference
@@ -88,6 +90,41 @@ def test_points_and_regions_on_the_host_are_the_dense_truth(states, exe):
             got = host_region(exe, x.scene, lo, size)
             exp = sc.dense_region(t, x.off, lo, size)
             assert (got == exp).all(), (x.index, name, lo, size, np.argwhere(got != exp)[:8])
+
+
+def test_the_scans_on_the_host_are_the_dense_truth(states):
+    """tests/cpp/scan_on_host.cpp on s.frame(): the point set (NaN, +-inf, outside and integer positions among it) in all six directions at
+    reaches 1, 7 and VX_SCAN_TO_EDGE, and every scan box -- each footprint along each axis over the whole octree and beyond, so that side
+    elevations cross every LOD ring --, record for record against scan_cases' numpy truth over the dense arrays."""
+    for x in states:
+        what = f"state {x.index} {x.scene.fmt}"
+        scans = scn.HostScans(scn.harness(), x.case)
+        try:
+            for (d, reach), exp in x.blocks.points.items():
+                got = scans.points(x.inputs.pts, d, reach)
+                assert scn.differing(got, exp) is None, f"{what} points {scn.DIR_NAMES[d]} reach {reach}: {scn.differing(got, exp)}"
+            for (name, d), (lo, size) in x.inputs.scan_boxes.items():
+                got = scans.columns(lo, size, d)
+                assert scn.differing(got, x.blocks.columns[name, d]) is None, f"{what} columns {name} {scn.DIR_NAMES[d]} {lo} {size}: {scn.differing(got, x.blocks.columns[name, d])}"
+        finally:
+            scans.close()
+
+
+def test_the_lists_on_the_host_are_the_dense_truth(states):
+    """tests/cpp/list_on_host.cpp on s.frame(): every list box under every flag set against list_cases' numpy truth, and the list of the
+    LOD 4 / LOD 3 box cut by a capacity of 1,000 records: the total stays, the records are the first 1,000."""
+    for x in states:
+        what = f"state {x.index} {x.scene.fmt}"
+        lists = lc.HostLists(lc.harness(), x.case)
+        try:
+            for (name, flags), exp in x.blocks.lists.items():
+                got, total = lists.list(*x.inputs.list_boxes[name], flags)
+                assert total == len(exp) and lc.differing(got, exp) is None, f"{what} {name} flags {flags}: total {total} of {len(exp)}; {lc.differing(got, exp)}"
+            exp = x.blocks.lists[sc.CUT_BOX, sc.EXPOSED_FACES]
+            got, total, _ = lists.buffer(*x.inputs.list_boxes[sc.CUT_BOX], sc.EXPOSED_FACES, sc.CUT)
+            assert len(exp) > sc.CUT and total == len(exp) and lc.differing(got, exp[:sc.CUT]) is None, f"{what} cut: {lc.differing(got, exp[:sc.CUT])}"
+        finally:
+            lists.close()
 
 
 def test_the_ray_set_on_the_host_is_the_oracles(states, devhost, tracehost):  # noqa: F811

@@ -175,6 +175,30 @@ typedef struct vx_scan_hit {
     uint32_t _pad;                /* written 0 */
 } vx_scan_hit;
 
+/* A batch of axis-aligned boxes read where they lie (vx_overlap_boxes). Box i spans, per axis, [mn, mx) with
+ *   mn = origin[i] + offset[i]   (one fp32 add; offset == NULL: mn = origin[i])
+ *   mx = mn + extents[i]         (one fp32 add)
+ * -- the order of gameplay.rs:212-217 and of the physics fan (physics.rs / svo_picker.rs:183-243), so a vx_entity record is read in
+ * place: origin = &e[0].position, offset = &e[0].aabb_offset, extents = &e[0].aabb_extents, all three strides 64.
+ * Every pointer 4-byte aligned, in the memory kind given to the call; strides in bytes, multiples of 4; origin_stride >= 12; offset_stride
+ * and extents_stride >= 12, or 0 = that one vector for every box. */
+typedef struct vx_box_batch {
+    const void* origin;
+    const void* offset;    /* may be NULL */
+    const void* extents;
+    uint32_t origin_stride, offset_stride, extents_stride;
+    uint32_t only_value;   /* 0: every block counts; else only voxels whose BlockId equals it (water, lava, a ladder) */
+} vx_box_batch;
+
+#define VX_BOX_INVALID 0xFFFFFFFFu
+/* What a box holds (vx_overlap_boxes); 32 bytes. */
+typedef struct vx_box_hit {
+    uint32_t blocks;   /* voxels of the box's cover that hold a (counted) block; VX_BOX_INVALID: the record described no box */
+    uint32_t value;    /* BlockId of the first of them in vx_read_region's order (z, then y, then x ascending); 0 = none */
+    int32_t lo[3];     /* the bounds of those voxels in SVO coordinates, [lo, hi); all 0 when blocks is 0 or VX_BOX_INVALID */
+    int32_t hi[3];
+} vx_box_hit;
+
 /* Optional per-pixel record of what trace_ray saw (world.glsl:27-90) -- the "hit position, depth" outputs
  * used for parity checks; not part of the reference's surface. */
 typedef struct vx_hit {
@@ -472,6 +496,32 @@ int vx_scan_points(vx_context* ctx, const void* pos, uint32_t pos_stride, uint32
  * 0..5; null lo or size; size[u] * size[v] > 16777216 (2^24) columns; size[a] > 16777216; a null out for a box that holds a voxel; a
  * misaligned device out. Any size component 0: VX_OK. Before the first commit: VX_ERR_STATE. */
 int vx_scan_columns(vx_context* ctx, const int32_t lo[3], const uint32_t size[3], int direction, int memory, vx_scan_hit* out);
+/* What is inside each of `count` axis-aligned float boxes (vx_box_batch): does the box overlap a block, how many voxels of it, which block
+ * first, and within which bounds -- the reference's test of the player's AABB against a voxel (handle_voxel_placement, gameplay.rs:211-222)
+ * for a batch, asked of the world the device holds: spawn and placement checks, "is this entity stuck", "how much of it is under water"
+ * (only_value), the bounds to push a penetrating entity out along, trigger volumes.
+ * When a record is a box: every component of origin, offset and extents is finite, every extent is > 0 and <= 64, and mn and mx are finite.
+ * Anything else gives {VX_BOX_INVALID, 0, {0,0,0}, {0,0,0}} in both memory kinds (vx_block_points' way with a position that is no position);
+ * the call does not fail for it. The limit of 64 keeps a wave's walk to at most 9 bricks an axis: larger volumes are vx_list_region with
+ * capacity == 0.
+ * The cover: per axis the voxels v with v + 1 > mn and v < mx (overlap of positive length: a box resting exactly on a block's top does not
+ * overlap it; a caller who wants touching to count grows the box) -- floor(mn) .. ceil(mx) - 1, then cut to the world [0, 2^depth): outside
+ * the world is air. A cover with no voxel on some axis (outside the world; a huge coordinate whose add absorbs the extent) gives blocks = 0.
+ * Coordinates such as 3e9, -3e9 and 1e30 are valid.
+ * What a voxel holds: vx_block_points' value at its centre; a LOD voxel of side 2^k counts once for each fine voxel of it inside the cover, as
+ * in vx_read_region; translucent blocks count. With only_value != 0 a voxel counts when its value equals it; the count, the first block and
+ * the bounds all use that one rule.
+ * One wave a box: the wave walks the bricks of 8 x 8 x 8 voxels the cover touches, the levels above a brick once for the wave, the last three
+ * per lane, and folds its lanes' answers once at the end. One launch.
+ * Memory kinds, ordering and fences are vx_block_points'. VX_MEM_HOST: synchronous; the three vectors of each box travel unchanged through
+ * pinned memory (the kernel does the adds in both memory kinds); one launch, one wait. VX_MEM_DEVICE (out aligned to 16 bytes): enqueued on
+ * the context's stream, returns after enqueueing, ordered behind the commits made so far and earlier batch calls (it may read the vx_entity
+ * records an earlier vx_physics_step wrote); later commits wait for it; the fence is vx_sync. out must not overlap what `boxes` points to;
+ * `boxes` itself is read during the call.
+ * VX_ERR_INVALID_ARGUMENT (its message names the field; nothing is written): a null ctx; an unknown memory kind; with count > 0: null boxes,
+ * out, origin or extents; a stride or an alignment that breaks vx_box_batch's rules; count > 16777216 (2^24); a misaligned device out.
+ * count == 0: VX_OK (nothing is read or written). Before the first commit: VX_ERR_STATE. */
+int vx_overlap_boxes(vx_context* ctx, const vx_box_batch* boxes, uint32_t count, int memory, vx_box_hit* out);
 /* Physics::step_many (src/systems/physics.rs:122-136) `steps` times over `count` entities in ONE kernel launch, against the world as last
  * committed: per step and entity the AABB's fan of axis-parallel picker rays (Aabb::generate_picker_tasks, svo_picker.rs:183-243: max_dst
  * 10), folded into six contact distances (parse_picker_results, svo_picker.rs:245-299), then Physics::update_entity and

@@ -171,6 +171,33 @@ pub const VX_SCAN_NONE: i32 = i32::MIN;
 /// `reach`: as far as the world goes (the header's VX_SCAN_TO_EDGE)
 pub const VX_SCAN_TO_EDGE: u32 = u32::MAX;
 
+/// A batch of axis-aligned boxes read where they lie (`vx_overlap_boxes`): box i spans [mn, mx) with mn = origin[i] + offset[i] (offset null:
+/// mn = origin[i]) and mx = mn + extents[i]. Strides in bytes, multiples of 4; origin_stride >= 12; offset_stride and extents_stride >= 12, or
+/// 0 = that one vector for every box. `vx_entity` records are read in place: &e[0].position, &e[0].aabb_offset, &e[0].aabb_extents, strides 64.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct vx_box_batch {
+    pub origin: *const c_void,
+    pub offset: *const c_void,
+    pub extents: *const c_void,
+    pub origin_stride: u32,
+    pub offset_stride: u32,
+    pub extents_stride: u32,
+    pub only_value: u32,
+}
+/// What a box holds (`vx_overlap_boxes`): the voxels of its cover that hold a (counted) block (`VX_BOX_INVALID`: the record described no
+/// box), the block id of the first of them in `vx_read_region`'s order, and their bounds [lo, hi) in SVO coordinates.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct vx_box_hit {
+    pub blocks: u32,
+    pub value: u32,
+    pub lo: [i32; 3],
+    pub hi: [i32; 3],
+}
+/// `vx_box_hit::blocks` of a record that described no box (the header's VX_BOX_INVALID)
+pub const VX_BOX_INVALID: u32 = u32::MAX;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct vx_stats {
@@ -200,6 +227,8 @@ const _: () = assert!(std::mem::size_of::<vx_ray_hit>() == 32);
 const _: () = assert!(std::mem::size_of::<vx_block_cell>() == 8);
 const _: () = assert!(std::mem::size_of::<vx_block_at>() == 8);
 const _: () = assert!(std::mem::size_of::<vx_scan_hit>() == 16);
+const _: () = assert!(std::mem::size_of::<vx_box_batch>() == 40);
+const _: () = assert!(std::mem::size_of::<vx_box_hit>() == 32);
 const _: () = assert!(std::mem::size_of::<MaterialInstance>() == 32); // svo_registry.rs:29-40 is #[repr(C)]
 const _: () = assert!(std::mem::size_of::<PickerTask>() == 48 && std::mem::size_of::<PickerResult>() == 48); // svo_picker.rs:13-32
 
@@ -251,6 +280,9 @@ extern "C" {
     /// the same scan for every column of the box [lo, lo + size) across the axis of `direction`, from the face it enters, as a dense array
     /// [v - lo[v]][u - lo[u]] (u < v the two other axes; VX_DIR_NEG_Y: a heightmap [z][x]); `memory`: VX_MEM_HOST / VX_MEM_DEVICE
     pub fn vx_scan_columns(ctx: *mut vx_context, lo: *const [i32; 3], size: *const [u32; 3], direction: c_int, memory: c_int, out: *mut vx_scan_hit) -> c_int;
+    /// what each of `count` float boxes (`vx_box_batch`) holds: how many voxels of its cover hold a block (`only_value`: of that id), the first
+    /// of them, their bounds; a record that is no box gives `VX_BOX_INVALID`; `memory`: VX_MEM_HOST / VX_MEM_DEVICE (`out` aligned to 16 bytes)
+    pub fn vx_overlap_boxes(ctx: *mut vx_context, boxes: *const vx_box_batch, count: u32, memory: c_int, out: *mut vx_box_hit) -> c_int;
     /// Physics::step_many (physics.rs:122-136) `steps` times for `count` entities in one launch; `memory`: VX_MEM_HOST / VX_MEM_DEVICE
     pub fn vx_physics_step(ctx: *mut vx_context, entities: *mut vx_entity, count: u32, memory: c_int, delta_time: f32, steps: u32,
                            contacts: *mut vx_aabb_result) -> c_int;

@@ -1,7 +1,8 @@
 // libvoxelhip.so, block ids read from the device: vx_block_points and vx_read_region, the first block along an axis: vx_scan_points and
-// vx_scan_columns, and the blocks of a box as a list: vx_list_region (include/voxel_hip.h) -- argument checks (vx_blocks.hpp's, vx_scan.hpp's and
-// vx_list.hpp's rules), the pinned scratch the host-memory calls read and write through (csrc/vx_pinned_pool.hpp), and the launches of
-// kernels_blocks.hip, kernels_scan.hip and kernels_list.hip.
+// vx_scan_columns, the blocks of a box as a list: vx_list_region, and what a batch of float boxes holds: vx_overlap_boxes (include/voxel_hip.h)
+// -- argument checks (vx_blocks.hpp's, vx_scan.hpp's, vx_list.hpp's and vx_boxes.hpp's rules), the pinned scratch the host-memory calls read
+// and write through (csrc/vx_pinned_pool.hpp), and the launches of kernels_blocks.hip, kernels_scan.hip, kernels_list.hip and
+// kernels_boxes.hip.
 // A further translation unit on the context, like raycast_runtime.cpp: what it needs of the context is vx_context.hpp's (runtime.cpp).
 #include <cstring>
 #include <map>
@@ -216,5 +217,46 @@ int vx_scan_columns(vx_context* ctx, const int32_t lo[3], const uint32_t size[3]
     HIP_TRY(vxk::launch_scan_columns(kernel_variant(ctx), ctx->stream, vxrt::scene_on_bytes(ctx), p, reinterpret_cast<vx_scan_hit*>(pool.dev)));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     std::memcpy(out, pool.host, columns * sizeof(vx_scan_hit));
+    return VX_OK;
+}
+
+int vx_overlap_boxes(vx_context* ctx, const vx_box_batch* boxes, uint32_t count, int memory, vx_box_hit* out) {
+    static_assert(sizeof(vx_box_hit) == 32, "the ABI's record size");
+    if (memory != VX_MEM_HOST && memory != VX_MEM_DEVICE) return fail(VX_ERR_INVALID_ARGUMENT, "overlap_boxes: memory is neither VX_MEM_HOST nor VX_MEM_DEVICE");
+    if (const char* what = vxb::check_boxes(boxes, count, out)) return fail(VX_ERR_INVALID_ARGUMENT, std::string("overlap_boxes: ") + what);
+    if (count && memory == VX_MEM_DEVICE && reinterpret_cast<uintptr_t>(out) % 16) return fail(VX_ERR_INVALID_ARGUMENT, "overlap_boxes: out in device memory must be aligned to 16 bytes");
+    if (!ctx) return fail(VX_ERR_INVALID_ARGUMENT, "null context");
+    if (int rc = vxrt::check_ready(ctx)) return rc;
+    VX_LOCK(ctx);
+    if (count == 0) return VX_OK;
+
+    if (memory == VX_MEM_DEVICE) {
+        HIP_TRY(vxk::launch_overlap_boxes(kernel_variant(ctx), ctx->stream, vxrt::scene_on_bytes(ctx), boxes->origin, boxes->offset, boxes->extents,
+                                          boxes->origin_stride, boxes->offset_stride, boxes->extents_stride, boxes->only_value, count, out));
+        return vxrt::mark_world_read(ctx);
+    }
+
+    // the origins packed at stride 12 | the offsets (none; one; one a box) | the extents (one; one a box) | the records (at a multiple of 16):
+    // each vector's bytes unchanged -- the kernel does the adds, as for device memory
+    const auto packed = [count](const void* p, uint32_t stride) { return !p ? size_t(0) : (stride ? size_t(count) * 12 : size_t(12)); };
+    const size_t at_offset = packed(boxes->origin, boxes->origin_stride), at_extents = at_offset + packed(boxes->offset, boxes->offset_stride);
+    const size_t at_out = round16(at_extents + packed(boxes->extents, boxes->extents_stride)), out_bytes = size_t(count) * sizeof(vx_box_hit);
+    vxrt::PinnedPool& pool = vxrt::pinned_pool_of(ctx->device);
+    std::lock_guard<std::mutex> pool_lock(pool.mutex);
+    if (int rc = vxrt::pinned_pool_reserve(pool, at_out + out_bytes)) return rc;
+    const auto pack = [count, &pool](size_t at, const void* p, uint32_t stride) {
+        const uint8_t* from = static_cast<const uint8_t*>(p);
+        if (!p) return;
+        if (stride == 12 || stride == 0) std::memcpy(pool.host + at, from, stride ? size_t(count) * 12 : size_t(12));
+        else for (size_t i = 0; i < count; ++i) std::memcpy(pool.host + at + 12 * i, from + size_t(stride) * i, 12);  // (exactly a vector's bytes)
+    };
+    pack(0, boxes->origin, boxes->origin_stride);
+    pack(at_offset, boxes->offset, boxes->offset_stride);
+    pack(at_extents, boxes->extents, boxes->extents_stride);
+    HIP_TRY(vxk::launch_overlap_boxes(kernel_variant(ctx), ctx->stream, vxrt::scene_on_bytes(ctx), pool.dev, boxes->offset ? pool.dev + at_offset : nullptr,
+                                      pool.dev + at_extents, 12, boxes->offset_stride ? 12u : 0u, boxes->extents_stride ? 12u : 0u, boxes->only_value, count,
+                                      reinterpret_cast<vx_box_hit*>(pool.dev + at_out)));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // synchronous, like vx_block_points' host-memory call
+    std::memcpy(out, pool.host + at_out, out_bytes);
     return VX_OK;
 }

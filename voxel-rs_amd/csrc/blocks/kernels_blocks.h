@@ -1,11 +1,12 @@
 // What blocks_runtime.cpp knows of the block lookup kernels (kernels_blocks.hip), of the scans along an axis (kernels_scan.hip) and of the
-// list of a box's blocks (kernels_list.hip).
+// list of a box's blocks (kernels_list.hip) and of what a batch of float boxes holds (kernels_boxes.hip).
 #pragma once
 
 #include <hip/hip_runtime_api.h>
 
 #include "vx_args.hpp"
 #include "vx_blocks.hpp"
+#include "vx_boxes.hpp"
 #include "vx_list.hpp"
 #include "vx_scan.hpp"
 
@@ -39,5 +40,12 @@ hipError_t launch_list_count(int svo, hipStream_t stream, const vxd::SceneArgs& 
 hipError_t launch_list_offsets(hipStream_t stream, uint32_t* counts, uint32_t bricks, uint32_t* total);
 hipError_t launch_list_write(int svo, hipStream_t stream, const vxd::SceneArgs& sc, const vxb::Region& r, uint32_t flags, uint32_t* counts, vx_block_at* out,
                              uint32_t capacity);
+
+// `count` (1..2^24) workgroups of one wave, one box a wave: float[3]s at origin + i * origin_stride, offset + i * offset_stride (offset may be
+// null: no add) and extents + i * extents_stride (4-byte aligned; strides multiples of 4, >= 12, offset's and extents' may be 0 = one vector for
+// every box); only_value: 0 = every block counts; out: `count` records of device-visible memory, 16-byte aligned, that overlaps no input
+hipError_t launch_overlap_boxes(int svo, hipStream_t stream, const vxd::SceneArgs& sc, const void* origin, const void* offset, const void* extents,
+                                uint32_t origin_stride, uint32_t offset_stride, uint32_t extents_stride, uint32_t only_value, uint32_t count,
+                                vx_box_hit* out);
 
 }  // namespace vxk

@@ -43,13 +43,17 @@ BLOCK_AT_DTYPE = np.dtype([("where", "<u4"), ("value", "<u4")])
 VX_LIST_FACES, VX_LIST_EXPOSED = 1, 2
 # vx_scan_hit (vx_scan_points, vx_scan_columns): the first voxel holding a block along an axis; directions numbered like face_id
 SCAN_HIT_DTYPE = np.dtype([("coord", "<i4"), ("value", "<u4"), ("cell_log2", "<u4"), ("_pad", "<u4")])
+# vx_box_hit (vx_overlap_boxes): what a float box holds -- the voxels of its cover that hold a (counted) block, the first of them in
+# read_region's order, their bounds [lo, hi); blocks == VX_BOX_INVALID: the record described no box
+BOX_HIT_DTYPE = np.dtype([("blocks", "<u4"), ("value", "<u4"), ("lo", "<i4", 3), ("hi", "<i4", 3)])
+VX_BOX_INVALID = 0xFFFFFFFF
 VX_DIR_NEG_X, VX_DIR_POS_X, VX_DIR_NEG_Y, VX_DIR_POS_Y, VX_DIR_NEG_Z, VX_DIR_POS_Z = range(6)
 VX_SCAN_NONE = -0x80000000
 VX_SCAN_TO_EDGE = 0xFFFFFFFF
 FACE_NORMALS = np.array([[-1, 0, 0], [1, 0, 0], [0, -1, 0], [0, 1, 0], [0, 0, -1], [0, 0, 1]], dtype=np.float32)  # by face_id
 assert HIT_DTYPE.itemsize == 48 and PICKER_TASK_DTYPE.itemsize == 48 and PICKER_RESULT_DTYPE.itemsize == 48 and FRAME_DTYPE.itemsize == 36
 assert ENTITY_DTYPE.itemsize == 64 and AABB_RESULT_DTYPE.itemsize == 24 and RAY_HIT_DTYPE.itemsize == 32 and SCAN_HIT_DTYPE.itemsize == 16
-assert BLOCK_AT_DTYPE.itemsize == 8
+assert BLOCK_AT_DTYPE.itemsize == 8 and BOX_HIT_DTYPE.itemsize == 32
 
 COUNTER_FIELDS = ["rays", "iterations", "pushes", "leaf_tests", "leaf_tests_trilinear", "boundaries", "csvo_header_bytes", "csvo_pointer_bytes",
                   "pixels", "lit_pixels", "shadow_rays", "wave_steps", "services", "refills", "tail_wave_steps", "tail_iterations"]
@@ -73,6 +77,12 @@ class RayBatch(C.Structure):
     """vx_ray_batch"""
     _fields_ = [("origin", C.c_void_p), ("dir", C.c_void_p), ("max_dst", C.c_void_p), ("origin_stride", C.c_uint32), ("dir_stride", C.c_uint32),
                 ("max_dst_stride", C.c_uint32), ("max_dst_all", C.c_float), ("flags", C.c_uint32)]
+
+
+class BoxBatch(C.Structure):
+    """vx_box_batch"""
+    _fields_ = [("origin", C.c_void_p), ("offset", C.c_void_p), ("extents", C.c_void_p), ("origin_stride", C.c_uint32), ("offset_stride", C.c_uint32),
+                ("extents_stride", C.c_uint32), ("only_value", C.c_uint32)]
 
 
 class Result(C.Structure):
@@ -115,6 +125,7 @@ SYMBOLS = {
     "vx_list_region": (_int, [_vp, C.POINTER(C.c_int32 * 3), C.POINTER(_u32 * 3), _u32, _int, _vp, _u32, _vp]),
     "vx_scan_points": (_int, [_vp, _vp, _u32, _u32, _int, _u32, _int, _vp]),
     "vx_scan_columns": (_int, [_vp, C.POINTER(C.c_int32 * 3), C.POINTER(_u32 * 3), _int, _int, _vp]),
+    "vx_overlap_boxes": (_int, [_vp, C.POINTER(BoxBatch), _u32, _int, _vp]),
     "vx_physics_step": (_int, [_vp, _vp, _u32, _int, C.c_float, _u32, _vp]),
     "vx_debug_trace": (_int, [_vp, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.c_float, _int, C.POINTER(Result), _vp, _u32, C.POINTER(_u32)]),
     "vx_sync": (_int, [_vp]),
@@ -272,6 +283,29 @@ def entity_positions(entities):
     if nbytes % ENTITY_DTYPE.itemsize or not entities.is_contiguous():
         raise TypeError("entity_positions: a device tensor must be contiguous and hold whole 64-byte vx_entity records")
     return entities.reshape(-1).view(torch.uint8).view(torch.float32).view(-1, 16)[:, 0:3]
+
+
+def entity_boxes(entities):
+    """The boxes inside vx_entity records as the arguments of Svo.overlap_boxes: (origin, extents, offset) -- position, aabb_extents and
+    aabb_offset as (N, 3) float32 views at a stride of 64 bytes, of a NumPy array of ENTITY_DTYPE or of a contiguous torch tensor whose
+    bytes are vx_entity records. No copy: svo.overlap_boxes(*entity_boxes(e)) reads the records in place."""
+    if isinstance(entities, np.ndarray):
+        if entities.dtype != ENTITY_DTYPE:
+            raise TypeError("entity_boxes: a host array must be of hip.ENTITY_DTYPE")
+        e = entities.reshape(-1)
+        return e["position"], e["aabb_extents"], e["aabb_offset"]
+    import torch
+
+    nbytes = entities.numel() * entities.element_size()
+    if nbytes % ENTITY_DTYPE.itemsize or not entities.is_contiguous():
+        raise TypeError("entity_boxes: a device tensor must be contiguous and hold whole 64-byte vx_entity records")
+    f = entities.reshape(-1).view(torch.uint8).view(torch.float32).view(-1, 16)
+    return f[:, 0:3], f[:, 9:12], f[:, 6:9]
+
+
+def box_hits_to_numpy(hits):
+    """A device record tensor of Svo.overlap_boxes as BOX_HIT_DTYPE records (copies to the host: synchronise first)."""
+    return hits.cpu().numpy().view(np.uint8).reshape(-1).view(BOX_HIT_DTYPE)
 
 
 def ray_hits_to_numpy(hits):
@@ -787,6 +821,46 @@ class Svo:
         elif not getattr(out, "is_cuda", False) or not out.is_contiguous() or out.numel() * out.element_size() != columns * SCAN_HIT_DTYPE.itemsize:
             raise TypeError("scan_columns: out must be a contiguous CUDA tensor of size.u * size.v x 16 bytes")
         _check(lib().vx_scan_columns(self._h, C.byref(lo3), C.byref(size3), int(direction), VX_MEM_DEVICE, _vp(out.data_ptr())))
+        return out
+
+    # -- what float boxes hold (gameplay.rs:211-222: the player's AABB against a voxel, for a batch) -----------------------------------------------
+    def overlap_boxes(self, origin, extents, offset=None, only_value=0, out=None, device=False):
+        """vx_overlap_boxes: what each box [origin + offset, origin + offset + extents) holds (BOX_HIT_DTYPE: blocks -- the voxels of its cover
+        that hold a block, or VX_BOX_INVALID --, value of the first of them, their bounds lo, hi). origin: (N, 3) float32 at any row stride;
+        extents and offset: the same, or one (3,) vector for every box; offset None: no add (entity_boxes(e) gives all three of vx_entity
+        records in place). only_value: 0 = every block counts, else only voxels of that id. At most 64 along each axis.
+        Host (NumPy arrays): synchronous; returns `out` or a fresh array of BOX_HIT_DTYPE.
+        Device (torch CUDA tensors; device=True insists on them): returns after enqueueing, without synchronising -- pair with sync(); the
+        records are `out` or a fresh int32 tensor of shape (N, 8) on the origins' device (box_hits_to_numpy)."""
+        host = isinstance(origin, np.ndarray)
+        if len(origin.shape) != 2 or origin.shape[1] != 3:
+            raise TypeError("overlap_boxes: origin must have shape (N, 3)")
+        count = int(origin.shape[0])
+        given = [origin, extents] + ([offset] if offset is not None else [])
+        if host and (device or not all(isinstance(x, np.ndarray) for x in given)):
+            raise TypeError("overlap_boxes: origin, extents and offset must all be NumPy arrays, or -- device=True -- all torch CUDA tensors")
+        if not host and not all(getattr(x, "is_cuda", False) for x in given):
+            raise TypeError("overlap_boxes: origin, extents and offset must all be NumPy arrays or all torch CUDA tensors")
+        batch = BoxBatch()
+        batch.origin, batch.origin_stride = _ray_vectors("origin", origin, count, 3)
+        batch.extents, batch.extents_stride = _ray_vectors("extents", extents, count, 3)
+        if offset is not None:
+            batch.offset, batch.offset_stride = _ray_vectors("offset", offset, count, 3)
+        batch.only_value = int(only_value)
+        if host:
+            if out is None:
+                out = np.zeros(count, dtype=BOX_HIT_DTYPE)
+            elif not isinstance(out, np.ndarray) or out.dtype != BOX_HIT_DTYPE or out.size != count or not out.flags.c_contiguous or not out.flags.writeable:
+                raise TypeError("overlap_boxes: out must be a writeable C-contiguous array of N hip.BOX_HIT_DTYPE records")
+            _check(lib().vx_overlap_boxes(self._h, C.byref(batch), count, VX_MEM_HOST, out.ctypes.data_as(_vp)))
+            return out
+        import torch
+
+        if out is None:
+            out = torch.empty((count, 8), dtype=torch.int32, device=origin.device)
+        elif not out.is_cuda or not out.is_contiguous() or out.numel() * out.element_size() < count * BOX_HIT_DTYPE.itemsize:
+            raise TypeError("overlap_boxes: out must be a contiguous CUDA tensor of at least N x 32 bytes")
+        _check(lib().vx_overlap_boxes(self._h, C.byref(batch), count, VX_MEM_DEVICE, _vp(out.data_ptr())))
         return out
 
     # -- Physics::step_many (src/systems/physics.rs:122-136), on the device ---------------------------------------

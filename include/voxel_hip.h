@@ -199,6 +199,29 @@ typedef struct vx_box_hit {
     int32_t hi[3];
 } vx_box_hit;
 
+#define VX_FLOOD_MAX_STEPS   250u
+#define VX_FLOOD_NO_POSITION 0xFDu   /* every byte of a field whose position is no position */
+#define VX_FLOOD_UNREACHED   0xFEu   /* passable, not reached within max_steps */
+#define VX_FLOOD_BLOCKED     0xFFu   /* not passable */
+#define VX_FLOOD_SEED_ALWAYS 1u      /* the seed cell is step 0 and spreads even if it holds a block (a lamp is a block) */
+#define VX_FLOOD_INVALID     0xFFFFFFFFu
+/* What every query of a vx_flood_points call shares; read on the host during the call. */
+typedef struct vx_flood_shape {
+    uint32_t size[3];      /* the box of each query, 1..32 an axis */
+    uint32_t seed_at[3];   /* the seed's cell inside the box, < size: lo = floor(p) - seed_at */
+    uint32_t max_steps;    /* 0..VX_FLOOD_MAX_STEPS */
+    uint32_t pass_value;   /* 0: only air passes; else voxels with this BlockId pass too (water) */
+    uint32_t flags;        /* 0 or VX_FLOOD_SEED_ALWAYS */
+} vx_flood_shape;
+/* What a flood reached (vx_flood_points); 16 bytes. */
+typedef struct vx_flood_info {
+    uint32_t reached;      /* cells with a step count (the seed included); VX_FLOOD_INVALID: no position */
+    uint32_t farthest;     /* the largest step count; 0 when reached <= 1 */
+    uint32_t faces;        /* bit f (numbered like face_id) set when a reached cell lies on that face of the box: 0 = the flood is
+                              enclosed within the box */
+    uint32_t seed_value;   /* vx_block_points' value at the seed cell */
+} vx_flood_info;
+
 /* Optional per-pixel record of what trace_ray saw (world.glsl:27-90) -- the "hit position, depth" outputs
  * used for parity checks; not part of the reference's surface. */
 typedef struct vx_hit {
@@ -522,6 +545,36 @@ int vx_scan_columns(vx_context* ctx, const int32_t lo[3], const uint32_t size[3]
  * out, origin or extents; a stride or an alignment that breaks vx_box_batch's rules; count > 16777216 (2^24); a misaligned device out.
  * count == 0: VX_OK (nothing is read or written). Before the first commit: VX_ERR_STATE. */
 int vx_overlap_boxes(vx_context* ctx, const vx_box_batch* boxes, uint32_t count, int memory, vx_box_hit* out);
+/* Step distances through air around each of `count` positions: a breadth-first flood of a small box, asked of the world the device holds --
+ * which cells a mob can reach and in how many steps (a flow field to walk down), how far a lamp's light gets around corners, whether a room
+ * is sealed or the flood leaks out of the box, how big a cave is. The reference would loop get_block (gameplay.rs:161-201) over the
+ * neighbourhood and search on the host. Everything is integer and exact.
+ * Positions are gathered exactly as vx_block_points gathers them (packed arrays, vx_entity.position, vx_ray_hit.pos in place). The seed is
+ * floor(p) per component, saturated to int32 as in vx_scan_points; the box of the query is [lo, lo + size) with lo = seed - seed_at (kept
+ * modulo 2^32 as vx_read_region keeps a box: it may overhang the world, and finite positions such as 3e9 and -3e9 are valid). A NaN or
+ * infinite component is no position: the field is all VX_FLOOD_NO_POSITION and the record {VX_FLOOD_INVALID, 0, 0, 0}; the call does not fail.
+ * A cell is passable when vx_block_points' value at its centre is 0 or equals a non-zero pass_value; outside [0, 2^depth)^3 is air; a LOD
+ * voxel blocks each of its fine voxels. Cells outside the box do not exist: the box bounds the flood.
+ * Steps are 6-connected: a cell's byte is the length of the shortest path from the seed through passable cells of the box, when that is at
+ * most max_steps; other passable cells are VX_FLOOD_UNREACHED, impassable ones VX_FLOOD_BLOCKED. A seed that is not passable reaches nothing
+ * ({0, 0, 0, seed_value}); under VX_FLOOD_SEED_ALWAYS it is step 0 and spreads, and its own byte is 0.
+ * At least one of `fields` and `info` is given. Query k's field is size[0] * size[1] * size[2] bytes at fields + k * field_stride, laid out as
+ * vx_read_region lays a box out (x fastest). field_stride is a multiple of 16 and at least the voxel count; 0 means the voxel count rounded
+ * up to 16. The bytes from the voxel count up to its multiple of 16 are written VX_FLOOD_BLOCKED (for every query, one without a position
+ * too); bytes beyond are not touched. With fields == NULL only the records are written: the cheap "is it sealed, how big is it".
+ * One workgroup of four waves a query: the box's passable cells as rows of 32 bits in LDS (each brick of 8 x 8 x 8 voxels entered once), a
+ * flood step a handful of shifts and ORs a row. One launch; no workgroup waits for another.
+ * Memory kinds, ordering and fences are vx_block_points'. VX_MEM_HOST: synchronous, through pinned memory; one launch, one wait.
+ * VX_MEM_DEVICE (fields and info aligned to 16 bytes): enqueued on the context's stream, returns after enqueueing, ordered behind the commits
+ * made so far and earlier batch calls (it may read the vx_entity records an earlier vx_physics_step wrote); later commits wait for it; the
+ * fence is vx_sync. The outputs must not overlap pos or one another; `shape` itself is read during the call.
+ * VX_ERR_INVALID_ARGUMENT (its message names the field; nothing is written): a null ctx; an unknown memory kind; with count > 0: a null
+ * shape or pos; fields and info both null; vx_block_points' stride and alignment rules; a size component of 0 or above 32; seed_at >= size;
+ * max_steps > VX_FLOOD_MAX_STEPS; an unknown flag bit; a field_stride that breaks the rule; count > 16777216 (2^24), or with fields count *
+ * field_stride > 16777216 bytes; a misaligned device output. count == 0: VX_OK (nothing is read or written). Before the first commit:
+ * VX_ERR_STATE. */
+int vx_flood_points(vx_context* ctx, const void* pos, uint32_t pos_stride, uint32_t count, const vx_flood_shape* shape, int memory,
+                    uint8_t* fields, uint32_t field_stride, vx_flood_info* info);
 /* Physics::step_many (src/systems/physics.rs:122-136) `steps` times over `count` entities in ONE kernel launch, against the world as last
  * committed: per step and entity the AABB's fan of axis-parallel picker rays (Aabb::generate_picker_tasks, svo_picker.rs:183-243: max_dst
  * 10), folded into six contact distances (parse_picker_results, svo_picker.rs:245-299), then Physics::update_entity and

@@ -198,6 +198,38 @@ pub struct vx_box_hit {
 /// `vx_box_hit::blocks` of a record that described no box (the header's VX_BOX_INVALID)
 pub const VX_BOX_INVALID: u32 = u32::MAX;
 
+/// What every query of a `vx_flood_points` call shares: the box of each query (1..32 cells an axis), the seed's cell inside it (lo =
+/// floor(p) - seed_at), the step limit (0..=VX_FLOOD_MAX_STEPS), a block id that passes like air (0: none), and 0 or VX_FLOOD_SEED_ALWAYS.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct vx_flood_shape {
+    pub size: [u32; 3],
+    pub seed_at: [u32; 3],
+    pub max_steps: u32,
+    pub pass_value: u32,
+    pub flags: u32,
+}
+/// What a flood reached (`vx_flood_points`): the cells with a step count (`VX_FLOOD_INVALID`: no position), the largest step count, the faces
+/// of the box a reached cell lies on (bit f numbered like face_id; 0 = enclosed), and `vx_block_points`' value at the seed.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct vx_flood_info {
+    pub reached: u32,
+    pub farthest: u32,
+    pub faces: u32,
+    pub seed_value: u32,
+}
+/// the header's VX_FLOOD_* (written in hexadecimal there and here)
+pub const VX_FLOOD_MAX_STEPS: u32 = 0xFA;
+/// a field's bytes that are no step count: of a position that is no position; passable but not reached; not passable
+pub const VX_FLOOD_NO_POSITION: u8 = 0xFD;
+pub const VX_FLOOD_UNREACHED: u8 = 0xFE;
+pub const VX_FLOOD_BLOCKED: u8 = 0xFF;
+/// `vx_flood_shape::flags`: the seed cell is step 0 and spreads even if it holds a block
+pub const VX_FLOOD_SEED_ALWAYS: u32 = 0x1;
+/// `vx_flood_info::reached` of a position that is no position
+pub const VX_FLOOD_INVALID: u32 = u32::MAX;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct vx_stats {
@@ -229,6 +261,8 @@ const _: () = assert!(std::mem::size_of::<vx_block_at>() == 8);
 const _: () = assert!(std::mem::size_of::<vx_scan_hit>() == 16);
 const _: () = assert!(std::mem::size_of::<vx_box_batch>() == 40);
 const _: () = assert!(std::mem::size_of::<vx_box_hit>() == 32);
+const _: () = assert!(std::mem::size_of::<vx_flood_shape>() == 36);
+const _: () = assert!(std::mem::size_of::<vx_flood_info>() == 16);
 const _: () = assert!(std::mem::size_of::<MaterialInstance>() == 32); // svo_registry.rs:29-40 is #[repr(C)]
 const _: () = assert!(std::mem::size_of::<PickerTask>() == 48 && std::mem::size_of::<PickerResult>() == 48); // svo_picker.rs:13-32
 
@@ -283,6 +317,11 @@ extern "C" {
     /// what each of `count` float boxes (`vx_box_batch`) holds: how many voxels of its cover hold a block (`only_value`: of that id), the first
     /// of them, their bounds; a record that is no box gives `VX_BOX_INVALID`; `memory`: VX_MEM_HOST / VX_MEM_DEVICE (`out` aligned to 16 bytes)
     pub fn vx_overlap_boxes(ctx: *mut vx_context, boxes: *const vx_box_batch, count: u32, memory: c_int, out: *mut vx_box_hit) -> c_int;
+    /// step distances through air around each of `count` positions (read as `vx_block_points` reads them): a breadth-first flood of the box
+    /// `shape` describes; query k's field -- a byte a cell, x fastest -- at fields + k * field_stride (a multiple of 16, 0 = the voxel count
+    /// rounded up to 16), its record at info[k]; either output may be null, not both; `memory`: VX_MEM_HOST / VX_MEM_DEVICE (both aligned to 16)
+    pub fn vx_flood_points(ctx: *mut vx_context, pos: *const c_void, pos_stride: u32, count: u32, shape: *const vx_flood_shape, memory: c_int,
+                           fields: *mut u8, field_stride: u32, info: *mut vx_flood_info) -> c_int;
     /// Physics::step_many (physics.rs:122-136) `steps` times for `count` entities in one launch; `memory`: VX_MEM_HOST / VX_MEM_DEVICE
     pub fn vx_physics_step(ctx: *mut vx_context, entities: *mut vx_entity, count: u32, memory: c_int, delta_time: f32, steps: u32,
                            contacts: *mut vx_aabb_result) -> c_int;

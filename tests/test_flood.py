@@ -1,0 +1,314 @@
+"""vx_flood_points on the GPU (voxel-rs_amd/csrc/blocks/kernels_flood.hip): step distances through air around a batch of positions, against
+the host harness's bytes (tests/cpp/flood_on_host.cpp: the same header on the host, which tests/test_flood_on_host.py holds against numpy over
+the dense arrays) and against numpy directly where the world or the positions change. Four worlds, both formats; every comparison is byte for
+byte. A case -- the first 100 seeded positions and every named one, every call of flood_cases.calls_for -- is computed once and left unchanged."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from batch_cases import _chunk_of
+from flood_cases import (BLOCKED, FLOOD_CASES, INVALID, MAX_STEPS, SEEDED, SHAPE, HostFlood, burrow_blocks, calls_for, differing, harness, in_form, make_flood_case,
+                         points_truth, positions_for, torch_positions)
+from helpers import vra  # noqa: F401
+from physics_cases import DT
+from voxel_rs_amd import hip
+
+pytestmark = pytest.mark.gpu
+SENTINEL = 0x5A5A5A5A
+TAIL = 48  # bytes behind the last field a call may write to, which it has to leave alone
+
+
+def make_context(c, capacity=None):
+    svo = hip.Svo(c.svo_type, c.world.size_in_bytes + (1 << 20) if capacity is None else capacity)
+    svo.set_materials(c.mats)
+    svo.set_textures(c.tex, 6)
+    svo.update_full(c.world)
+    return svo
+
+
+def filled_fields(count, stride):
+    import torch
+
+    return torch.full((count * stride + TAIL,), 0x5A, dtype=torch.uint8, device="cuda")
+
+
+def filled_info(count):
+    import torch
+
+    return torch.full((count + 2, 4), SENTINEL, dtype=torch.int32, device="cuda")
+
+
+def check_device(fields, info, count, stride, exp_fields, exp_info, what):
+    """Buffers longer than the call needs: the fields at their stride with the sentinel between and behind them, the records and two more.
+    info None: a call that was given no records."""
+    got_info = exp_info if info is None else hip.flood_infos_to_numpy(info)
+    got = fields.cpu().numpy()
+    rows = got[:count * stride].reshape(count, stride)
+    written = exp_fields.shape[1]
+    assert differing(rows[:, :written], got_info[:count], exp_fields, exp_info) is None, f"{what}: {differing(rows[:, :written], got_info[:count], exp_fields, exp_info)}"
+    assert (rows[:, written:] == 0x5A).all() and (got[count * stride:] == 0x5A).all() and (got_info[count:].view(np.uint32) == SENTINEL).all(), what
+
+
+_CASES = {}
+
+
+def the_case(name, fmt):
+    """The world, a context that has it, the positions the GPU is asked about and the harness's bytes for every call; shared by the tests."""
+    if (name, fmt) not in _CASES:
+        c = make_flood_case(name, fmt)
+        c.pick = np.concatenate([np.arange(100), np.arange(SEEDED, len(c.positions))])
+        c.calls = calls_for(c)
+        host = HostFlood(harness(), c)
+        c.expected = {call[0]: host.call(c, call, c.pick) for call in c.calls}
+        host.close()
+        c.svo = make_context(c)
+        _CASES[name, fmt] = c
+    return _CASES[name, fmt]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _contexts():
+    yield
+    for c in _CASES.values():
+        c.svo.close()
+    _CASES.clear()
+
+
+@pytest.fixture(scope="module", params=FLOOD_CASES, ids=[f"{n}-{f}" for n, f in FLOOD_CASES])
+def case(request):
+    return the_case(*request.param)
+
+
+def test_device_and_host_memory_give_the_harness_bytes(case):
+    """Every call -- every shape at every step limit, the flag, a pass_value, the forms in turn, vx_entity records among them --: the device
+    calls queued together before one vx_sync, each into buffers longer than it needs; then the same positions as host-memory calls."""
+    svo, n = case.svo, len(case.pick)
+    queued = []
+    for name, shape, max_steps, pass_value, flags, form in case.calls:
+        raw, stride, view = in_form(positions_for(case, shape)[case.pick], form)
+        pos = torch_positions(raw, stride, n)
+        f, i = svo.flood_points(pos, shape.size, shape.seed_at, max_steps, pass_value, flags, fields=filled_fields(n, shape.padded), info=filled_info(n))
+        queued.append((pos, view, f, i))
+    svo.sync()
+    floods = 0
+    for (name, shape, max_steps, pass_value, flags, form), (_, view, f, i) in zip(case.calls, queued):
+        exp_fields, exp_info = case.expected[name]
+        check_device(f, i, n, shape.padded, exp_fields, exp_info, f"{case.name}-{case.fmt} {name}")
+        hf, hi = svo.flood_points(view, shape.size, shape.seed_at, max_steps, pass_value, flags)
+        assert hi.dtype == hip.FLOOD_INFO_DTYPE and differing(hf, hi, exp_fields, exp_info) is None, f"{name} in host memory: {differing(hf, hi, exp_fields, exp_info)}"
+        floods += 2 * n
+    full = case.expected["17-250"][1]
+    assert (full["reached"] == INVALID).sum() == 10 and (full["reached"][:100] >= 100).mean() >= (0.6 if case.name != "burrow" else 0.3)
+    print(f"\n{case.name}-{case.fmt}: {floods} floods")
+
+
+def test_outputs_and_strides(case):
+    """Fields only, records only, and a field_stride larger than the box (the bytes beyond the rounded voxel count keep their sentinel), in
+    device and in host memory; one query; none."""
+    svo, shape, n = case.svo, SHAPE["17"], len(case.pick)
+    exp_fields, exp_info = case.expected["17-24"]
+    form = [c for c in case.calls if c[0] == "17-24"][0][5]
+    raw, stride, view = in_form(positions_for(case, shape)[case.pick], form)
+    pos = torch_positions(raw, stride, n)
+    wide = shape.padded + 32
+    f_only = svo.flood_points(pos, shape.size, shape.seed_at, 24, fields=filled_fields(n, shape.padded), info=None)
+    i_only = svo.flood_points(pos, shape.size, shape.seed_at, 24, fields=None, info=filled_info(n))
+    both = svo.flood_points(pos, shape.size, shape.seed_at, 24, fields=filled_fields(n, wide), info=filled_info(n), field_stride=wide)
+    one = svo.flood_points(pos[7:8], shape.size, shape.seed_at, 24, fields=filled_fields(1, shape.padded), info=filled_info(1))
+    none = svo.flood_points(pos[:0], shape.size, shape.seed_at, 24, fields=filled_fields(0, shape.padded), info=filled_info(0))
+    svo.sync()
+    assert f_only[1] is None and i_only[0] is None
+    check_device(f_only[0], None, n, shape.padded, exp_fields, exp_info, "fields only")
+    assert hip.flood_infos_to_numpy(i_only[1])[:n].tobytes() == exp_info.tobytes() and (hip.flood_infos_to_numpy(i_only[1])[n:].view(np.uint32) == SENTINEL).all()
+    check_device(both[0], both[1], n, wide, exp_fields, exp_info, "a stride larger than the box")
+    check_device(one[0], one[1], 1, shape.padded, exp_fields[7:8], exp_info[7:8], "one query")
+    check_device(none[0], none[1], 0, shape.padded, exp_fields[:0], exp_info[:0], "no query")
+    # host memory
+    hf, hi = svo.flood_points(view, shape.size, shape.seed_at, 24, info=None)
+    assert hi is None and (hf == exp_fields).all()
+    hf, hi = svo.flood_points(view, shape.size, shape.seed_at, 24, fields=None)
+    assert hf is None and hi.tobytes() == exp_info.tobytes()
+    out = np.full((n, wide), 0x5A, dtype=np.uint8)
+    hf, hi = svo.flood_points(view, shape.size, shape.seed_at, 24, fields=out, field_stride=wide)
+    assert (out[:, :shape.padded] == exp_fields).all() and (out[:, shape.padded:] == 0x5A).all() and hi.tobytes() == exp_info.tobytes()
+    hf, hi = svo.flood_points(view[7:8], shape.size, shape.seed_at, 24)
+    assert (hf == exp_fields[7:8]).all() and hi.tobytes() == exp_info[7:8].tobytes()
+    hf, hi = svo.flood_points(view[:0], shape.size, shape.seed_at, 24)
+    assert hf.shape == (0, shape.padded) and hi.shape == (0,)
+
+
+@pytest.mark.parametrize("fmt", ["esvo", "csvo"])
+def test_4096_copies_of_one_position(fmt):
+    """4,096 workgroups on one query: every field and record is the first one's, which is the harness's."""
+    import torch
+
+    c = the_case("glasshouse", fmt)
+    shape = SHAPE["9_two_bricks"]
+    exp_fields, exp_info = c.expected["9_two_bricks-250"]
+    k = int(np.flatnonzero((exp_info["reached"][:100] >= 100) & (exp_fields[:100] == BLOCKED)[:, :shape.voxels].any(axis=1))[0])
+    p = positions_for(c, shape)[c.pick][k]
+    pos = torch.from_numpy(np.tile(p, (4096, 1))).cuda()
+    f, i = c.svo.flood_points(pos, shape.size, shape.seed_at, 250, fields=filled_fields(4096, shape.padded), info=filled_info(4096))
+    c.svo.sync()
+    check_device(f, i, 4096, shape.padded, np.tile(exp_fields[k], (4096, 1)), np.tile(exp_info[k:k + 1], 4096), "4,096 copies")
+
+
+@pytest.mark.parametrize("fmt", ["esvo", "csvo"])
+def test_behind_physics_step(fmt):
+    """256 flying entities in device memory stepped 8 times (they move 1.28 voxels down and sideways), then vx_flood_points over the same
+    records' positions in place with no sync between the two calls; after one vx_sync the entities are read back, and fields and records are
+    numpy's for the positions the steps left -- which differ from those of the positions before."""
+    import torch
+
+    c = the_case("glasshouse", fmt)
+    rng = np.random.default_rng(91)
+    e = np.zeros(256, dtype=hip.ENTITY_DTYPE)
+    e["position"] = rng.uniform((2.0, 2.0, 2.0), (30.0, 14.0, 30.0), (256, 3))
+    e["velocity"] = np.stack([rng.uniform(-30, 30, len(e)), np.full(len(e), -40.0), rng.uniform(-30, 30, len(e))], axis=1)
+    e["aabb_offset"], e["aabb_extents"] = (-0.4, 0.0, -0.4), (0.8, 1.8, 0.8)
+    e["gravity"], e["max_fall_velocity"], e["flags"] = 20.0, 50.0, hip.ENTITY_FLYING
+    shape = SHAPE["17"]
+    d = torch.from_numpy(e.view(np.uint8).copy()).cuda()
+    c.svo.physics_step(d, DT, 8)
+    f, i = c.svo.flood_points(hip.entity_positions(d), shape.size, shape.seed_at, 24, fields=filled_fields(256, shape.padded), info=filled_info(256))
+    c.svo.sync()
+    after = d.cpu().numpy().view(hip.ENTITY_DTYPE)
+    assert (after["position"][:, 1] < e["position"][:, 1] - 1.0).all()
+    before = points_truth(c, e["position"], shape, 24)
+    exp_fields, exp_info = points_truth(c, after["position"], shape, 24)
+    assert ((before[0] != exp_fields).any(axis=1)).sum() >= 64
+    check_device(f, i, 256, shape.padded, exp_fields, exp_info, "behind vx_physics_step")
+    hf, hi = c.svo.flood_points(hip.entity_positions(after), shape.size, shape.seed_at, 24)
+    assert differing(hf, hi, exp_fields, exp_info) is None
+
+
+@pytest.mark.parametrize("fmt", ["esvo", "csvo"])
+def test_a_commit_opens_the_sealed_room(fmt):
+    """`burrow`: a call into device memory, a tunnel dug on the host chunk from the sealed room to the chunk's face and committed with
+    vx_commit_all, the call again into other buffers, one vx_sync: the first buffers show the old world -- the room enclosed, 27 cells -- and
+    the second the new one, the flood leaking out of the box; both exactly as numpy has them (the commit's uploads wait for the event
+    mark_world_read records behind the launch)."""
+    c = make_flood_case("burrow", fmt)
+    svo = make_context(c)
+    try:
+        shape = SHAPE["17"]
+        pts = c.positions[[c.names["room"], c.names["cell"], c.names["corridor"], c.names["serpentine_start"]]]
+        raw, stride, _ = in_form(pts, "packed")
+        pos = torch_positions(raw, stride, len(pts))
+        old = points_truth(c, pts, shape, MAX_STEPS)
+        first = svo.flood_points(pos, shape.size, shape.seed_at, MAX_STEPS, fields=filled_fields(len(pts), shape.padded), info=filled_info(len(pts)))
+        b = burrow_blocks()
+        b[0:4, 13, 5] = 0  # from the room's wall to the chunk's -x face: outside the chunk is air
+        c.world.set_chunk((1, 1, 1), _chunk_of((1, 1, 1), 5, b))
+        c.world.serialize()
+        svo.update_full(c.world)  # vx_commit_all
+        changed = c.truth.copy()
+        changed[:32, :32, :32] = b
+        new = points_truth(c, pts, shape, MAX_STEPS, truth=changed)
+        second = svo.flood_points(pos, shape.size, shape.seed_at, MAX_STEPS, fields=filled_fields(len(pts), shape.padded), info=filled_info(len(pts)))
+        svo.sync()
+        assert tuple(old[1][0]) == (27, 3, 0, 0) and new[1][0]["faces"] != 0 and new[1][0]["reached"] > 27 + 4
+        assert old[1][1:].tobytes() == new[1][1:].tobytes() and tuple(old[1][1]) == (1, 0, 0, 0)
+        check_device(*first, len(pts), shape.padded, *old, "before the commit")
+        check_device(*second, len(pts), shape.padded, *new, "after the commit")
+    finally:
+        svo.close()
+
+
+def test_esvo_big():
+    """The glasshouse in an ESVO context of 4 GiB, which selects the VX_SVO_ESVO_BIG build of the kernel: every call."""
+    c = the_case("glasshouse", "esvo")
+    h = C.c_void_p()
+    rc = hip.lib().vx_create(c.svo_type, 1 << 32, 0, C.byref(h))
+    if rc == 3:  # VX_ERR_OUT_OF_MEMORY, from vx_create itself: the one reason to skip (as tests/test_blocks.py::test_esvo_big)
+        pytest.skip("vx_create: " + hip.lib().vx_last_error().decode())
+    assert rc == 0, hip.lib().vx_last_error()
+    svo = hip.Svo.__new__(hip.Svo)
+    svo._h, svo.svo_type = h, c.svo_type
+    try:
+        svo.set_materials(c.mats)
+        svo.set_textures(c.tex, 6)
+        svo.update_full(c.world)
+        assert svo.get_stats()["capacity_bytes"] == 1 << 32
+        n, queued = len(c.pick), []
+        for name, shape, max_steps, pass_value, flags, form in c.calls:
+            raw, stride, view = in_form(positions_for(c, shape)[c.pick], form)
+            pos = torch_positions(raw, stride, n)
+            queued.append((pos, svo.flood_points(pos, shape.size, shape.seed_at, max_steps, pass_value, flags, fields=filled_fields(n, shape.padded), info=filled_info(n))))
+        svo.sync()
+        for (name, shape, *_), (_, (f, i)) in zip(c.calls, queued):
+            check_device(f, i, n, shape.padded, *c.expected[name], name)
+        name, shape, max_steps, pass_value, flags, form = c.calls[-1]
+        _, _, view = in_form(positions_for(c, shape)[c.pick], form)
+        hf, hi = svo.flood_points(view, shape.size, shape.seed_at, max_steps, pass_value, flags)
+        assert differing(hf, hi, *c.expected[name]) is None
+    finally:
+        svo.close()
+
+
+def test_errors_leave_the_output_alone(case):
+    """Every invalid argument returns VX_ERR_INVALID_ARGUMENT with the field named and leaves host and device outputs at their sentinels; a
+    context without a commit returns VX_ERR_STATE; count == 0 is VX_OK and writes nothing."""
+    import torch
+
+    L, h, vp = hip.lib(), case.svo._h, C.c_void_p
+    fields = np.full(2 * 4928 + 16, 0x5A, dtype=np.uint8)
+    info = np.full(3, SENTINEL, dtype=np.uint32).repeat(4)
+    sentinel = fields.tobytes() + info.tobytes()
+    d_fields, d_info = filled_fields(2, 4928), filled_info(2)
+    v = np.tile(np.array([3.5, 3.5, 3.5], dtype=np.float32), 8)
+    d_v = torch.from_numpy(v).cuda()
+    assert d_fields.data_ptr() % 16 == 0 and d_info.data_ptr() % 16 == 0 and v.ctypes.data % 4 == 0
+
+    def shape(**fields_):
+        s = hip.flood_shape((17, 17, 17), (8, 8, 8), 250)
+        for k, val in fields_.items():
+            setattr(s, k, val)
+        return s
+
+    u3 = C.c_uint32 * 3
+    hb, db = v.ctypes.data, d_v.data_ptr()
+    hf, hi, df, di = vp(fields.ctypes.data), vp(info.ctypes.data), vp(d_fields.data_ptr()), vp(d_info.data_ptr())
+    H, D = hip.VX_MEM_HOST, hip.VX_MEM_DEVICE
+    for call, word in ((lambda: L.vx_flood_points(None, hb, 12, 2, C.byref(shape()), H, hf, 0, hi), b"null context"),
+                       (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape()), 3, hf, 0, hi), b"VX_MEM"),
+                       (lambda: L.vx_flood_points(h, hb, 12, 2, None, H, hf, 0, hi), b"null shape"),
+                       (lambda: L.vx_flood_points(h, None, 12, 2, C.byref(shape()), H, hf, 0, hi), b"null pos"),
+                       (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape()), H, None, 0, None), b"fields and info"),
+                       (lambda: L.vx_flood_points(h, hb, 8, 2, C.byref(shape()), H, hf, 0, hi), b"pos_stride"),
+                       (lambda: L.vx_flood_points(h, hb + 2, 12, 2, C.byref(shape()), H, hf, 0, hi), b"pos must be aligned"),
+                       (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape(size=u3(17, 0, 17), seed_at=u3(8, 0, 8))), H, hf, 0, hi), b"size"),
+                       (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape(size=u3(17, 17, 33))), H, hf, 0, hi), b"size"),
+                       (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape(seed_at=u3(17, 8, 8))), H, hf, 0, hi), b"seed_at"),
+                       (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape(max_steps=251)), H, hf, 0, hi), b"max_steps"),
+                       (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape(flags=2)), H, hf, 0, hi), b"flags"),
+                       (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape()), H, hf, 4912, hi), b"field_stride"),
+                       (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape()), H, hf, 4936, hi), b"field_stride"),
+                       (lambda: L.vx_flood_points(h, hb, 12, (1 << 24) + 1, C.byref(shape()), H, None, 0, hi), b"count exceeds"),
+                       (lambda: L.vx_flood_points(h, hb, 12, 3405, C.byref(shape()), H, hf, 0, hi), b"count * field_stride"),
+                       (lambda: L.vx_flood_points(h, db, 12, 2, C.byref(shape()), D, vp(d_fields.data_ptr() + 8), 0, di), b"fields in device memory"),
+                       (lambda: L.vx_flood_points(h, db, 12, 2, C.byref(shape()), D, df, 0, vp(d_info.data_ptr() + 4)), b"info in device memory"),
+                       (lambda: L.vx_flood_points(h, db + 1, 12, 2, C.byref(shape()), D, df, 0, di), b"pos must be aligned")):
+        rc = call()
+        assert rc == 1 and word in L.vx_last_error(), (rc, word, L.vx_last_error())
+        assert fields.tobytes() + info.tobytes() == sentinel
+    fresh = hip.Svo(case.svo_type, 1 << 20)
+    try:
+        assert L.vx_flood_points(fresh._h, hb, 12, 2, C.byref(shape()), H, hf, 0, hi) == 6 and b"committed" in L.vx_last_error()
+        assert L.vx_flood_points(fresh._h, db, 12, 2, C.byref(shape()), D, df, 0, di) == 6
+        assert fields.tobytes() + info.tobytes() == sentinel
+    finally:
+        fresh.close()
+    # count == 0: VX_OK whatever the rest is; nothing is read or written
+    assert L.vx_flood_points(h, hb, 12, 0, C.byref(shape()), H, hf, 0, hi) == 0
+    assert L.vx_flood_points(h, None, 0, 0, None, H, None, 0, None) == 0
+    assert L.vx_flood_points(h, db, 12, 0, C.byref(shape()), D, df, 0, di) == 0
+    case.svo.sync()
+    assert fields.tobytes() + info.tobytes() == sentinel
+    assert (d_fields.cpu().numpy() == 0x5A).all() and (d_info.cpu().numpy().view(np.uint32) == SENTINEL).all()
+    # and the call still works: two queries at (3.5, 3.5, 3.5), as numpy has them
+    assert L.vx_flood_points(h, hb, 12, 2, C.byref(shape()), H, hf, 0, hi) == 0
+    exp_fields, exp_info = points_truth(case, v[:6].reshape(2, 3), SHAPE["17"], 250)
+    assert fields[:2 * 4928].tobytes() == exp_fields.tobytes() and (fields[2 * 4928:] == 0x5A).all()
+    assert info[:8].tobytes() == exp_info.tobytes() and (info[8:] == SENTINEL).all()

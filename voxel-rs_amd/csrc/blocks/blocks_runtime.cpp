@@ -1,8 +1,9 @@
 // libvoxelhip.so, block ids read from the device: vx_block_points and vx_read_region, the first block along an axis: vx_scan_points and
-// vx_scan_columns, the blocks of a box as a list: vx_list_region, and what a batch of float boxes holds: vx_overlap_boxes (include/voxel_hip.h)
-// -- argument checks (vx_blocks.hpp's, vx_scan.hpp's, vx_list.hpp's and vx_boxes.hpp's rules), the pinned scratch the host-memory calls read
-// and write through (csrc/vx_pinned_pool.hpp), and the launches of kernels_blocks.hip, kernels_scan.hip, kernels_list.hip and
-// kernels_boxes.hip.
+// vx_scan_columns, the blocks of a box as a list: vx_list_region, what a batch of float boxes holds: vx_overlap_boxes, and step distances
+// through air around a batch of positions: vx_flood_points (include/voxel_hip.h)
+// -- argument checks (vx_blocks.hpp's, vx_scan.hpp's, vx_list.hpp's, vx_boxes.hpp's and vx_flood.hpp's rules), the pinned scratch the
+// host-memory calls read and write through (csrc/vx_pinned_pool.hpp), and the launches of kernels_blocks.hip, kernels_scan.hip,
+// kernels_list.hip, kernels_boxes.hip and kernels_flood.hip.
 // A further translation unit on the context, like raycast_runtime.cpp: what it needs of the context is vx_context.hpp's (runtime.cpp).
 #include <cstring>
 #include <map>
@@ -258,5 +259,43 @@ int vx_overlap_boxes(vx_context* ctx, const vx_box_batch* boxes, uint32_t count,
                                       reinterpret_cast<vx_box_hit*>(pool.dev + at_out)));
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // synchronous, like vx_block_points' host-memory call
     std::memcpy(out, pool.host + at_out, out_bytes);
+    return VX_OK;
+}
+
+int vx_flood_points(vx_context* ctx, const void* pos, uint32_t pos_stride, uint32_t count, const vx_flood_shape* shape, int memory, uint8_t* fields,
+                    uint32_t field_stride, vx_flood_info* info) {
+    static_assert(sizeof(vx_flood_info) == 16 && sizeof(vx_flood_shape) == 36, "the ABI's record sizes");
+    if (memory != VX_MEM_HOST && memory != VX_MEM_DEVICE) return fail(VX_ERR_INVALID_ARGUMENT, "flood_points: memory is neither VX_MEM_HOST nor VX_MEM_DEVICE");
+    if (const char* what = vxb::check_flood(pos, pos_stride, count, shape, fields, field_stride, info)) return fail(VX_ERR_INVALID_ARGUMENT, std::string("flood_points: ") + what);
+    if (count && memory == VX_MEM_DEVICE && reinterpret_cast<uintptr_t>(fields) % 16) return fail(VX_ERR_INVALID_ARGUMENT, "flood_points: fields in device memory must be aligned to 16 bytes");
+    if (count && memory == VX_MEM_DEVICE && reinterpret_cast<uintptr_t>(info) % 16) return fail(VX_ERR_INVALID_ARGUMENT, "flood_points: info in device memory must be aligned to 16 bytes");
+    if (!ctx) return fail(VX_ERR_INVALID_ARGUMENT, "null context");
+    if (int rc = vxrt::check_ready(ctx)) return rc;
+    VX_LOCK(ctx);
+    if (count == 0) return VX_OK;
+    const uint32_t voxels = vxb::flood_voxels(*shape), packed = vxb::flood_round16(voxels);
+    const uint32_t stride = field_stride ? field_stride : packed;
+
+    if (memory == VX_MEM_DEVICE) {
+        HIP_TRY(vxk::launch_flood_points(kernel_variant(ctx), ctx->stream, vxrt::scene_on_bytes(ctx), pos, pos_stride, count, *shape, fields, stride, info));
+        return vxrt::mark_world_read(ctx);
+    }
+
+    // the positions packed at stride 12 | the records (at a multiple of 16) | the fields, each the voxel count rounded up to 16: the bytes a
+    // query writes, which go to the caller's stride from there
+    const size_t at_info = round16(size_t(count) * 12), info_bytes = info ? size_t(count) * sizeof(vx_flood_info) : 0;
+    const size_t at_fields = at_info + info_bytes, field_bytes = fields ? size_t(count) * packed : 0;
+    vxrt::PinnedPool& pool = vxrt::pinned_pool_of(ctx->device);
+    std::lock_guard<std::mutex> pool_lock(pool.mutex);
+    if (int rc = vxrt::pinned_pool_reserve(pool, at_fields + field_bytes)) return rc;
+    const uint8_t* from = static_cast<const uint8_t*>(pos);
+    if (pos_stride == 12) std::memcpy(pool.host, from, size_t(count) * 12);
+    else for (size_t i = 0; i < count; ++i) std::memcpy(pool.host + 12 * i, from + size_t(pos_stride) * i, 12);
+    HIP_TRY(vxk::launch_flood_points(kernel_variant(ctx), ctx->stream, vxrt::scene_on_bytes(ctx), pool.dev, 12, count, *shape, fields ? pool.dev + at_fields : nullptr,
+                                     packed, info ? reinterpret_cast<vx_flood_info*>(pool.dev + at_info) : nullptr));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // synchronous, like vx_block_points' host-memory call
+    if (info) std::memcpy(info, pool.host + at_info, info_bytes);
+    if (fields && stride == packed) std::memcpy(fields, pool.host + at_fields, field_bytes);
+    else if (fields) for (size_t i = 0; i < count; ++i) std::memcpy(fields + i * stride, pool.host + at_fields + i * packed, packed);
     return VX_OK;
 }

@@ -1,5 +1,6 @@
 // What blocks_runtime.cpp knows of the block lookup kernels (kernels_blocks.hip), of the scans along an axis (kernels_scan.hip) and of the
-// list of a box's blocks (kernels_list.hip) and of what a batch of float boxes holds (kernels_boxes.hip).
+// list of a box's blocks (kernels_list.hip), of what a batch of float boxes holds (kernels_boxes.hip) and of the floods around a batch of positions
+// (kernels_flood.hip).
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -7,6 +8,7 @@
 #include "vx_args.hpp"
 #include "vx_blocks.hpp"
 #include "vx_boxes.hpp"
+#include "vx_flood.hpp"
 #include "vx_list.hpp"
 #include "vx_scan.hpp"
 
@@ -47,5 +49,12 @@ hipError_t launch_list_write(int svo, hipStream_t stream, const vxd::SceneArgs& 
 hipError_t launch_overlap_boxes(int svo, hipStream_t stream, const vxd::SceneArgs& sc, const void* origin, const void* offset, const void* extents,
                                 uint32_t origin_stride, uint32_t offset_stride, uint32_t extents_stride, uint32_t only_value, uint32_t count,
                                 vx_box_hit* out);
+
+// `count` (1..2^24) workgroups of 256 threads, one query a workgroup: a float[3] at pos + i * pos_stride, read as launch_block_points reads it;
+// shape: within vxb::check_flood's rules (refused here too: the kernel indexes LDS by it); fields (may be null: records only): 16-byte aligned,
+// query i's bytes at fields + i * field_stride, field_stride a multiple of 16 and at least the voxel count, of which the voxel count rounded
+// up to 16 are written; info (may be null, not both): `count` records, 16-byte aligned. Device-visible memory that overlaps no input.
+hipError_t launch_flood_points(int svo, hipStream_t stream, const vxd::SceneArgs& sc, const void* pos, uint32_t pos_stride, uint32_t count, const vx_flood_shape& shape,
+                               uint8_t* fields, uint32_t field_stride, vx_flood_info* info);
 
 }  // namespace vxk

@@ -47,13 +47,19 @@ SCAN_HIT_DTYPE = np.dtype([("coord", "<i4"), ("value", "<u4"), ("cell_log2", "<u
 # read_region's order, their bounds [lo, hi); blocks == VX_BOX_INVALID: the record described no box
 BOX_HIT_DTYPE = np.dtype([("blocks", "<u4"), ("value", "<u4"), ("lo", "<i4", 3), ("hi", "<i4", 3)])
 VX_BOX_INVALID = 0xFFFFFFFF
+# vx_flood_info (vx_flood_points): what a flood reached -- cells with a step count (VX_FLOOD_INVALID: no position), the largest step count,
+# the faces of the box a reached cell lies on (0: enclosed), the value at the seed. A field is one byte a cell: the step count, or one of
+# VX_FLOOD_NO_POSITION, VX_FLOOD_UNREACHED, VX_FLOOD_BLOCKED
+FLOOD_INFO_DTYPE = np.dtype([("reached", "<u4"), ("farthest", "<u4"), ("faces", "<u4"), ("seed_value", "<u4")])
+VX_FLOOD_MAX_STEPS, VX_FLOOD_NO_POSITION, VX_FLOOD_UNREACHED, VX_FLOOD_BLOCKED = 250, 0xFD, 0xFE, 0xFF
+VX_FLOOD_SEED_ALWAYS, VX_FLOOD_INVALID = 1, 0xFFFFFFFF
 VX_DIR_NEG_X, VX_DIR_POS_X, VX_DIR_NEG_Y, VX_DIR_POS_Y, VX_DIR_NEG_Z, VX_DIR_POS_Z = range(6)
 VX_SCAN_NONE = -0x80000000
 VX_SCAN_TO_EDGE = 0xFFFFFFFF
 FACE_NORMALS = np.array([[-1, 0, 0], [1, 0, 0], [0, -1, 0], [0, 1, 0], [0, 0, -1], [0, 0, 1]], dtype=np.float32)  # by face_id
 assert HIT_DTYPE.itemsize == 48 and PICKER_TASK_DTYPE.itemsize == 48 and PICKER_RESULT_DTYPE.itemsize == 48 and FRAME_DTYPE.itemsize == 36
 assert ENTITY_DTYPE.itemsize == 64 and AABB_RESULT_DTYPE.itemsize == 24 and RAY_HIT_DTYPE.itemsize == 32 and SCAN_HIT_DTYPE.itemsize == 16
-assert BLOCK_AT_DTYPE.itemsize == 8 and BOX_HIT_DTYPE.itemsize == 32
+assert BLOCK_AT_DTYPE.itemsize == 8 and BOX_HIT_DTYPE.itemsize == 32 and FLOOD_INFO_DTYPE.itemsize == 16
 
 COUNTER_FIELDS = ["rays", "iterations", "pushes", "leaf_tests", "leaf_tests_trilinear", "boundaries", "csvo_header_bytes", "csvo_pointer_bytes",
                   "pixels", "lit_pixels", "shadow_rays", "wave_steps", "services", "refills", "tail_wave_steps", "tail_iterations"]
@@ -83,6 +89,11 @@ class BoxBatch(C.Structure):
     """vx_box_batch"""
     _fields_ = [("origin", C.c_void_p), ("offset", C.c_void_p), ("extents", C.c_void_p), ("origin_stride", C.c_uint32), ("offset_stride", C.c_uint32),
                 ("extents_stride", C.c_uint32), ("only_value", C.c_uint32)]
+
+
+class FloodShape(C.Structure):
+    """vx_flood_shape"""
+    _fields_ = [("size", C.c_uint32 * 3), ("seed_at", C.c_uint32 * 3), ("max_steps", C.c_uint32), ("pass_value", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class Result(C.Structure):
@@ -126,6 +137,7 @@ SYMBOLS = {
     "vx_scan_points": (_int, [_vp, _vp, _u32, _u32, _int, _u32, _int, _vp]),
     "vx_scan_columns": (_int, [_vp, C.POINTER(C.c_int32 * 3), C.POINTER(_u32 * 3), _int, _int, _vp]),
     "vx_overlap_boxes": (_int, [_vp, C.POINTER(BoxBatch), _u32, _int, _vp]),
+    "vx_flood_points": (_int, [_vp, _vp, _u32, _u32, C.POINTER(FloodShape), _int, _vp, _u32, _vp]),
     "vx_physics_step": (_int, [_vp, _vp, _u32, _int, C.c_float, _u32, _vp]),
     "vx_debug_trace": (_int, [_vp, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.c_float, _int, C.POINTER(Result), _vp, _u32, C.POINTER(_u32)]),
     "vx_sync": (_int, [_vp]),
@@ -306,6 +318,18 @@ def entity_boxes(entities):
 def box_hits_to_numpy(hits):
     """A device record tensor of Svo.overlap_boxes as BOX_HIT_DTYPE records (copies to the host: synchronise first)."""
     return hits.cpu().numpy().view(np.uint8).reshape(-1).view(BOX_HIT_DTYPE)
+
+
+def flood_infos_to_numpy(infos):
+    """A device record tensor of Svo.flood_points as FLOOD_INFO_DTYPE records (copies to the host: synchronise first)."""
+    return infos.cpu().numpy().view(np.uint8).reshape(-1).view(FLOOD_INFO_DTYPE)
+
+
+def flood_shape(size, seed_at=None, max_steps=VX_FLOOD_MAX_STEPS, pass_value=0, flags=0):
+    """A vx_flood_shape; seed_at None: the box's centre cell, size // 2."""
+    size = [int(v) for v in size]
+    seed_at = [v // 2 for v in size] if seed_at is None else [int(v) for v in seed_at]
+    return FloodShape((C.c_uint32 * 3)(*size), (C.c_uint32 * 3)(*seed_at), int(max_steps), int(pass_value), int(flags))
 
 
 def ray_hits_to_numpy(hits):
@@ -862,6 +886,56 @@ class Svo:
             raise TypeError("overlap_boxes: out must be a contiguous CUDA tensor of at least N x 32 bytes")
         _check(lib().vx_overlap_boxes(self._h, C.byref(batch), count, VX_MEM_DEVICE, _vp(out.data_ptr())))
         return out
+
+    # -- step distances through air (a breadth-first search over get_block, gameplay.rs:161-201, for a batch) ----------------------------------------
+    def flood_points(self, positions, size, seed_at=None, max_steps=VX_FLOOD_MAX_STEPS, pass_value=0, flags=0, fields=True, info=True, field_stride=0):
+        """vx_flood_points: the breadth-first flood of the box of `size` cells (1..32 an axis) around each position, whose cell floor(p) is cell
+        `seed_at` of the box (None: size // 2). positions: as block_points takes them. Returns (fields, info), either None when not asked for:
+        fields -- uint8 [N, field_stride], of which the first size.x * size.y * size.z bytes of a row are the query's cells, x fastest (the step
+        count, or VX_FLOOD_NO_POSITION, VX_FLOOD_UNREACHED, VX_FLOOD_BLOCKED); field_stride 0: the voxel count rounded up to 16 -- and info --
+        FLOOD_INFO_DTYPE records. fields and info: True for fresh memory, False or None for none, or the memory to write to.
+        Host (a NumPy array): synchronous.
+        Device (a torch CUDA tensor): returns after enqueueing, without synchronising -- pair with sync(); fields is a uint8 tensor and info
+        an int32 tensor of shape (N, 4) on the positions' device (flood_infos_to_numpy)."""
+        host = isinstance(positions, np.ndarray)
+        if len(positions.shape) != 2 or positions.shape[1] != 3:
+            raise TypeError("flood_points: positions must have shape (N, 3)")
+        count = int(positions.shape[0])
+        if not host and not getattr(positions, "is_cuda", False):
+            raise TypeError("flood_points: positions must be a NumPy array or a torch CUDA tensor")
+        shape = flood_shape(size, seed_at, max_steps, pass_value, flags)
+        voxels = int(shape.size[0]) * int(shape.size[1]) * int(shape.size[2])
+        stride = int(field_stride) if field_stride else (voxels + 15) // 16 * 16
+        ptr, pos_stride = _ray_vectors("positions", positions, count, 3)
+        fields = None if fields is False else fields
+        info = None if info is False else info
+        if host:
+            if fields is True:
+                fields = np.zeros((count, stride), dtype=np.uint8)
+            elif fields is not None and (not isinstance(fields, np.ndarray) or fields.dtype != np.uint8 or fields.size < count * stride or not fields.flags.c_contiguous
+                                         or not fields.flags.writeable):
+                raise TypeError("flood_points: fields must be a writeable C-contiguous uint8 array of at least N x field_stride bytes")
+            if info is True:
+                info = np.zeros(count, dtype=FLOOD_INFO_DTYPE)
+            elif info is not None and (not isinstance(info, np.ndarray) or info.dtype != FLOOD_INFO_DTYPE or info.size != count or not info.flags.c_contiguous
+                                       or not info.flags.writeable):
+                raise TypeError("flood_points: info must be a writeable C-contiguous array of N hip.FLOOD_INFO_DTYPE records")
+            _check(lib().vx_flood_points(self._h, _vp(ptr), pos_stride, count, C.byref(shape), VX_MEM_HOST, None if fields is None else fields.ctypes.data_as(_vp),
+                                         int(field_stride), None if info is None else info.ctypes.data_as(_vp)))
+            return fields, info
+        import torch
+
+        if fields is True:
+            fields = torch.empty((count, stride), dtype=torch.uint8, device=positions.device)
+        elif fields is not None and (not fields.is_cuda or not fields.is_contiguous() or fields.numel() * fields.element_size() < count * stride):
+            raise TypeError("flood_points: fields must be a contiguous CUDA tensor of at least N x field_stride bytes")
+        if info is True:
+            info = torch.empty((count, 4), dtype=torch.int32, device=positions.device)
+        elif info is not None and (not info.is_cuda or not info.is_contiguous() or info.numel() * info.element_size() < count * FLOOD_INFO_DTYPE.itemsize):
+            raise TypeError("flood_points: info must be a contiguous CUDA tensor of at least N x 16 bytes")
+        _check(lib().vx_flood_points(self._h, _vp(ptr), pos_stride, count, C.byref(shape), VX_MEM_DEVICE, None if fields is None else _vp(fields.data_ptr()),
+                                     int(field_stride), None if info is None else _vp(info.data_ptr())))
+        return fields, info
 
     # -- Physics::step_many (src/systems/physics.rs:122-136), on the device ---------------------------------------
     def physics_step(self, entities, dt, steps=1, want_contacts=False, count=None, contacts=None):

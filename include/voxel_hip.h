@@ -222,6 +222,29 @@ typedef struct vx_flood_info {
     uint32_t seed_value;   /* vx_block_points' value at the seed cell */
 } vx_flood_info;
 
+#define VX_LIGHT_MAX_SIDE    48u
+#define VX_LIGHT_MAX_PROPS   4096u
+#define VX_LIGHT_TRANSPARENT 0x10u   /* props bit 4: light passes through this block */
+#define VX_LIGHT_NO_SKY      1u      /* flags: leave the sky channel (the high nibble) 0 and scan no column */
+#define VX_LIGHT_NO_BLOCKS   2u      /* flags: leave the block channel (the low nibble) 0 */
+#define VX_LIGHT_INVALID     0xFFFFFFFFu
+/* What every query of a vx_light_boxes call shares; read on the host during the call. */
+typedef struct vx_light_shape {
+    uint32_t size[3];        /* the box of each query, 1..VX_LIGHT_MAX_SIDE an axis */
+    uint32_t flags;          /* 0, VX_LIGHT_NO_SKY or VX_LIGHT_NO_BLOCKS; not both */
+    const uint8_t* props;    /* HOST memory whatever `memory` says: props[id] = emission (bits 0..3) | VX_LIGHT_TRANSPARENT; bits 5..7 must be 0 */
+    uint32_t props_count;    /* 0..VX_LIGHT_MAX_PROPS; ids at or above it: opaque, emit nothing. props[0] is ignored: air passes light and emits
+                                none */
+} vx_light_shape;
+/* What the light of a box amounts to (vx_light_boxes); 16 bytes. */
+typedef struct vx_light_info {
+    uint32_t lit;            /* cells whose byte is not 0 */
+    uint32_t sources;        /* cells of the box whose block emits (emission > 0); 0 under VX_LIGHT_NO_BLOCKS */
+    uint32_t open_columns;   /* columns (x, z) of the box whose TOP cell is exposed to the sky; 0 under VX_LIGHT_NO_SKY */
+    uint32_t faces;          /* bit f (numbered like face_id) set when a cell on that face of the box has a level >= 2 in either channel:
+                                light that would go on beyond the box */
+} vx_light_info;
+
 /* Optional per-pixel record of what trace_ray saw (world.glsl:27-90) -- the "hit position, depth" outputs
  * used for parity checks; not part of the reference's surface. */
 typedef struct vx_hit {
@@ -575,6 +598,42 @@ int vx_overlap_boxes(vx_context* ctx, const vx_box_batch* boxes, uint32_t count,
  * VX_ERR_STATE. */
 int vx_flood_points(vx_context* ctx, const void* pos, uint32_t pos_stride, uint32_t count, const vx_flood_shape* shape, int memory,
                     uint8_t* fields, uint32_t field_stride, vx_flood_info* info);
+/* Sky and block light levels, 0..15 each, for every cell of `count` boxes of the world the device holds -- what mesh shading, mob spawning,
+ * plant growth and "is this room dark" read, and what the reference's host would compute by looping get_block (gameplay.rs:161-201) over a
+ * section and its margin and running two breadth-first searches. Everything is integer and exact.
+ * Box k is [lo_k, lo_k + size): lo_k an int32[3] read at lo + k * lo_stride, in the memory kind of the call, 4-byte aligned, the stride a
+ * multiple of 4 and at least 12 (a packed array, or a field of a larger record in place). It is kept modulo 2^32 as vx_read_region keeps a
+ * box: it may be negative or overhang the world. A cell holds vx_block_points' value at its centre: outside [0, 2^depth)^3 is air, a LOD
+ * voxel gives its value to each of its fine voxels. A cell is passable when its value is 0 or props[value] has VX_LIGHT_TRANSPARENT.
+ * Sky (the high nibble): a cell is exposed when it is passable and every cell above it in the world -- the same x and z, larger y, inside the
+ * box or beyond it, up to the world's top -- is passable. Exposed cells have 15; every other passable cell has max(0, the largest of its six
+ * neighbours inside the box - 1); impassable cells have 0. Cells outside the box do not exist for the spread: only the exposure test looks
+ * beyond the box, and only upwards.
+ * Block (the low nibble): a cell whose block emits e > 0 has at least e whether or not it is passable (a lamp is a block); a passable cell
+ * has the larger of its own emission and (the largest of its six neighbours inside the box - 1), floored at 0; an impassable cell has just
+ * its emission: it lights its neighbours but lets nothing through.
+ * Light falls off by one a step, so nothing farther than 15 cells matters: a caller who wants the levels of a 16^3 section to be independent
+ * of the box asks for the section with 15 cells of margin on every side -- a box of 46 -- and keeps the middle.
+ * At least one of `fields` and `info` is given. Query k's field is size[0] * size[1] * size[2] bytes at fields + k * field_stride, sky << 4 |
+ * block a cell, laid out as vx_read_region lays a box out (x fastest). field_stride is a multiple of 16 and at least the voxel count; 0
+ * means the voxel count rounded up to 16. The bytes from the voxel count up to its multiple of 16 are written 0; bytes beyond are not
+ * touched. With fields == NULL only the records are written. A flag leaves its channel out: the nibble is 0 and so is the record's count
+ * of it (open_columns, sources).
+ * One workgroup of four waves a query: the box's passable cells and emissions as rows of 64 bits (each brick of 8 x 8 x 8 voxels entered
+ * once), one upward scan a column above the box that steps over empty octree cells, a level-ordered flood of shifts and ORs a row and
+ * channel. One launch; no workgroup waits for another.
+ * Memory kinds, ordering and fences are vx_flood_points'. VX_MEM_HOST: synchronous, through pinned memory; one launch, one wait.
+ * VX_MEM_DEVICE (fields and info aligned to 16 bytes): enqueued on the context's stream, returns after enqueueing, ordered behind the commits
+ * made so far and earlier batch calls; later commits wait for it; the fence is vx_sync. The outputs must not overlap lo or one another.
+ * `shape` and `props` are host memory read during the call: props travels through pinned memory ordered on the stream, and the caller may
+ * overwrite it when the call returns.
+ * VX_ERR_INVALID_ARGUMENT (its message names the field; nothing is written): a null ctx; an unknown memory kind; with count > 0: a null
+ * shape or lo; fields and info both null; a stride or an alignment that breaks the rules above; a size component of 0 or above 48; an unknown
+ * flag bit, or both flags; props_count > 4096, or null props with props_count > 0; a props byte with one of bits 5..7 set; a field_stride that
+ * breaks the rule; count > 16777216 (2^24), or with fields count * field_stride > 16777216 bytes; a misaligned device output. count == 0:
+ * VX_OK (nothing is read or written). Before the first commit: VX_ERR_STATE. */
+int vx_light_boxes(vx_context* ctx, const void* lo, uint32_t lo_stride, uint32_t count, const vx_light_shape* shape, int memory,
+                   uint8_t* fields, uint32_t field_stride, vx_light_info* info);
 /* Physics::step_many (src/systems/physics.rs:122-136) `steps` times over `count` entities in ONE kernel launch, against the world as last
  * committed: per step and entity the AABB's fan of axis-parallel picker rays (Aabb::generate_picker_tasks, svo_picker.rs:183-243: max_dst
  * 10), folded into six contact distances (parse_picker_results, svo_picker.rs:245-299), then Physics::update_entity and

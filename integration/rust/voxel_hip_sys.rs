@@ -230,6 +230,38 @@ pub const VX_FLOOD_SEED_ALWAYS: u32 = 0x1;
 /// `vx_flood_info::reached` of a position that is no position
 pub const VX_FLOOD_INVALID: u32 = u32::MAX;
 
+/// What every query of a `vx_light_boxes` call shares: the box of each query (1..=VX_LIGHT_MAX_SIDE cells an axis), 0 or one of
+/// VX_LIGHT_NO_SKY and VX_LIGHT_NO_BLOCKS, and the table of props -- HOST memory whatever the call's memory kind, read during the call:
+/// props[id] = emission (bits 0..3) | VX_LIGHT_TRANSPARENT; ids at or above props_count (at most VX_LIGHT_MAX_PROPS) are opaque and dark.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct vx_light_shape {
+    pub size: [u32; 3],
+    pub flags: u32,
+    pub props: *const u8,
+    pub props_count: u32,
+}
+/// What the light of a box amounts to (`vx_light_boxes`): the cells whose byte is not 0, the cells that emit (0 under VX_LIGHT_NO_BLOCKS),
+/// the columns whose top cell is exposed to the sky (0 under VX_LIGHT_NO_SKY), and the faces of the box (bit f numbered like face_id) on
+/// which a cell has a level of 2 or more in either channel.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct vx_light_info {
+    pub lit: u32,
+    pub sources: u32,
+    pub open_columns: u32,
+    pub faces: u32,
+}
+/// the header's VX_LIGHT_* (48 and 4,096, written in hexadecimal here)
+pub const VX_LIGHT_MAX_SIDE: u32 = 0x30;
+pub const VX_LIGHT_MAX_PROPS: u32 = 0x1000;
+/// a props byte's bit 4: light passes through this block
+pub const VX_LIGHT_TRANSPARENT: u8 = 0x10;
+/// `vx_light_shape::flags`: leave that channel 0
+pub const VX_LIGHT_NO_SKY: u32 = 0x1;
+pub const VX_LIGHT_NO_BLOCKS: u32 = 0x2;
+pub const VX_LIGHT_INVALID: u32 = u32::MAX;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct vx_stats {
@@ -263,6 +295,8 @@ const _: () = assert!(std::mem::size_of::<vx_box_batch>() == 40);
 const _: () = assert!(std::mem::size_of::<vx_box_hit>() == 32);
 const _: () = assert!(std::mem::size_of::<vx_flood_shape>() == 36);
 const _: () = assert!(std::mem::size_of::<vx_flood_info>() == 16);
+const _: () = assert!(std::mem::size_of::<vx_light_shape>() == 32);
+const _: () = assert!(std::mem::size_of::<vx_light_info>() == 16);
 const _: () = assert!(std::mem::size_of::<MaterialInstance>() == 32); // svo_registry.rs:29-40 is #[repr(C)]
 const _: () = assert!(std::mem::size_of::<PickerTask>() == 48 && std::mem::size_of::<PickerResult>() == 48); // svo_picker.rs:13-32
 
@@ -322,6 +356,11 @@ extern "C" {
     /// rounded up to 16), its record at info[k]; either output may be null, not both; `memory`: VX_MEM_HOST / VX_MEM_DEVICE (both aligned to 16)
     pub fn vx_flood_points(ctx: *mut vx_context, pos: *const c_void, pos_stride: u32, count: u32, shape: *const vx_flood_shape, memory: c_int,
                            fields: *mut u8, field_stride: u32, info: *mut vx_flood_info) -> c_int;
+    /// sky and block light levels (0..15 each, sky << 4 | block a cell, x fastest) of the boxes [lo_k, lo_k + shape.size), lo_k an int32[3]
+    /// at lo + k * lo_stride; box k's field at fields + k * field_stride (a multiple of 16, 0 = the voxel count rounded up to 16), its record
+    /// at info[k]; either output may be null, not both; `memory`: VX_MEM_HOST / VX_MEM_DEVICE (both aligned to 16); props is host memory
+    pub fn vx_light_boxes(ctx: *mut vx_context, lo: *const c_void, lo_stride: u32, count: u32, shape: *const vx_light_shape, memory: c_int,
+                          fields: *mut u8, field_stride: u32, info: *mut vx_light_info) -> c_int;
     /// Physics::step_many (physics.rs:122-136) `steps` times for `count` entities in one launch; `memory`: VX_MEM_HOST / VX_MEM_DEVICE
     pub fn vx_physics_step(ctx: *mut vx_context, entities: *mut vx_entity, count: u32, memory: c_int, delta_time: f32, steps: u32,
                            contacts: *mut vx_aabb_result) -> c_int;

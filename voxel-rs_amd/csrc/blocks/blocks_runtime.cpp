@@ -1,9 +1,9 @@
 // libvoxelhip.so, block ids read from the device: vx_block_points and vx_read_region, the first block along an axis: vx_scan_points and
-// vx_scan_columns, the blocks of a box as a list: vx_list_region, what a batch of float boxes holds: vx_overlap_boxes, and step distances
-// through air around a batch of positions: vx_flood_points (include/voxel_hip.h)
-// -- argument checks (vx_blocks.hpp's, vx_scan.hpp's, vx_list.hpp's, vx_boxes.hpp's and vx_flood.hpp's rules), the pinned scratch the
-// host-memory calls read and write through (csrc/vx_pinned_pool.hpp), and the launches of kernels_blocks.hip, kernels_scan.hip,
-// kernels_list.hip, kernels_boxes.hip and kernels_flood.hip.
+// vx_scan_columns, the blocks of a box as a list: vx_list_region, what a batch of float boxes holds: vx_overlap_boxes, step distances
+// through air around a batch of positions: vx_flood_points, and the light levels of a batch of boxes: vx_light_boxes (include/voxel_hip.h)
+// -- argument checks (vx_blocks.hpp's, vx_scan.hpp's, vx_list.hpp's, vx_boxes.hpp's, vx_flood.hpp's and vx_light.hpp's rules), the pinned
+// scratch the host-memory calls read and write through (csrc/vx_pinned_pool.hpp), and the launches of kernels_blocks.hip, kernels_scan.hip,
+// kernels_list.hip, kernels_boxes.hip, kernels_flood.hip and kernels_light.hip.
 // A further translation unit on the context, like raycast_runtime.cpp: what it needs of the context is vx_context.hpp's (runtime.cpp).
 #include <cstring>
 #include <map>
@@ -54,6 +54,76 @@ int reserve_list_counts(vx_context* ctx, size_t entries, uint32_t** counts) {
     }
     *counts = s.counts;
     return VX_OK;
+}
+
+// vx_light_boxes' table of props for a device-memory call, which returns before the launch has read it: a small ring of pinned buffers the
+// kernel reads in place (no copy command), each guarded by an event, as views_runtime.cpp keeps its camera tables -- a call takes the next
+// slot after waiting for the launch that read it four calls ago. One ring a device, kept for the life of the process; a slot's event is
+// recorded on a stream of the ring's own, which is never destroyed and waits for the launch through an event that lives for the call alone
+// (an event may not be waited for once the stream it was recorded on is gone with its context).
+struct PropsSlot {
+    uint8_t* host = nullptr;
+    uint8_t* dev = nullptr;
+    hipEvent_t done = nullptr;
+    bool used = false;
+};
+struct PropsRing {
+    static constexpr unsigned kSlots = 4;
+    std::mutex mutex;
+    PropsSlot slot[kSlots];
+    unsigned next = 0;
+    hipStream_t fence = nullptr;  // carries the slots' events; no work of its own
+};
+
+PropsRing& props_ring_of(int device) {
+    static std::mutex rings_mutex;
+    static std::map<int, PropsRing> rings;  // (node-based: a ring's address is stable)
+    std::lock_guard<std::mutex> lock(rings_mutex);
+    return rings[device];
+}
+
+// the ring's next slot, idle, under the ring's mutex
+int props_slot_acquire(PropsRing& ring, PropsSlot** out) {
+    PropsSlot& s = ring.slot[ring.next++ % PropsRing::kSlots];
+    if (!s.done) HIP_TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+    if (s.used) HIP_TRY(hipEventSynchronize(s.done));
+    s.used = false;
+    if (!s.host) {
+        void *h = nullptr, *d = nullptr;
+        HIP_TRY(hipHostMalloc(&h, VX_LIGHT_MAX_PROPS, hipHostMallocMapped));
+        if (const hipError_t e = hipHostGetDevicePointer(&d, h, 0); e != hipSuccess) {
+            (void)hipHostFree(h);
+            HIP_TRY(e);
+        }
+        s.host = static_cast<uint8_t*>(h);
+        s.dev = static_cast<uint8_t*>(d);
+    }
+    *out = &s;
+    return VX_OK;
+}
+
+// slot.done follows everything queued on `stream` so far, without belonging to it
+hipError_t props_slot_guard(PropsRing& ring, PropsSlot& slot, hipStream_t stream) {
+    if (!ring.fence)
+        if (const hipError_t e = hipStreamCreateWithFlags(&ring.fence, hipStreamNonBlocking); e != hipSuccess) return e;
+    hipEvent_t queued = nullptr;
+    if (const hipError_t e = hipEventCreateWithFlags(&queued, hipEventDisableTiming); e != hipSuccess) return e;
+    hipError_t e = hipEventRecord(queued, stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(ring.fence, queued, 0);
+    if (e == hipSuccess) e = hipEventRecord(slot.done, ring.fence);
+    (void)hipEventDestroy(queued);  // (released once it has happened)
+    if (e != hipSuccess) {
+        // no guard: the slot may not be handed out again before the launch is through with it
+        (void)hipStreamSynchronize(stream);
+        slot.used = false;
+    }
+    return e;
+}
+
+// the table as the kernel reads it: props_count bytes, zeros up to VX_LIGHT_MAX_PROPS
+void fill_props(const vx_light_shape& s, uint8_t* at) {
+    if (s.props_count) std::memcpy(at, s.props, s.props_count);
+    std::memset(at + s.props_count, 0, VX_LIGHT_MAX_PROPS - s.props_count);
 }
 
 }  // namespace
@@ -294,6 +364,54 @@ int vx_flood_points(vx_context* ctx, const void* pos, uint32_t pos_stride, uint3
     HIP_TRY(vxk::launch_flood_points(kernel_variant(ctx), ctx->stream, vxrt::scene_on_bytes(ctx), pool.dev, 12, count, *shape, fields ? pool.dev + at_fields : nullptr,
                                      packed, info ? reinterpret_cast<vx_flood_info*>(pool.dev + at_info) : nullptr));
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // synchronous, like vx_block_points' host-memory call
+    if (info) std::memcpy(info, pool.host + at_info, info_bytes);
+    if (fields && stride == packed) std::memcpy(fields, pool.host + at_fields, field_bytes);
+    else if (fields) for (size_t i = 0; i < count; ++i) std::memcpy(fields + i * stride, pool.host + at_fields + i * packed, packed);
+    return VX_OK;
+}
+
+int vx_light_boxes(vx_context* ctx, const void* lo, uint32_t lo_stride, uint32_t count, const vx_light_shape* shape, int memory, uint8_t* fields,
+                   uint32_t field_stride, vx_light_info* info) {
+    static_assert(sizeof(vx_light_info) == 16 && sizeof(vx_light_shape) == 32, "the ABI's record sizes");
+    if (memory != VX_MEM_HOST && memory != VX_MEM_DEVICE) return fail(VX_ERR_INVALID_ARGUMENT, "light_boxes: memory is neither VX_MEM_HOST nor VX_MEM_DEVICE");
+    if (const char* what = vxb::check_light(lo, lo_stride, count, shape, fields, field_stride, info)) return fail(VX_ERR_INVALID_ARGUMENT, std::string("light_boxes: ") + what);
+    if (count && memory == VX_MEM_DEVICE && reinterpret_cast<uintptr_t>(fields) % 16) return fail(VX_ERR_INVALID_ARGUMENT, "light_boxes: fields in device memory must be aligned to 16 bytes");
+    if (count && memory == VX_MEM_DEVICE && reinterpret_cast<uintptr_t>(info) % 16) return fail(VX_ERR_INVALID_ARGUMENT, "light_boxes: info in device memory must be aligned to 16 bytes");
+    if (!ctx) return fail(VX_ERR_INVALID_ARGUMENT, "null context");
+    if (int rc = vxrt::check_ready(ctx)) return rc;
+    VX_LOCK(ctx);
+    if (count == 0) return VX_OK;
+    const uint32_t voxels = vxb::light_voxels(shape->size), packed = vxb::light_round16(voxels);
+    const uint32_t stride = field_stride ? field_stride : packed;
+
+    if (memory == VX_MEM_DEVICE) {
+        PropsRing& ring = props_ring_of(ctx->device);
+        std::lock_guard<std::mutex> ring_lock(ring.mutex);
+        PropsSlot* slot = nullptr;
+        if (int rc = props_slot_acquire(ring, &slot)) return rc;
+        fill_props(*shape, slot->host);
+        slot->used = true;  // (from here on the stream may hold work that reads the slot)
+        const hipError_t launched = vxk::launch_light_boxes(kernel_variant(ctx), ctx->stream, vxrt::scene_on_bytes(ctx), lo, lo_stride, count, shape->size, shape->flags,
+                                                            slot->dev, fields, stride, info);
+        HIP_TRY(props_slot_guard(ring, *slot, ctx->stream));
+        HIP_TRY(launched);
+        return vxrt::mark_world_read(ctx);
+    }
+
+    // the props | the boxes packed at stride 12 | the records (at a multiple of 16) | the fields, each the voxel count rounded up to 16: the
+    // bytes a query writes, which go to the caller's stride from there
+    const size_t at_lo = VX_LIGHT_MAX_PROPS, at_info = at_lo + round16(size_t(count) * 12), info_bytes = info ? size_t(count) * sizeof(vx_light_info) : 0;
+    const size_t at_fields = at_info + info_bytes, field_bytes = fields ? size_t(count) * packed : 0;
+    vxrt::PinnedPool& pool = vxrt::pinned_pool_of(ctx->device);
+    std::lock_guard<std::mutex> pool_lock(pool.mutex);
+    if (int rc = vxrt::pinned_pool_reserve(pool, at_fields + field_bytes)) return rc;
+    fill_props(*shape, pool.host);
+    const uint8_t* from = static_cast<const uint8_t*>(lo);
+    if (lo_stride == 12) std::memcpy(pool.host + at_lo, from, size_t(count) * 12);
+    else for (size_t i = 0; i < count; ++i) std::memcpy(pool.host + at_lo + 12 * i, from + size_t(lo_stride) * i, 12);
+    HIP_TRY(vxk::launch_light_boxes(kernel_variant(ctx), ctx->stream, vxrt::scene_on_bytes(ctx), pool.dev + at_lo, 12, count, shape->size, shape->flags, pool.dev,
+                                    fields ? pool.dev + at_fields : nullptr, packed, info ? reinterpret_cast<vx_light_info*>(pool.dev + at_info) : nullptr));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // synchronous, like vx_flood_points' host-memory call
     if (info) std::memcpy(info, pool.host + at_info, info_bytes);
     if (fields && stride == packed) std::memcpy(fields, pool.host + at_fields, field_bytes);
     else if (fields) for (size_t i = 0; i < count; ++i) std::memcpy(fields + i * stride, pool.host + at_fields + i * packed, packed);

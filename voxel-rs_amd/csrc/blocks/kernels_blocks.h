@@ -1,6 +1,6 @@
 // What blocks_runtime.cpp knows of the block lookup kernels (kernels_blocks.hip), of the scans along an axis (kernels_scan.hip) and of the
-// list of a box's blocks (kernels_list.hip), of what a batch of float boxes holds (kernels_boxes.hip) and of the floods around a batch of positions
-// (kernels_flood.hip).
+// list of a box's blocks (kernels_list.hip), of what a batch of float boxes holds (kernels_boxes.hip), of the floods around a batch of positions
+// (kernels_flood.hip) and of the light levels of a batch of boxes (kernels_light.hip).
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -9,6 +9,7 @@
 #include "vx_blocks.hpp"
 #include "vx_boxes.hpp"
 #include "vx_flood.hpp"
+#include "vx_light.hpp"
 #include "vx_list.hpp"
 #include "vx_scan.hpp"
 
@@ -56,5 +57,13 @@ hipError_t launch_overlap_boxes(int svo, hipStream_t stream, const vxd::SceneArg
 // up to 16 are written; info (may be null, not both): `count` records, 16-byte aligned. Device-visible memory that overlaps no input.
 hipError_t launch_flood_points(int svo, hipStream_t stream, const vxd::SceneArgs& sc, const void* pos, uint32_t pos_stride, uint32_t count, const vx_flood_shape& shape,
                                uint8_t* fields, uint32_t field_stride, vx_flood_info* info);
+
+// `count` (1..2^24) workgroups of 256 threads, one box a workgroup: an int32[3] at lo + i * lo_stride (4-byte aligned, the stride a multiple of
+// 4 and at least 12); size, flags: within vxb::check_light's rules (refused here too: the kernel indexes LDS by them); props: the table as the
+// kernel reads it, VX_LIGHT_MAX_PROPS bytes, 4-byte aligned, zeros behind props_count; fields (may be null: records only): 16-byte aligned,
+// box i's bytes at fields + i * field_stride, field_stride a multiple of 16 and at least the voxel count, of which the voxel count rounded up
+// to 16 are written; info (may be null, not both): `count` records, 16-byte aligned. Device-visible memory that overlaps no input.
+hipError_t launch_light_boxes(int svo, hipStream_t stream, const vxd::SceneArgs& sc, const void* lo, uint32_t lo_stride, uint32_t count, const uint32_t size[3],
+                              uint32_t flags, const void* props, uint8_t* fields, uint32_t field_stride, vx_light_info* info);
 
 }  // namespace vxk

@@ -53,13 +53,17 @@ VX_BOX_INVALID = 0xFFFFFFFF
 FLOOD_INFO_DTYPE = np.dtype([("reached", "<u4"), ("farthest", "<u4"), ("faces", "<u4"), ("seed_value", "<u4")])
 VX_FLOOD_MAX_STEPS, VX_FLOOD_NO_POSITION, VX_FLOOD_UNREACHED, VX_FLOOD_BLOCKED = 250, 0xFD, 0xFE, 0xFF
 VX_FLOOD_SEED_ALWAYS, VX_FLOOD_INVALID = 1, 0xFFFFFFFF
+# vx_light_info (vx_light_boxes): what the light of a box amounts to -- the cells whose byte is not 0, the cells that emit, the columns whose top
+# cell is exposed to the sky, the faces of the box on which a cell has a level of 2 or more. A field is one byte a cell: sky << 4 | block
+LIGHT_INFO_DTYPE = np.dtype([("lit", "<u4"), ("sources", "<u4"), ("open_columns", "<u4"), ("faces", "<u4")])
+VX_LIGHT_MAX_SIDE, VX_LIGHT_MAX_PROPS, VX_LIGHT_TRANSPARENT, VX_LIGHT_NO_SKY, VX_LIGHT_NO_BLOCKS, VX_LIGHT_INVALID = 48, 4096, 0x10, 1, 2, 0xFFFFFFFF
 VX_DIR_NEG_X, VX_DIR_POS_X, VX_DIR_NEG_Y, VX_DIR_POS_Y, VX_DIR_NEG_Z, VX_DIR_POS_Z = range(6)
 VX_SCAN_NONE = -0x80000000
 VX_SCAN_TO_EDGE = 0xFFFFFFFF
 FACE_NORMALS = np.array([[-1, 0, 0], [1, 0, 0], [0, -1, 0], [0, 1, 0], [0, 0, -1], [0, 0, 1]], dtype=np.float32)  # by face_id
 assert HIT_DTYPE.itemsize == 48 and PICKER_TASK_DTYPE.itemsize == 48 and PICKER_RESULT_DTYPE.itemsize == 48 and FRAME_DTYPE.itemsize == 36
 assert ENTITY_DTYPE.itemsize == 64 and AABB_RESULT_DTYPE.itemsize == 24 and RAY_HIT_DTYPE.itemsize == 32 and SCAN_HIT_DTYPE.itemsize == 16
-assert BLOCK_AT_DTYPE.itemsize == 8 and BOX_HIT_DTYPE.itemsize == 32 and FLOOD_INFO_DTYPE.itemsize == 16
+assert BLOCK_AT_DTYPE.itemsize == 8 and BOX_HIT_DTYPE.itemsize == 32 and FLOOD_INFO_DTYPE.itemsize == 16 and LIGHT_INFO_DTYPE.itemsize == 16
 
 COUNTER_FIELDS = ["rays", "iterations", "pushes", "leaf_tests", "leaf_tests_trilinear", "boundaries", "csvo_header_bytes", "csvo_pointer_bytes",
                   "pixels", "lit_pixels", "shadow_rays", "wave_steps", "services", "refills", "tail_wave_steps", "tail_iterations"]
@@ -94,6 +98,11 @@ class BoxBatch(C.Structure):
 class FloodShape(C.Structure):
     """vx_flood_shape"""
     _fields_ = [("size", C.c_uint32 * 3), ("seed_at", C.c_uint32 * 3), ("max_steps", C.c_uint32), ("pass_value", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class LightShape(C.Structure):
+    """vx_light_shape"""
+    _fields_ = [("size", C.c_uint32 * 3), ("flags", C.c_uint32), ("props", C.c_void_p), ("props_count", C.c_uint32)]
 
 
 class Result(C.Structure):
@@ -138,6 +147,7 @@ SYMBOLS = {
     "vx_scan_columns": (_int, [_vp, C.POINTER(C.c_int32 * 3), C.POINTER(_u32 * 3), _int, _int, _vp]),
     "vx_overlap_boxes": (_int, [_vp, C.POINTER(BoxBatch), _u32, _int, _vp]),
     "vx_flood_points": (_int, [_vp, _vp, _u32, _u32, C.POINTER(FloodShape), _int, _vp, _u32, _vp]),
+    "vx_light_boxes": (_int, [_vp, _vp, _u32, _u32, C.POINTER(LightShape), _int, _vp, _u32, _vp]),
     "vx_physics_step": (_int, [_vp, _vp, _u32, _int, C.c_float, _u32, _vp]),
     "vx_debug_trace": (_int, [_vp, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.c_float, _int, C.POINTER(Result), _vp, _u32, C.POINTER(_u32)]),
     "vx_sync": (_int, [_vp]),
@@ -330,6 +340,18 @@ def flood_shape(size, seed_at=None, max_steps=VX_FLOOD_MAX_STEPS, pass_value=0, 
     size = [int(v) for v in size]
     seed_at = [v // 2 for v in size] if seed_at is None else [int(v) for v in seed_at]
     return FloodShape((C.c_uint32 * 3)(*size), (C.c_uint32 * 3)(*seed_at), int(max_steps), int(pass_value), int(flags))
+
+
+def light_infos_to_numpy(infos):
+    """A device record tensor of Svo.light_boxes as LIGHT_INFO_DTYPE records (copies to the host: synchronise first)."""
+    return infos.cpu().numpy().view(np.uint8).reshape(-1).view(LIGHT_INFO_DTYPE)
+
+
+def light_shape(size, props, flags=0):
+    """(a vx_light_shape, the array its props pointer points into: keep it until the call has returned). props: uint8, at most 4,096 of them."""
+    table = np.ascontiguousarray(np.asarray(props, dtype=np.uint8).reshape(-1))
+    size = [int(v) for v in size]
+    return LightShape((C.c_uint32 * 3)(*size), int(flags), table.ctypes.data if len(table) else None, len(table)), table
 
 
 def ray_hits_to_numpy(hits):
@@ -935,6 +957,63 @@ class Svo:
             raise TypeError("flood_points: info must be a contiguous CUDA tensor of at least N x 16 bytes")
         _check(lib().vx_flood_points(self._h, _vp(ptr), pos_stride, count, C.byref(shape), VX_MEM_DEVICE, None if fields is None else _vp(fields.data_ptr()),
                                      int(field_stride), None if info is None else _vp(info.data_ptr())))
+        return fields, info
+
+    # -- light levels (two breadth-first searches over get_block, gameplay.rs:161-201, for a batch of boxes) --------------------------------------------
+    def light_boxes(self, lo, size, props, flags=0, fields=None, info=None, field_stride=0):
+        """vx_light_boxes: the sky and block light levels of every cell of the boxes [lo_k, lo_k + size) (1..48 cells an axis). lo: int32 (N, 3),
+        a NumPy array or a torch CUDA tensor, packed or a strided view whose last axis is contiguous (the stride a multiple of 4 bytes, at least
+        12). props: uint8, props[id] = emission | VX_LIGHT_TRANSPARENT, always host memory. Returns (fields, info), either None when not asked for:
+        fields -- uint8 [N, field_stride], of which the first size.x * size.y * size.z bytes of a row are the box's cells, x fastest, sky << 4 |
+        block; field_stride 0: the voxel count rounded up to 16 -- and info -- LIGHT_INFO_DTYPE records. fields and info: None (or True) for fresh
+        memory, False for none, or the memory to write to (unlike flood_points, where None stands for none).
+        Host (a NumPy array): synchronous.
+        Device (a torch CUDA tensor): returns after enqueueing, without synchronising -- pair with sync(); fields is a uint8 tensor and info
+        an int32 tensor of shape (N, 4) on lo's device (light_infos_to_numpy)."""
+        host = isinstance(lo, np.ndarray)
+        if len(lo.shape) != 2 or lo.shape[1] != 3:
+            raise TypeError("light_boxes: lo must have shape (N, 3)")
+        count = int(lo.shape[0])
+        if not host and not getattr(lo, "is_cuda", False):
+            raise TypeError("light_boxes: lo must be a NumPy array or a torch CUDA tensor")
+        shape, table = light_shape(size, props, flags)
+        voxels = int(shape.size[0]) * int(shape.size[1]) * int(shape.size[2])
+        stride = int(field_stride) if field_stride else (voxels + 15) // 16 * 16
+        fields = True if fields is None else (None if fields is False else fields)
+        info = True if info is None else (None if info is False else info)
+        if host:
+            if lo.dtype != np.int32 or (count and (lo.strides[1] != 4 or lo.strides[0] % 4 or lo.strides[0] < 12)):
+                raise TypeError("light_boxes: lo must be int32 rows at a stride that is a multiple of 4 bytes and at least 12")
+            ptr, lo_stride = lo.ctypes.data, int(lo.strides[0]) if count else 12
+            if fields is True:
+                fields = np.zeros((count, stride), dtype=np.uint8)
+            elif fields is not None and (not isinstance(fields, np.ndarray) or fields.dtype != np.uint8 or fields.size < count * stride or not fields.flags.c_contiguous
+                                         or not fields.flags.writeable):
+                raise TypeError("light_boxes: fields must be a writeable C-contiguous uint8 array of at least N x field_stride bytes")
+            if info is True:
+                info = np.zeros(count, dtype=LIGHT_INFO_DTYPE)
+            elif info is not None and (not isinstance(info, np.ndarray) or info.dtype != LIGHT_INFO_DTYPE or info.size != count or not info.flags.c_contiguous
+                                       or not info.flags.writeable):
+                raise TypeError("light_boxes: info must be a writeable C-contiguous array of N hip.LIGHT_INFO_DTYPE records")
+            _check(lib().vx_light_boxes(self._h, _vp(ptr), lo_stride, count, C.byref(shape), VX_MEM_HOST, None if fields is None else fields.ctypes.data_as(_vp),
+                                        int(field_stride), None if info is None else info.ctypes.data_as(_vp)))
+            return fields, info
+        import torch
+
+        if lo.dtype != torch.int32 or (count and (lo.stride(1) != 1 or lo.stride(0) < 3)):
+            raise TypeError("light_boxes: lo must be int32 rows whose last axis is contiguous, at a stride of at least 3 elements")
+        ptr, lo_stride = lo.data_ptr(), 4 * int(lo.stride(0)) if count else 12
+        if fields is True:
+            fields = torch.empty((count, stride), dtype=torch.uint8, device=lo.device)
+        elif fields is not None and (not fields.is_cuda or not fields.is_contiguous() or fields.numel() * fields.element_size() < count * stride):
+            raise TypeError("light_boxes: fields must be a contiguous CUDA tensor of at least N x field_stride bytes")
+        if info is True:
+            info = torch.empty((count, 4), dtype=torch.int32, device=lo.device)
+        elif info is not None and (not info.is_cuda or not info.is_contiguous() or info.numel() * info.element_size() < count * LIGHT_INFO_DTYPE.itemsize):
+            raise TypeError("light_boxes: info must be a contiguous CUDA tensor of at least N x 16 bytes")
+        _check(lib().vx_light_boxes(self._h, _vp(ptr), lo_stride, count, C.byref(shape), VX_MEM_DEVICE, None if fields is None else _vp(fields.data_ptr()),
+                                    int(field_stride), None if info is None else _vp(info.data_ptr())))
+        del table  # (read during the call)
         return fields, info
 
     # -- Physics::step_many (src/systems/physics.rs:122-136), on the device ---------------------------------------

@@ -245,6 +245,33 @@ typedef struct vx_light_info {
                                 light that would go on beyond the box */
 } vx_light_info;
 
+#define VX_WALK_MAX_STEPS   250u
+#define VX_WALK_NO_POSITION 0xFDu   /* every byte of a field whose position is no position */
+#define VX_WALK_UNREACHED   0xFEu   /* standable, not reached within max_steps */
+#define VX_WALK_NO_STAND    0xFFu   /* the agent cannot stand here */
+#define VX_WALK_STOP_AT_GOAL 1u     /* flags: the flood ends after the whole step that reaches the settled goal */
+#define VX_WALK_NONE        0xFFFFFFFFu
+/* What every query of a vx_walk_points call shares; read on the host during the call. */
+typedef struct vx_walk_shape {
+    uint32_t size[3];        /* the box of each query; 1..32 on x and z; size[1] >= 1 and size[1] + height <= 32 */
+    uint32_t seed_at[3];     /* < size: lo = floor(p) - seed_at, as in vx_flood_shape */
+    uint32_t max_steps;      /* 0..VX_WALK_MAX_STEPS */
+    uint32_t pass_value;     /* as vx_flood_shape's: this id passes like air (and, like air, is no floor) */
+    uint32_t height;         /* 1..4 cells of headroom the agent needs */
+    uint32_t climb;          /* 0 or 1: the step up it can take */
+    uint32_t drop;           /* 0..3: the most it steps down */
+    uint32_t path_capacity;  /* 0..252, a multiple of 4: entries of a query's path */
+    uint32_t flags;          /* 0 or VX_WALK_STOP_AT_GOAL */
+} vx_walk_shape;
+/* What a walk reached (vx_walk_points); 32 bytes, two 16-byte stores. */
+typedef struct vx_walk_info {
+    uint32_t reached, farthest, faces, seed_value;   /* as vx_flood_info, over standable cells */
+    uint32_t start_ry;       /* y, inside the box, of the cell the seed settled on; VX_WALK_NONE: it stands nowhere */
+    uint32_t goal_ry;        /* the same for the goal; VX_WALK_NONE: no goal given, no position, outside the box, or it stands nowhere */
+    uint32_t path_steps;     /* step count of the settled goal; VX_WALK_NONE when goal_ry is, or the goal was not reached */
+    uint32_t _pad;           /* written 0 */
+} vx_walk_info;
+
 /* Optional per-pixel record of what trace_ray saw (world.glsl:27-90) -- the "hit position, depth" outputs
  * used for parity checks; not part of the reference's surface. */
 typedef struct vx_hit {
@@ -634,6 +661,55 @@ int vx_flood_points(vx_context* ctx, const void* pos, uint32_t pos_stride, uint3
  * VX_OK (nothing is read or written). Before the first commit: VX_ERR_STATE. */
 int vx_light_boxes(vx_context* ctx, const void* lo, uint32_t lo_stride, uint32_t count, const vx_light_shape* shape, int memory,
                    uint8_t* fields, uint32_t field_stride, vx_light_info* info);
+/* Walking distances and paths for ground agents around each of `count` positions: where vx_flood_points floods through air (a mob that
+ * flies), this call searches the walking graph of the world the device holds -- cells with a floor under them and headroom for the agent,
+ * steps of one block up, drops of a few blocks down -- and traces the path from the position to a goal. The reference would loop get_block
+ * (gameplay.rs:161-201) over the neighbourhood and search on the host. Everything is integer and exact.
+ * Cells. Positions, the box ([lo, lo + size), lo = floor(p) - seed_at modulo 2^32, floor saturated to int32) and the field layout are
+ * vx_flood_points': a byte a cell, x fastest, at fields + k * field_stride; field_stride is 0 (the voxel count rounded up to 16) or a
+ * multiple of 16 and at least the voxel count; the bytes from the voxel count up to its multiple of 16 are written VX_WALK_NO_STAND, bytes
+ * beyond are not touched. A cell is passable when vx_block_points' value there is 0 or equals a non-zero pass_value; outside the world is
+ * air; a LOD voxel blocks each of its fine voxels.
+ * Standable. Cell (x, y, z) is standable when (x, y .. y + height - 1, z) are all passable and (x, y - 1, z) is not. This is judged by the
+ * WORLD, also below the box's bottom layer and above its top: size[1] + height layers are read, one below the box and height - 1 above it
+ * (the up and drop rules reach no higher), so size[1] + height <= 32. Nothing outside the world is a floor. Only cells of the box are
+ * nodes.
+ * Edges run from a standable cell c = (x, y, z) to a standable cell c' = (x', y', z') of a column next to it (x +- 1 or z +- 1, no
+ * diagonals, inside the box), and each costs one step:
+ *   level: y' = y;
+ *   up, with climb == 1: y' = y + 1, and (x, y + height, z) is passable -- the agent rises in its own column first;
+ *   down by d = 1..drop: y' = y - d, and (x', y' + height .. y + height - 1, z') are passable -- the agent moves over at its own level,
+ *   then falls.
+ * Settling. The seed is floor(p). If (x, s.y .. s.y + height - 1, z) are not all passable it stands nowhere. Otherwise it falls while the
+ * cell below is passable and stands on the first standable cell; if it leaves the box's bottom first, it stands nowhere. A seed that
+ * stands nowhere reaches nothing -- {0, 0, 0, seed_value, VX_WALK_NONE, goal_ry, VX_WALK_NONE, 0} -- and its field still tells standable
+ * from not. `goal` may be NULL; otherwise a float[3] is read at goal + k * goal_stride under pos' own stride and alignment rules, a
+ * goal_stride of 0 meaning one goal for all. The goal settles by the same rule, and must lie in the box before and after settling. A NaN
+ * or infinite goal is "no goal" for that query, not an error. A NaN or infinite pos is no position: the field is all VX_WALK_NO_POSITION,
+ * the record {VX_FLOOD_INVALID's value, 0, 0, 0, VX_WALK_NONE, VX_WALK_NONE, VX_WALK_NONE, 0} and the path all VX_WALK_NONE.
+ * The field. Breadth-first step counts over that graph from the settled seed, up to max_steps; VX_WALK_UNREACHED for other standable
+ * cells, VX_WALK_NO_STAND for the rest. The record's reached, farthest, faces and seed_value are vx_flood_info's, over standable cells
+ * (seed_value is the value at floor(p), not where it settled).
+ * VX_WALK_STOP_AT_GOAL: the flood ends after the whole step that reaches the settled goal; the field and the record are exactly those of
+ * max_steps = min(max_steps, path_steps).
+ * Paths. A path is written when goal, paths and path_capacity > 0 are all given: query k's entries are path_capacity uint32 at paths + k *
+ * path_capacity. Entry i is the cell after i + 1 steps, as rx | ry << 8 | rz << 16 (entry 0 is the next cell to move to). The first
+ * min(path_steps, path_capacity) entries are written; the rest, up to the capacity, are VX_WALK_NONE, and with no path every entry is.
+ * The path is found backwards from the goal: from a cell of step k, the first cell of step k - 1 that has an edge to it, searched by the
+ * side it lies on in the order -x, +x, -z, +z, and per side level, then from below (the up edge), then from above by d = 1, 2, 3. That
+ * makes the path unique.
+ * One workgroup of four waves a query, one launch; no workgroup waits for another.
+ * At least one of fields, info and paths is given. Memory kinds, ordering and fences are vx_flood_points'. VX_MEM_HOST: synchronous,
+ * through pinned memory. VX_MEM_DEVICE (fields, paths and info aligned to 16 bytes): enqueued on the context's stream, ordered behind the
+ * commits made so far and earlier batch calls; later commits wait for it; the fence is vx_sync. The outputs must not overlap the inputs or
+ * one another; `shape` itself is read during the call.
+ * VX_ERR_INVALID_ARGUMENT (its message names the field; nothing is written): a null ctx; an unknown memory kind; with count > 0: a null
+ * shape or pos; fields, info and paths all null; paths without goal; vx_block_points' stride and alignment rules for pos, and for goal
+ * with a goal_stride of 0 allowed; a size, seed_at, max_steps, height, climb, drop, path_capacity or flags outside what vx_walk_shape
+ * states; a field_stride that breaks the rule; count > 16777216 (2^24), or count * field_stride or count * path_capacity * 4 above
+ * 16777216 bytes; a misaligned device output. count == 0: VX_OK (nothing is read or written). Before the first commit: VX_ERR_STATE. */
+int vx_walk_points(vx_context* ctx, const void* pos, uint32_t pos_stride, const void* goal, uint32_t goal_stride, uint32_t count,
+                   const vx_walk_shape* shape, int memory, uint8_t* fields, uint32_t field_stride, uint32_t* paths, vx_walk_info* info);
 /* Physics::step_many (src/systems/physics.rs:122-136) `steps` times over `count` entities in ONE kernel launch, against the world as last
  * committed: per step and entity the AABB's fan of axis-parallel picker rays (Aabb::generate_picker_tasks, svo_picker.rs:183-243: max_dst
  * 10), folded into six contact distances (parse_picker_results, svo_picker.rs:245-299), then Physics::update_entity and

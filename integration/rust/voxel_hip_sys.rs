@@ -262,6 +262,49 @@ pub const VX_LIGHT_NO_SKY: u32 = 0x1;
 pub const VX_LIGHT_NO_BLOCKS: u32 = 0x2;
 pub const VX_LIGHT_INVALID: u32 = u32::MAX;
 
+/// What every query of a `vx_walk_points` call shares: the box of each query (1..32 cells on x and z; size[1] + height <= 32), the seed's cell
+/// inside it (lo = floor(p) - seed_at), the step limit (0..=VX_WALK_MAX_STEPS), a block id that passes like air (0: none), the agent's height
+/// (1..=4 cells of headroom), the step up it can take (0 or 1), the most it steps down (0..=3), the entries of a query's path (0..=252, a
+/// multiple of 4), and 0 or VX_WALK_STOP_AT_GOAL.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct vx_walk_shape {
+    pub size: [u32; 3],
+    pub seed_at: [u32; 3],
+    pub max_steps: u32,
+    pub pass_value: u32,
+    pub height: u32,
+    pub climb: u32,
+    pub drop: u32,
+    pub path_capacity: u32,
+    pub flags: u32,
+}
+/// What a walk reached (`vx_walk_points`): `reached`, `farthest`, `faces` and `seed_value` as `vx_flood_info`'s, over standable cells; the y
+/// inside the box of the cells the seed and the goal settled on (`VX_WALK_NONE`: it stands nowhere; for the goal also: none given, outside the
+/// box); the goal's step count (`VX_WALK_NONE`: not reached); `_pad` is written 0.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct vx_walk_info {
+    pub reached: u32,
+    pub farthest: u32,
+    pub faces: u32,
+    pub seed_value: u32,
+    pub start_ry: u32,
+    pub goal_ry: u32,
+    pub path_steps: u32,
+    pub _pad: u32,
+}
+/// the header's VX_WALK_* (written in hexadecimal there and here)
+pub const VX_WALK_MAX_STEPS: u32 = 0xFA;
+/// a field's bytes that are no step count: of a position that is no position; standable but not reached; not standable
+pub const VX_WALK_NO_POSITION: u8 = 0xFD;
+pub const VX_WALK_UNREACHED: u8 = 0xFE;
+pub const VX_WALK_NO_STAND: u8 = 0xFF;
+/// `vx_walk_shape::flags`: the flood ends after the whole step that reaches the settled goal
+pub const VX_WALK_STOP_AT_GOAL: u32 = 0x1;
+/// no cell, no step count: `vx_walk_info::start_ry`, `goal_ry`, `path_steps`, and a path's entries beyond its end
+pub const VX_WALK_NONE: u32 = u32::MAX;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct vx_stats {
@@ -297,6 +340,8 @@ const _: () = assert!(std::mem::size_of::<vx_flood_shape>() == 36);
 const _: () = assert!(std::mem::size_of::<vx_flood_info>() == 16);
 const _: () = assert!(std::mem::size_of::<vx_light_shape>() == 32);
 const _: () = assert!(std::mem::size_of::<vx_light_info>() == 16);
+const _: () = assert!(std::mem::size_of::<vx_walk_shape>() == 52);
+const _: () = assert!(std::mem::size_of::<vx_walk_info>() == 32);
 const _: () = assert!(std::mem::size_of::<MaterialInstance>() == 32); // svo_registry.rs:29-40 is #[repr(C)]
 const _: () = assert!(std::mem::size_of::<PickerTask>() == 48 && std::mem::size_of::<PickerResult>() == 48); // svo_picker.rs:13-32
 
@@ -361,6 +406,14 @@ extern "C" {
     /// at info[k]; either output may be null, not both; `memory`: VX_MEM_HOST / VX_MEM_DEVICE (both aligned to 16); props is host memory
     pub fn vx_light_boxes(ctx: *mut vx_context, lo: *const c_void, lo_stride: u32, count: u32, shape: *const vx_light_shape, memory: c_int,
                           fields: *mut u8, field_stride: u32, info: *mut vx_light_info) -> c_int;
+    /// walking distances and paths for ground agents around each of `count` positions (read as `vx_block_points` reads them; `goal`: null, or a
+    /// float[3] at goal + k * goal_stride, a goal_stride of 0 meaning one goal for all): breadth-first step counts over the walking graph of the
+    /// box `shape` describes -- a floor below, `height` cells of headroom, one block up, `drop` down; query k's field -- a byte a cell, x fastest --
+    /// at fields + k * field_stride (a multiple of 16, 0 = the voxel count rounded up to 16), its path -- `path_capacity` cells as rx | ry << 8 |
+    /// rz << 16, VX_WALK_NONE beyond its end -- at paths + k * path_capacity, its record at info[k]; any output may be null, not all; `memory`:
+    /// VX_MEM_HOST / VX_MEM_DEVICE (all three aligned to 16)
+    pub fn vx_walk_points(ctx: *mut vx_context, pos: *const c_void, pos_stride: u32, goal: *const c_void, goal_stride: u32, count: u32,
+                          shape: *const vx_walk_shape, memory: c_int, fields: *mut u8, field_stride: u32, paths: *mut u32, info: *mut vx_walk_info) -> c_int;
     /// Physics::step_many (physics.rs:122-136) `steps` times for `count` entities in one launch; `memory`: VX_MEM_HOST / VX_MEM_DEVICE
     pub fn vx_physics_step(ctx: *mut vx_context, entities: *mut vx_entity, count: u32, memory: c_int, delta_time: f32, steps: u32,
                            contacts: *mut vx_aabb_result) -> c_int;

@@ -1,9 +1,10 @@
 // libvoxelhip.so, block ids read from the device: vx_block_points and vx_read_region, the first block along an axis: vx_scan_points and
 // vx_scan_columns, the blocks of a box as a list: vx_list_region, what a batch of float boxes holds: vx_overlap_boxes, step distances
-// through air around a batch of positions: vx_flood_points, and the light levels of a batch of boxes: vx_light_boxes (include/voxel_hip.h)
-// -- argument checks (vx_blocks.hpp's, vx_scan.hpp's, vx_list.hpp's, vx_boxes.hpp's, vx_flood.hpp's and vx_light.hpp's rules), the pinned
-// scratch the host-memory calls read and write through (csrc/vx_pinned_pool.hpp), and the launches of kernels_blocks.hip, kernels_scan.hip,
-// kernels_list.hip, kernels_boxes.hip, kernels_flood.hip and kernels_light.hip.
+// through air around a batch of positions: vx_flood_points, the light levels of a batch of boxes: vx_light_boxes, and walking distances and
+// paths for ground agents: vx_walk_points (include/voxel_hip.h)
+// -- argument checks (vx_blocks.hpp's, vx_scan.hpp's, vx_list.hpp's, vx_boxes.hpp's, vx_flood.hpp's, vx_light.hpp's and vx_walk.hpp's rules),
+// the pinned scratch the host-memory calls read and write through (csrc/vx_pinned_pool.hpp), and the launches of kernels_blocks.hip,
+// kernels_scan.hip, kernels_list.hip, kernels_boxes.hip, kernels_flood.hip, kernels_light.hip and kernels_walk.hip.
 // A further translation unit on the context, like raycast_runtime.cpp: what it needs of the context is vx_context.hpp's (runtime.cpp).
 #include <cstring>
 #include <map>
@@ -413,6 +414,55 @@ int vx_light_boxes(vx_context* ctx, const void* lo, uint32_t lo_stride, uint32_t
                                     fields ? pool.dev + at_fields : nullptr, packed, info ? reinterpret_cast<vx_light_info*>(pool.dev + at_info) : nullptr));
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // synchronous, like vx_flood_points' host-memory call
     if (info) std::memcpy(info, pool.host + at_info, info_bytes);
+    if (fields && stride == packed) std::memcpy(fields, pool.host + at_fields, field_bytes);
+    else if (fields) for (size_t i = 0; i < count; ++i) std::memcpy(fields + i * stride, pool.host + at_fields + i * packed, packed);
+    return VX_OK;
+}
+
+int vx_walk_points(vx_context* ctx, const void* pos, uint32_t pos_stride, const void* goal, uint32_t goal_stride, uint32_t count, const vx_walk_shape* shape, int memory,
+                   uint8_t* fields, uint32_t field_stride, uint32_t* paths, vx_walk_info* info) {
+    static_assert(sizeof(vx_walk_info) == 32 && sizeof(vx_walk_shape) == 52, "the ABI's record sizes");
+    if (memory != VX_MEM_HOST && memory != VX_MEM_DEVICE) return fail(VX_ERR_INVALID_ARGUMENT, "walk_points: memory is neither VX_MEM_HOST nor VX_MEM_DEVICE");
+    if (const char* what = vxb::check_walk(pos, pos_stride, goal, goal_stride, count, shape, fields, field_stride, paths, info))
+        return fail(VX_ERR_INVALID_ARGUMENT, std::string("walk_points: ") + what);
+    if (count && memory == VX_MEM_DEVICE && reinterpret_cast<uintptr_t>(fields) % 16) return fail(VX_ERR_INVALID_ARGUMENT, "walk_points: fields in device memory must be aligned to 16 bytes");
+    if (count && memory == VX_MEM_DEVICE && reinterpret_cast<uintptr_t>(paths) % 16) return fail(VX_ERR_INVALID_ARGUMENT, "walk_points: paths in device memory must be aligned to 16 bytes");
+    if (count && memory == VX_MEM_DEVICE && reinterpret_cast<uintptr_t>(info) % 16) return fail(VX_ERR_INVALID_ARGUMENT, "walk_points: info in device memory must be aligned to 16 bytes");
+    if (!ctx) return fail(VX_ERR_INVALID_ARGUMENT, "null context");
+    if (int rc = vxrt::check_ready(ctx)) return rc;
+    VX_LOCK(ctx);
+    if (count == 0) return VX_OK;
+    const uint32_t voxels = vxb::walk_voxels(*shape), packed = vxb::flood_round16(voxels);
+    const uint32_t stride = field_stride ? field_stride : packed;
+    if (!shape->path_capacity) paths = nullptr;  // (no entry to write)
+    if (!fields && !info && !paths) return VX_OK;  // (paths alone, of no entries: nothing is written)
+
+    if (memory == VX_MEM_DEVICE) {
+        HIP_TRY(vxk::launch_walk_points(kernel_variant(ctx), ctx->stream, vxrt::scene_on_bytes(ctx), pos, pos_stride, goal, goal_stride, count, *shape, fields, stride, paths, info));
+        return vxrt::mark_world_read(ctx);
+    }
+
+    // the positions packed at stride 12 | the goals packed at stride 12, or the one goal | the records | the paths | the fields, each the
+    // voxel count rounded up to 16: the bytes a query writes, which go to the caller's stride from there (every part at a multiple of 16)
+    const size_t goals = goal ? (goal_stride ? size_t(count) : 1u) : 0u;
+    const size_t at_goal = round16(size_t(count) * 12), at_info = at_goal + round16(goals * 12), info_bytes = info ? size_t(count) * sizeof(vx_walk_info) : 0;
+    const size_t at_paths = at_info + info_bytes, path_bytes = paths ? size_t(count) * shape->path_capacity * 4u : 0;
+    const size_t at_fields = at_paths + path_bytes, field_bytes = fields ? size_t(count) * packed : 0;
+    vxrt::PinnedPool& pool = vxrt::pinned_pool_of(ctx->device);
+    std::lock_guard<std::mutex> pool_lock(pool.mutex);
+    if (int rc = vxrt::pinned_pool_reserve(pool, at_fields + field_bytes)) return rc;
+    const uint8_t* from = static_cast<const uint8_t*>(pos);
+    if (pos_stride == 12) std::memcpy(pool.host, from, size_t(count) * 12);
+    else for (size_t i = 0; i < count; ++i) std::memcpy(pool.host + 12 * i, from + size_t(pos_stride) * i, 12);
+    from = static_cast<const uint8_t*>(goal);
+    if (goals && (goal_stride == 12 || goal_stride == 0)) std::memcpy(pool.host + at_goal, from, goals * 12);
+    else for (size_t i = 0; i < goals; ++i) std::memcpy(pool.host + at_goal + 12 * i, from + size_t(goal_stride) * i, 12);
+    HIP_TRY(vxk::launch_walk_points(kernel_variant(ctx), ctx->stream, vxrt::scene_on_bytes(ctx), pool.dev, 12, goal ? pool.dev + at_goal : nullptr, goal_stride ? 12u : 0u, count,
+                                    *shape, fields ? pool.dev + at_fields : nullptr, packed, paths ? reinterpret_cast<uint32_t*>(pool.dev + at_paths) : nullptr,
+                                    info ? reinterpret_cast<vx_walk_info*>(pool.dev + at_info) : nullptr));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // synchronous, like vx_flood_points' host-memory call
+    if (info) std::memcpy(info, pool.host + at_info, info_bytes);
+    if (paths) std::memcpy(paths, pool.host + at_paths, path_bytes);
     if (fields && stride == packed) std::memcpy(fields, pool.host + at_fields, field_bytes);
     else if (fields) for (size_t i = 0; i < count; ++i) std::memcpy(fields + i * stride, pool.host + at_fields + i * packed, packed);
     return VX_OK;

@@ -1,6 +1,6 @@
 // What blocks_runtime.cpp knows of the block lookup kernels (kernels_blocks.hip), of the scans along an axis (kernels_scan.hip) and of the
 // list of a box's blocks (kernels_list.hip), of what a batch of float boxes holds (kernels_boxes.hip), of the floods around a batch of positions
-// (kernels_flood.hip) and of the light levels of a batch of boxes (kernels_light.hip).
+// (kernels_flood.hip), of the light levels of a batch of boxes (kernels_light.hip) and of the walks of ground agents (kernels_walk.hip).
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -12,6 +12,7 @@
 #include "vx_light.hpp"
 #include "vx_list.hpp"
 #include "vx_scan.hpp"
+#include "vx_walk.hpp"
 
 namespace vxk {
 
@@ -65,5 +66,13 @@ hipError_t launch_flood_points(int svo, hipStream_t stream, const vxd::SceneArgs
 // to 16 are written; info (may be null, not both): `count` records, 16-byte aligned. Device-visible memory that overlaps no input.
 hipError_t launch_light_boxes(int svo, hipStream_t stream, const vxd::SceneArgs& sc, const void* lo, uint32_t lo_stride, uint32_t count, const uint32_t size[3],
                               uint32_t flags, const void* props, uint8_t* fields, uint32_t field_stride, vx_light_info* info);
+
+// `count` (1..2^24) workgroups of 256 threads, one query a workgroup: positions as launch_flood_points reads them; goal (may be null: no goal):
+// a float[3] at goal + i * goal_stride, goal_stride 0: one for all; shape: within vxb::check_walk's rules (refused here too: the kernel
+// indexes LDS by it); fields as launch_flood_points'; paths (may be null; ignored without a goal or with path_capacity == 0): 16-byte
+// aligned, query i's shape.path_capacity entries at paths + i * shape.path_capacity; info (may be null, not all three): `count` records of 32
+// bytes, 16-byte aligned. Device-visible memory that overlaps no input.
+hipError_t launch_walk_points(int svo, hipStream_t stream, const vxd::SceneArgs& sc, const void* pos, uint32_t pos_stride, const void* goal, uint32_t goal_stride,
+                              uint32_t count, const vx_walk_shape& shape, uint8_t* fields, uint32_t field_stride, uint32_t* paths, vx_walk_info* info);
 
 }  // namespace vxk

@@ -57,6 +57,13 @@ VX_FLOOD_SEED_ALWAYS, VX_FLOOD_INVALID = 1, 0xFFFFFFFF
 # cell is exposed to the sky, the faces of the box on which a cell has a level of 2 or more. A field is one byte a cell: sky << 4 | block
 LIGHT_INFO_DTYPE = np.dtype([("lit", "<u4"), ("sources", "<u4"), ("open_columns", "<u4"), ("faces", "<u4")])
 VX_LIGHT_MAX_SIDE, VX_LIGHT_MAX_PROPS, VX_LIGHT_TRANSPARENT, VX_LIGHT_NO_SKY, VX_LIGHT_NO_BLOCKS, VX_LIGHT_INVALID = 48, 4096, 0x10, 1, 2, 0xFFFFFFFF
+# vx_walk_info (vx_walk_points): what a walk reached -- reached, farthest, faces and seed_value as FLOOD_INFO_DTYPE's over standable cells, the y inside
+# the box on which the seed and the goal came to stand, and the goal's step count (VX_WALK_NONE: none). A field is one byte a cell: the step
+# count, or one of VX_WALK_NO_POSITION, VX_WALK_UNREACHED, VX_WALK_NO_STAND; a path entry is rx | ry << 8 | rz << 16, or VX_WALK_NONE
+WALK_INFO_DTYPE = np.dtype([("reached", "<u4"), ("farthest", "<u4"), ("faces", "<u4"), ("seed_value", "<u4"), ("start_ry", "<u4"), ("goal_ry", "<u4"),
+                            ("path_steps", "<u4"), ("_pad", "<u4")])
+VX_WALK_MAX_STEPS, VX_WALK_NO_POSITION, VX_WALK_UNREACHED, VX_WALK_NO_STAND = 250, 0xFD, 0xFE, 0xFF
+VX_WALK_STOP_AT_GOAL, VX_WALK_NONE = 1, 0xFFFFFFFF
 VX_DIR_NEG_X, VX_DIR_POS_X, VX_DIR_NEG_Y, VX_DIR_POS_Y, VX_DIR_NEG_Z, VX_DIR_POS_Z = range(6)
 VX_SCAN_NONE = -0x80000000
 VX_SCAN_TO_EDGE = 0xFFFFFFFF
@@ -64,6 +71,7 @@ FACE_NORMALS = np.array([[-1, 0, 0], [1, 0, 0], [0, -1, 0], [0, 1, 0], [0, 0, -1
 assert HIT_DTYPE.itemsize == 48 and PICKER_TASK_DTYPE.itemsize == 48 and PICKER_RESULT_DTYPE.itemsize == 48 and FRAME_DTYPE.itemsize == 36
 assert ENTITY_DTYPE.itemsize == 64 and AABB_RESULT_DTYPE.itemsize == 24 and RAY_HIT_DTYPE.itemsize == 32 and SCAN_HIT_DTYPE.itemsize == 16
 assert BLOCK_AT_DTYPE.itemsize == 8 and BOX_HIT_DTYPE.itemsize == 32 and FLOOD_INFO_DTYPE.itemsize == 16 and LIGHT_INFO_DTYPE.itemsize == 16
+assert WALK_INFO_DTYPE.itemsize == 32
 
 COUNTER_FIELDS = ["rays", "iterations", "pushes", "leaf_tests", "leaf_tests_trilinear", "boundaries", "csvo_header_bytes", "csvo_pointer_bytes",
                   "pixels", "lit_pixels", "shadow_rays", "wave_steps", "services", "refills", "tail_wave_steps", "tail_iterations"]
@@ -98,6 +106,12 @@ class BoxBatch(C.Structure):
 class FloodShape(C.Structure):
     """vx_flood_shape"""
     _fields_ = [("size", C.c_uint32 * 3), ("seed_at", C.c_uint32 * 3), ("max_steps", C.c_uint32), ("pass_value", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class WalkShape(C.Structure):
+    """vx_walk_shape"""
+    _fields_ = [("size", C.c_uint32 * 3), ("seed_at", C.c_uint32 * 3), ("max_steps", C.c_uint32), ("pass_value", C.c_uint32), ("height", C.c_uint32),
+                ("climb", C.c_uint32), ("drop", C.c_uint32), ("path_capacity", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class LightShape(C.Structure):
@@ -148,6 +162,7 @@ SYMBOLS = {
     "vx_overlap_boxes": (_int, [_vp, C.POINTER(BoxBatch), _u32, _int, _vp]),
     "vx_flood_points": (_int, [_vp, _vp, _u32, _u32, C.POINTER(FloodShape), _int, _vp, _u32, _vp]),
     "vx_light_boxes": (_int, [_vp, _vp, _u32, _u32, C.POINTER(LightShape), _int, _vp, _u32, _vp]),
+    "vx_walk_points": (_int, [_vp, _vp, _u32, _vp, _u32, _u32, C.POINTER(WalkShape), _int, _vp, _u32, _vp, _vp]),
     "vx_physics_step": (_int, [_vp, _vp, _u32, _int, C.c_float, _u32, _vp]),
     "vx_debug_trace": (_int, [_vp, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.c_float, _int, C.POINTER(Result), _vp, _u32, C.POINTER(_u32)]),
     "vx_sync": (_int, [_vp]),
@@ -340,6 +355,18 @@ def flood_shape(size, seed_at=None, max_steps=VX_FLOOD_MAX_STEPS, pass_value=0, 
     size = [int(v) for v in size]
     seed_at = [v // 2 for v in size] if seed_at is None else [int(v) for v in seed_at]
     return FloodShape((C.c_uint32 * 3)(*size), (C.c_uint32 * 3)(*seed_at), int(max_steps), int(pass_value), int(flags))
+
+
+def walk_infos_to_numpy(infos):
+    """A device record tensor of Svo.walk_points as WALK_INFO_DTYPE records (copies to the host: synchronise first)."""
+    return infos.cpu().numpy().view(np.uint8).reshape(-1).view(WALK_INFO_DTYPE)
+
+
+def walk_shape(size, seed_at=None, max_steps=VX_WALK_MAX_STEPS, pass_value=0, height=2, climb=1, drop=3, path_capacity=0, flags=0):
+    """A vx_walk_shape; seed_at None: the box's centre cell, size // 2."""
+    size = [int(v) for v in size]
+    seed_at = [v // 2 for v in size] if seed_at is None else [int(v) for v in seed_at]
+    return WalkShape((C.c_uint32 * 3)(*size), (C.c_uint32 * 3)(*seed_at), int(max_steps), int(pass_value), int(height), int(climb), int(drop), int(path_capacity), int(flags))
 
 
 def light_infos_to_numpy(infos):
@@ -1015,6 +1042,77 @@ class Svo:
                                     int(field_stride), None if info is None else _vp(info.data_ptr())))
         del table  # (read during the call)
         return fields, info
+
+    # -- walking distances and paths (a search over get_block, gameplay.rs:161-201, on the walking graph, for a batch) --------------------------------
+    def walk_points(self, positions, size, goals=None, seed_at=None, max_steps=VX_WALK_MAX_STEPS, pass_value=0, height=2, climb=1, drop=3, path_capacity=0, flags=0,
+                    fields=True, info=True, paths=None, field_stride=0):
+        """vx_walk_points: breadth-first step counts over the walking graph (a floor below, `height` cells of headroom, one block up with climb,
+        up to `drop` down) of the box of `size` cells around each position, and the path to each goal. positions: as flood_points takes them.
+        goals: None, float32 (N, 3) at any row stride, or (3,): one goal for all; on the positions' side (host or device). Returns (fields,
+        info, paths), each None when not asked for: fields -- uint8 [N, field_stride] as flood_points' (the step count, or VX_WALK_NO_POSITION,
+        VX_WALK_UNREACHED, VX_WALK_NO_STAND) --, info -- WALK_INFO_DTYPE records --, paths -- uint32 [N, path_capacity], entry i the cell after
+        i + 1 steps as rx | ry << 8 | rz << 16, VX_WALK_NONE beyond the path. fields, info, paths: True for fresh memory, False or None for none,
+        or the memory to write to; paths None: fresh memory when goals are given and path_capacity > 0.
+        Host (a NumPy array): synchronous.
+        Device (a torch CUDA tensor): returns after enqueueing, without synchronising -- pair with sync(); fields is a uint8 tensor, info an
+        int32 tensor of shape (N, 8) (walk_infos_to_numpy) and paths an int32 tensor of shape (N, path_capacity) on the positions' device."""
+        host = isinstance(positions, np.ndarray)
+        if len(positions.shape) != 2 or positions.shape[1] != 3:
+            raise TypeError("walk_points: positions must have shape (N, 3)")
+        count = int(positions.shape[0])
+        if not host and not getattr(positions, "is_cuda", False):
+            raise TypeError("walk_points: positions must be a NumPy array or a torch CUDA tensor")
+        if goals is not None and isinstance(goals, np.ndarray) != host:
+            raise TypeError("walk_points: goals must lie where the positions lie")
+        shape = walk_shape(size, seed_at, max_steps, pass_value, height, climb, drop, path_capacity, flags)
+        voxels = int(shape.size[0]) * int(shape.size[1]) * int(shape.size[2])
+        stride = int(field_stride) if field_stride else (voxels + 15) // 16 * 16
+        ptr, pos_stride = _ray_vectors("positions", positions, count, 3)
+        goal_ptr, goal_stride = (None, 0) if goals is None else _ray_vectors("goals", goals, count, 3)
+        fields = None if fields is False else fields
+        info = None if info is False else info
+        if paths is None:
+            paths = goals is not None and int(path_capacity) > 0
+        paths = None if paths is False else paths
+        cap = int(path_capacity)
+        if host:
+            if fields is True:
+                fields = np.zeros((count, stride), dtype=np.uint8)
+            elif fields is not None and (not isinstance(fields, np.ndarray) or fields.dtype != np.uint8 or fields.size < count * stride or not fields.flags.c_contiguous
+                                         or not fields.flags.writeable):
+                raise TypeError("walk_points: fields must be a writeable C-contiguous uint8 array of at least N x field_stride bytes")
+            if info is True:
+                info = np.zeros(count, dtype=WALK_INFO_DTYPE)
+            elif info is not None and (not isinstance(info, np.ndarray) or info.dtype != WALK_INFO_DTYPE or info.size != count or not info.flags.c_contiguous
+                                       or not info.flags.writeable):
+                raise TypeError("walk_points: info must be a writeable C-contiguous array of N hip.WALK_INFO_DTYPE records")
+            if paths is True:
+                paths = np.zeros((count, cap), dtype=np.uint32)
+            elif paths is not None and (not isinstance(paths, np.ndarray) or paths.dtype != np.uint32 or paths.size < count * cap or not paths.flags.c_contiguous
+                                        or not paths.flags.writeable):
+                raise TypeError("walk_points: paths must be a writeable C-contiguous uint32 array of at least N x path_capacity entries")
+            _check(lib().vx_walk_points(self._h, _vp(ptr), pos_stride, None if goal_ptr is None else _vp(goal_ptr), goal_stride, count, C.byref(shape), VX_MEM_HOST,
+                                        None if fields is None else fields.ctypes.data_as(_vp), int(field_stride), None if paths is None else paths.ctypes.data_as(_vp),
+                                        None if info is None else info.ctypes.data_as(_vp)))
+            return fields, info, paths
+        import torch
+
+        if fields is True:
+            fields = torch.empty((count, stride), dtype=torch.uint8, device=positions.device)
+        elif fields is not None and (not fields.is_cuda or not fields.is_contiguous() or fields.numel() * fields.element_size() < count * stride):
+            raise TypeError("walk_points: fields must be a contiguous CUDA tensor of at least N x field_stride bytes")
+        if info is True:
+            info = torch.empty((count, 8), dtype=torch.int32, device=positions.device)
+        elif info is not None and (not info.is_cuda or not info.is_contiguous() or info.numel() * info.element_size() < count * WALK_INFO_DTYPE.itemsize):
+            raise TypeError("walk_points: info must be a contiguous CUDA tensor of at least N x 32 bytes")
+        if paths is True:
+            paths = torch.empty((count, cap), dtype=torch.int32, device=positions.device)
+        elif paths is not None and (not paths.is_cuda or not paths.is_contiguous() or paths.numel() * paths.element_size() < count * cap * 4):
+            raise TypeError("walk_points: paths must be a contiguous CUDA tensor of at least N x path_capacity x 4 bytes")
+        _check(lib().vx_walk_points(self._h, _vp(ptr), pos_stride, None if goal_ptr is None else _vp(goal_ptr), goal_stride, count, C.byref(shape), VX_MEM_DEVICE,
+                                    None if fields is None else _vp(fields.data_ptr()), int(field_stride), None if paths is None else _vp(paths.data_ptr()),
+                                    None if info is None else _vp(info.data_ptr())))
+        return fields, info, paths
 
     # -- Physics::step_many (src/systems/physics.rs:122-136), on the device ---------------------------------------
     def physics_step(self, entities, dt, steps=1, want_contacts=False, count=None, contacts=None):

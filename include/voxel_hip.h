@@ -199,6 +199,26 @@ typedef struct vx_box_hit {
     int32_t hi[3];
 } vx_box_hit;
 
+#define VX_MOVE_INVALID   0xFFFFFFFFu
+#define VX_MOVE_MAX_TRAVEL 64.0f
+#define VX_MOVE_ORDER_YXZ 0x21u   /* axis of pass 0 | pass 1 << 2 | pass 2 << 4: y, then x, then z */
+/* What every box of a vx_move_boxes call shares; read on the host during the call. */
+typedef struct vx_move_shape {
+    float scale;      /* displacement = motion * scale, one fp32 multiply a component (vx_entity.velocity in place, scale = delta_time) */
+    float skin;       /* finite, 0 <= skin <= 1: the gap a stopped box keeps from the block that stopped it */
+    uint32_t order;   /* a permutation of the axes 0, 1, 2 in bits 0..1, 2..3, 4..5; every other bit 0 */
+    uint32_t flags;   /* 0 */
+} vx_move_shape;
+/* How far a box got (vx_move_boxes); 48 bytes. */
+typedef struct vx_move_hit {
+    float origin[3];    /* the box's origin after the move */
+    float moved[3];     /* what was added to it, per axis */
+    uint32_t contacts;  /* bit 2a + (d_a > 0): a block was found ahead of that side of the box within the scan's range (numbered like
+                           face_id); VX_MOVE_INVALID: the record described no box, or no motion */
+    uint32_t value[3];  /* per axis the BlockId of the stopping voxel, 0 = none */
+    uint32_t _pad[2];   /* written 0 */
+} vx_move_hit;
+
 #define VX_FLOOD_MAX_STEPS   250u
 #define VX_FLOOD_NO_POSITION 0xFDu   /* every byte of a field whose position is no position */
 #define VX_FLOOD_UNREACHED   0xFEu   /* passable, not reached within max_steps */
@@ -595,6 +615,37 @@ int vx_scan_columns(vx_context* ctx, const int32_t lo[3], const uint32_t size[3]
  * out, origin or extents; a stride or an alignment that breaks vx_box_batch's rules; count > 16777216 (2^24); a misaligned device out.
  * count == 0: VX_OK (nothing is read or written). Before the first commit: VX_ERR_STATE. */
 int vx_overlap_boxes(vx_context* ctx, const vx_box_batch* boxes, uint32_t count, int memory, vx_box_hit* out);
+/* Each of `count` boxes (vx_box_batch, read as vx_overlap_boxes reads it, only_value included) moved by its motion through the world the
+ * device holds and stopped by blocks: how far it gets, and what stopped it. Unlike the picker fan behind vx_physics_step (rays a voxel apart,
+ * 10 long, all three axes clamped from the start position) every voxel ahead of the box's face counts, and the move goes axis by axis, each
+ * axis judged from where the earlier ones left the box. One launch, one wave a box.
+ * Motion: a float[3] at motion + i * motion_stride (a multiple of 4 and >= 12, or 0 = one motion for every box), 4-byte aligned, in the
+ * memory kind of the call; the displacement is d = motion * shape->scale, one fp32 multiply a component.
+ * Invalid records: a record that is no box (vx_overlap_boxes' rule), a motion with a non-finite component, or a displacement with a
+ * non-finite component or one above VX_MOVE_MAX_TRAVEL in magnitude gives contacts = VX_MOVE_INVALID and every other word 0; the call does
+ * not fail for it.
+ * The rule. The passes run in the order shape->order gives; the pass of axis a uses the box as the earlier passes left it and ends with
+ * origin[a] = origin[a] + m, mn[a] = origin[a] + offset[a], mx[a] = mn[a] + extents[a], one fp32 add each: what a later vx_overlap_boxes of
+ * the new origin computes. d == 0 (or -0): m = 0, no scan, no contact bit, value[a] = 0. Else the cross-section is the cover (floor(mn) ..
+ * ceil(mx) - 1, cut to the world) on the two other axes; an empty one finds nothing. The layers ahead, cut to [0, 2^depth) in float before
+ * the conversion:
+ *   d > 0: end = mx[a] + (d + skin); v in ceil(mx[a]) .. ceil(end) - 1; the nearest layer is the smallest v that holds a counted voxel within
+ *          the cross-section; gap = float(v) - mx[a]; m = min(d, max(0, gap - skin)).
+ *   d < 0: end = mn[a] + (d - skin); v in floor(end) .. floor(mn[a]) - 1; the nearest is the largest v; gap = mn[a] - float(v + 1);
+ *          m = -min(-d, max(0, gap - skin)).
+ * Voxels the box already overlaps along a lie behind its leading face and are never obstacles: a stuck box can move out. A face exactly on
+ * an integer plane has that plane's layer ahead of it at gap 0. A voxel counts as in vx_overlap_boxes (its value is not 0, or equals
+ * only_value; a LOD voxel once for each of its fine voxels; outside the world is air). Nothing found: m = d, no bit, value 0. Something
+ * found: the contact bit is set, even when m == d, and value[a] is the first counted voxel of the nearest layer within the cross-section in
+ * vx_read_region's order (z, then y, then x ascending).
+ * Memory kinds, ordering and fences are vx_overlap_boxes': VX_MEM_HOST is synchronous through pinned memory; VX_MEM_DEVICE (out aligned to
+ * 16 bytes) is enqueued on the context's stream behind commits and earlier batch calls. out overlaps no input: the origins are not written
+ * back in place.
+ * VX_ERR_INVALID_ARGUMENT (its message names the field; nothing is written): vx_overlap_boxes' list; a null shape; a null motion with
+ * count > 0; a motion stride or alignment that breaks the rule; a non-finite scale; a skin outside [0, 1] or NaN; an order that is no
+ * permutation or has other bits set; flags != 0. count == 0: VX_OK. Before the first commit: VX_ERR_STATE. */
+int vx_move_boxes(vx_context* ctx, const vx_box_batch* boxes, const void* motion, uint32_t motion_stride, uint32_t count,
+                  const vx_move_shape* shape, int memory, vx_move_hit* out);
 /* Step distances through air around each of `count` positions: a breadth-first flood of a small box, asked of the world the device holds --
  * which cells a mob can reach and in how many steps (a flow field to walk down), how far a lamp's light gets around corners, whether a room
  * is sealed or the flood leaks out of the box, how big a cave is. The reference would loop get_block (gameplay.rs:161-201) over the

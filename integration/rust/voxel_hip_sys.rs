@@ -198,6 +198,34 @@ pub struct vx_box_hit {
 /// `vx_box_hit::blocks` of a record that described no box (the header's VX_BOX_INVALID)
 pub const VX_BOX_INVALID: u32 = u32::MAX;
 
+/// What every box of a `vx_move_boxes` call shares: displacement = motion * scale (one fp32 multiply a component), the gap a stopped box
+/// keeps from the block that stopped it (0..=1), the order of the passes (a permutation of the axes in bits 0..1, 2..3, 4..5), and 0.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct vx_move_shape {
+    pub scale: f32,
+    pub skin: f32,
+    pub order: u32,
+    pub flags: u32,
+}
+/// How far a box got (`vx_move_boxes`): its origin after the move, what was added to it per axis, the sides on which a block lay ahead (bit
+/// 2a + (d_a > 0), numbered like face_id; `VX_MOVE_INVALID`: no box, or no motion), per axis the stopping voxel's block id; `_pad` is written 0.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct vx_move_hit {
+    pub origin: [f32; 3],
+    pub moved: [f32; 3],
+    pub contacts: u32,
+    pub value: [u32; 3],
+    pub _pad: [u32; 2],
+}
+/// `vx_move_hit::contacts` of a record that described no box or no motion (the header's VX_MOVE_INVALID)
+pub const VX_MOVE_INVALID: u32 = u32::MAX;
+/// the largest displacement along an axis (the header's VX_MOVE_MAX_TRAVEL)
+pub const VX_MOVE_MAX_TRAVEL: f32 = 64.0;
+/// `vx_move_shape::order`: y, then x, then z (the header's VX_MOVE_ORDER_YXZ)
+pub const VX_MOVE_ORDER_YXZ: u32 = 0x21;
+
 /// What every query of a `vx_flood_points` call shares: the box of each query (1..32 cells an axis), the seed's cell inside it (lo =
 /// floor(p) - seed_at), the step limit (0..=VX_FLOOD_MAX_STEPS), a block id that passes like air (0: none), and 0 or VX_FLOOD_SEED_ALWAYS.
 #[repr(C)]
@@ -336,6 +364,8 @@ const _: () = assert!(std::mem::size_of::<vx_block_at>() == 8);
 const _: () = assert!(std::mem::size_of::<vx_scan_hit>() == 16);
 const _: () = assert!(std::mem::size_of::<vx_box_batch>() == 40);
 const _: () = assert!(std::mem::size_of::<vx_box_hit>() == 32);
+const _: () = assert!(std::mem::size_of::<vx_move_shape>() == 16);
+const _: () = assert!(std::mem::size_of::<vx_move_hit>() == 48);
 const _: () = assert!(std::mem::size_of::<vx_flood_shape>() == 36);
 const _: () = assert!(std::mem::size_of::<vx_flood_info>() == 16);
 const _: () = assert!(std::mem::size_of::<vx_light_shape>() == 32);
@@ -396,6 +426,12 @@ extern "C" {
     /// what each of `count` float boxes (`vx_box_batch`) holds: how many voxels of its cover hold a block (`only_value`: of that id), the first
     /// of them, their bounds; a record that is no box gives `VX_BOX_INVALID`; `memory`: VX_MEM_HOST / VX_MEM_DEVICE (`out` aligned to 16 bytes)
     pub fn vx_overlap_boxes(ctx: *mut vx_context, boxes: *const vx_box_batch, count: u32, memory: c_int, out: *mut vx_box_hit) -> c_int;
+    /// each of `count` float boxes (`vx_box_batch`) moved by its motion (a float[3] at motion + i * motion_stride, 0 = one for all) times
+    /// `shape.scale`, axis by axis in `shape.order`, stopped `shape.skin` short of the first counted voxel ahead of its leading face; a record
+    /// that is no box or has no finite motion of at most `VX_MOVE_MAX_TRAVEL` gives `VX_MOVE_INVALID`; `memory`: VX_MEM_HOST / VX_MEM_DEVICE
+    /// (`out` aligned to 16 bytes)
+    pub fn vx_move_boxes(ctx: *mut vx_context, boxes: *const vx_box_batch, motion: *const c_void, motion_stride: u32, count: u32,
+                         shape: *const vx_move_shape, memory: c_int, out: *mut vx_move_hit) -> c_int;
     /// step distances through air around each of `count` positions (read as `vx_block_points` reads them): a breadth-first flood of the box
     /// `shape` describes; query k's field -- a byte a cell, x fastest -- at fields + k * field_stride (a multiple of 16, 0 = the voxel count
     /// rounded up to 16), its record at info[k]; either output may be null, not both; `memory`: VX_MEM_HOST / VX_MEM_DEVICE (both aligned to 16)

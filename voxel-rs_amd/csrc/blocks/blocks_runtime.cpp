@@ -1,10 +1,10 @@
 // libvoxelhip.so, block ids read from the device: vx_block_points and vx_read_region, the first block along an axis: vx_scan_points and
-// vx_scan_columns, the blocks of a box as a list: vx_list_region, what a batch of float boxes holds: vx_overlap_boxes, step distances
+// vx_scan_columns, the blocks of a box as a list: vx_list_region, what a batch of float boxes holds: vx_overlap_boxes, such boxes moved through the world: vx_move_boxes, step distances
 // through air around a batch of positions: vx_flood_points, the light levels of a batch of boxes: vx_light_boxes, and walking distances and
 // paths for ground agents: vx_walk_points (include/voxel_hip.h)
-// -- argument checks (vx_blocks.hpp's, vx_scan.hpp's, vx_list.hpp's, vx_boxes.hpp's, vx_flood.hpp's, vx_light.hpp's and vx_walk.hpp's rules),
+// -- argument checks (vx_blocks.hpp's, vx_scan.hpp's, vx_list.hpp's, vx_boxes.hpp's, vx_move.hpp's, vx_flood.hpp's, vx_light.hpp's and vx_walk.hpp's rules),
 // the pinned scratch the host-memory calls read and write through (csrc/vx_pinned_pool.hpp), and the launches of kernels_blocks.hip,
-// kernels_scan.hip, kernels_list.hip, kernels_boxes.hip, kernels_flood.hip, kernels_light.hip and kernels_walk.hip.
+// kernels_scan.hip, kernels_list.hip, kernels_boxes.hip, kernels_move.hip, kernels_flood.hip, kernels_light.hip and kernels_walk.hip.
 // A further translation unit on the context, like raycast_runtime.cpp: what it needs of the context is vx_context.hpp's (runtime.cpp).
 #include <cstring>
 #include <map>
@@ -329,6 +329,49 @@ int vx_overlap_boxes(vx_context* ctx, const vx_box_batch* boxes, uint32_t count,
                                       pool.dev + at_extents, 12, boxes->offset_stride ? 12u : 0u, boxes->extents_stride ? 12u : 0u, boxes->only_value, count,
                                       reinterpret_cast<vx_box_hit*>(pool.dev + at_out)));
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // synchronous, like vx_block_points' host-memory call
+    std::memcpy(out, pool.host + at_out, out_bytes);
+    return VX_OK;
+}
+
+int vx_move_boxes(vx_context* ctx, const vx_box_batch* boxes, const void* motion, uint32_t motion_stride, uint32_t count, const vx_move_shape* shape,
+                  int memory, vx_move_hit* out) {
+    static_assert(sizeof(vx_move_hit) == 48 && sizeof(vx_move_shape) == 16, "the ABI's record sizes");
+    if (memory != VX_MEM_HOST && memory != VX_MEM_DEVICE) return fail(VX_ERR_INVALID_ARGUMENT, "move_boxes: memory is neither VX_MEM_HOST nor VX_MEM_DEVICE");
+    if (const char* what = vxb::check_move(boxes, motion, motion_stride, count, shape, out)) return fail(VX_ERR_INVALID_ARGUMENT, std::string("move_boxes: ") + what);
+    if (count && memory == VX_MEM_DEVICE && reinterpret_cast<uintptr_t>(out) % 16) return fail(VX_ERR_INVALID_ARGUMENT, "move_boxes: out in device memory must be aligned to 16 bytes");
+    if (!ctx) return fail(VX_ERR_INVALID_ARGUMENT, "null context");
+    if (int rc = vxrt::check_ready(ctx)) return rc;
+    VX_LOCK(ctx);
+    if (count == 0) return VX_OK;
+
+    if (memory == VX_MEM_DEVICE) {
+        HIP_TRY(vxk::launch_move_boxes(kernel_variant(ctx), ctx->stream, vxrt::scene_on_bytes(ctx), boxes->origin, boxes->offset, boxes->extents, motion,
+                                       boxes->origin_stride, boxes->offset_stride, boxes->extents_stride, motion_stride, boxes->only_value, *shape, count, out));
+        return vxrt::mark_world_read(ctx);
+    }
+
+    // vx_overlap_boxes' layout with the motions (one; one a box) behind the extents: each vector's bytes unchanged
+    const auto packed = [count](const void* p, uint32_t stride) { return !p ? size_t(0) : (stride ? size_t(count) * 12 : size_t(12)); };
+    const size_t at_offset = packed(boxes->origin, boxes->origin_stride), at_extents = at_offset + packed(boxes->offset, boxes->offset_stride);
+    const size_t at_motion = at_extents + packed(boxes->extents, boxes->extents_stride);
+    const size_t at_out = round16(at_motion + packed(motion, motion_stride)), out_bytes = size_t(count) * sizeof(vx_move_hit);
+    vxrt::PinnedPool& pool = vxrt::pinned_pool_of(ctx->device);
+    std::lock_guard<std::mutex> pool_lock(pool.mutex);
+    if (int rc = vxrt::pinned_pool_reserve(pool, at_out + out_bytes)) return rc;
+    const auto pack = [count, &pool](size_t at, const void* p, uint32_t stride) {
+        const uint8_t* from = static_cast<const uint8_t*>(p);
+        if (!p) return;
+        if (stride == 12 || stride == 0) std::memcpy(pool.host + at, from, stride ? size_t(count) * 12 : size_t(12));
+        else for (size_t i = 0; i < count; ++i) std::memcpy(pool.host + at + 12 * i, from + size_t(stride) * i, 12);  // (exactly a vector's bytes)
+    };
+    pack(0, boxes->origin, boxes->origin_stride);
+    pack(at_offset, boxes->offset, boxes->offset_stride);
+    pack(at_extents, boxes->extents, boxes->extents_stride);
+    pack(at_motion, motion, motion_stride);
+    HIP_TRY(vxk::launch_move_boxes(kernel_variant(ctx), ctx->stream, vxrt::scene_on_bytes(ctx), pool.dev, boxes->offset ? pool.dev + at_offset : nullptr,
+                                   pool.dev + at_extents, pool.dev + at_motion, 12, boxes->offset_stride ? 12u : 0u, boxes->extents_stride ? 12u : 0u,
+                                   motion_stride ? 12u : 0u, boxes->only_value, *shape, count, reinterpret_cast<vx_move_hit*>(pool.dev + at_out)));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // synchronous, like vx_overlap_boxes' host-memory call
     std::memcpy(out, pool.host + at_out, out_bytes);
     return VX_OK;
 }

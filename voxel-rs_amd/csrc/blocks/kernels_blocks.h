@@ -1,5 +1,5 @@
 // What blocks_runtime.cpp knows of the block lookup kernels (kernels_blocks.hip), of the scans along an axis (kernels_scan.hip) and of the
-// list of a box's blocks (kernels_list.hip), of what a batch of float boxes holds (kernels_boxes.hip), of the floods around a batch of positions
+// list of a box's blocks (kernels_list.hip), of what a batch of float boxes holds (kernels_boxes.hip), of a batch of float boxes moved through the world (kernels_move.hip), of the floods around a batch of positions
 // (kernels_flood.hip), of the light levels of a batch of boxes (kernels_light.hip) and of the walks of ground agents (kernels_walk.hip).
 #pragma once
 
@@ -11,6 +11,7 @@
 #include "vx_flood.hpp"
 #include "vx_light.hpp"
 #include "vx_list.hpp"
+#include "vx_move.hpp"
 #include "vx_scan.hpp"
 #include "vx_walk.hpp"
 
@@ -51,6 +52,13 @@ hipError_t launch_list_write(int svo, hipStream_t stream, const vxd::SceneArgs& 
 hipError_t launch_overlap_boxes(int svo, hipStream_t stream, const vxd::SceneArgs& sc, const void* origin, const void* offset, const void* extents,
                                 uint32_t origin_stride, uint32_t offset_stride, uint32_t extents_stride, uint32_t only_value, uint32_t count,
                                 vx_box_hit* out);
+
+// `count` (1..2^24) workgroups of one wave, one box a wave: the boxes as launch_overlap_boxes reads them, a float[3] at motion + i *
+// motion_stride (4-byte aligned; the stride a multiple of 4 and >= 12, or 0 = one motion for every box); shape: within vxb::check_move's
+// rules; out: `count` records of device-visible memory, 16-byte aligned, that overlaps no input
+hipError_t launch_move_boxes(int svo, hipStream_t stream, const vxd::SceneArgs& sc, const void* origin, const void* offset, const void* extents,
+                             const void* motion, uint32_t origin_stride, uint32_t offset_stride, uint32_t extents_stride, uint32_t motion_stride,
+                             uint32_t only_value, const vx_move_shape& shape, uint32_t count, vx_move_hit* out);
 
 // `count` (1..2^24) workgroups of 256 threads, one query a workgroup: a float[3] at pos + i * pos_stride, read as launch_block_points reads it;
 // shape: within vxb::check_flood's rules (refused here too: the kernel indexes LDS by it); fields (may be null: records only): 16-byte aligned,

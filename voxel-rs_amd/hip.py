@@ -47,6 +47,11 @@ SCAN_HIT_DTYPE = np.dtype([("coord", "<i4"), ("value", "<u4"), ("cell_log2", "<u
 # read_region's order, their bounds [lo, hi); blocks == VX_BOX_INVALID: the record described no box
 BOX_HIT_DTYPE = np.dtype([("blocks", "<u4"), ("value", "<u4"), ("lo", "<i4", 3), ("hi", "<i4", 3)])
 VX_BOX_INVALID = 0xFFFFFFFF
+# vx_move_hit (vx_move_boxes): how far a box got -- its origin after the move, what was added to it per axis, the sides on which a block lay
+# ahead (bit 2a + (d_a > 0), numbered like face_id; VX_MOVE_INVALID: no box, or no motion), per axis the stopping voxel's value
+MOVE_HIT_DTYPE = np.dtype([("origin", "<f4", 3), ("moved", "<f4", 3), ("contacts", "<u4"), ("value", "<u4", 3), ("_pad", "<u4", 2)])
+VX_MOVE_INVALID, VX_MOVE_MAX_TRAVEL = 0xFFFFFFFF, 64.0
+VX_MOVE_ORDER_YXZ, VX_MOVE_ORDER_XYZ, VX_MOVE_ORDER_ZYX = 0x21, 0x24, 0x06  # axis of pass 0 | pass 1 << 2 | pass 2 << 4
 # vx_flood_info (vx_flood_points): what a flood reached -- cells with a step count (VX_FLOOD_INVALID: no position), the largest step count,
 # the faces of the box a reached cell lies on (0: enclosed), the value at the seed. A field is one byte a cell: the step count, or one of
 # VX_FLOOD_NO_POSITION, VX_FLOOD_UNREACHED, VX_FLOOD_BLOCKED
@@ -71,7 +76,7 @@ FACE_NORMALS = np.array([[-1, 0, 0], [1, 0, 0], [0, -1, 0], [0, 1, 0], [0, 0, -1
 assert HIT_DTYPE.itemsize == 48 and PICKER_TASK_DTYPE.itemsize == 48 and PICKER_RESULT_DTYPE.itemsize == 48 and FRAME_DTYPE.itemsize == 36
 assert ENTITY_DTYPE.itemsize == 64 and AABB_RESULT_DTYPE.itemsize == 24 and RAY_HIT_DTYPE.itemsize == 32 and SCAN_HIT_DTYPE.itemsize == 16
 assert BLOCK_AT_DTYPE.itemsize == 8 and BOX_HIT_DTYPE.itemsize == 32 and FLOOD_INFO_DTYPE.itemsize == 16 and LIGHT_INFO_DTYPE.itemsize == 16
-assert WALK_INFO_DTYPE.itemsize == 32
+assert WALK_INFO_DTYPE.itemsize == 32 and MOVE_HIT_DTYPE.itemsize == 48
 
 COUNTER_FIELDS = ["rays", "iterations", "pushes", "leaf_tests", "leaf_tests_trilinear", "boundaries", "csvo_header_bytes", "csvo_pointer_bytes",
                   "pixels", "lit_pixels", "shadow_rays", "wave_steps", "services", "refills", "tail_wave_steps", "tail_iterations"]
@@ -101,6 +106,11 @@ class BoxBatch(C.Structure):
     """vx_box_batch"""
     _fields_ = [("origin", C.c_void_p), ("offset", C.c_void_p), ("extents", C.c_void_p), ("origin_stride", C.c_uint32), ("offset_stride", C.c_uint32),
                 ("extents_stride", C.c_uint32), ("only_value", C.c_uint32)]
+
+
+class MoveShape(C.Structure):
+    """vx_move_shape"""
+    _fields_ = [("scale", C.c_float), ("skin", C.c_float), ("order", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class FloodShape(C.Structure):
@@ -160,6 +170,7 @@ SYMBOLS = {
     "vx_scan_points": (_int, [_vp, _vp, _u32, _u32, _int, _u32, _int, _vp]),
     "vx_scan_columns": (_int, [_vp, C.POINTER(C.c_int32 * 3), C.POINTER(_u32 * 3), _int, _int, _vp]),
     "vx_overlap_boxes": (_int, [_vp, C.POINTER(BoxBatch), _u32, _int, _vp]),
+    "vx_move_boxes": (_int, [_vp, C.POINTER(BoxBatch), _vp, _u32, _u32, C.POINTER(MoveShape), _int, _vp]),
     "vx_flood_points": (_int, [_vp, _vp, _u32, _u32, C.POINTER(FloodShape), _int, _vp, _u32, _vp]),
     "vx_light_boxes": (_int, [_vp, _vp, _u32, _u32, C.POINTER(LightShape), _int, _vp, _u32, _vp]),
     "vx_walk_points": (_int, [_vp, _vp, _u32, _vp, _u32, _u32, C.POINTER(WalkShape), _int, _vp, _u32, _vp, _vp]),
@@ -343,6 +354,31 @@ def entity_boxes(entities):
 def box_hits_to_numpy(hits):
     """A device record tensor of Svo.overlap_boxes as BOX_HIT_DTYPE records (copies to the host: synchronise first)."""
     return hits.cpu().numpy().view(np.uint8).reshape(-1).view(BOX_HIT_DTYPE)
+
+
+def move_hits_to_numpy(hits):
+    """A device record tensor of Svo.move_boxes as MOVE_HIT_DTYPE records (copies to the host: synchronise first)."""
+    return hits.cpu().numpy().view(np.uint8).reshape(-1).view(MOVE_HIT_DTYPE)
+
+
+def MOVE_SHAPE(scale=1.0, skin=2.0 ** -10, order=VX_MOVE_ORDER_YXZ, flags=0):
+    """A vx_move_shape."""
+    return MoveShape(float(scale), float(skin), int(order), int(flags))
+
+
+def entity_velocities(entities):
+    """vx_entity.velocity as the `motion` of Svo.move_boxes: an (N, 3) float32 view at a stride of 64 bytes, of what entity_boxes takes."""
+    if isinstance(entities, np.ndarray):
+        if entities.dtype != ENTITY_DTYPE:
+            raise TypeError("entity_velocities: a host array must be of hip.ENTITY_DTYPE")
+        return entities.reshape(-1)["velocity"]
+    import torch
+
+    nbytes = entities.numel() * entities.element_size()
+    if nbytes % ENTITY_DTYPE.itemsize or not entities.is_contiguous():
+        raise TypeError("entity_velocities: a device tensor must be contiguous and hold whole 64-byte vx_entity records")
+    at = ENTITY_DTYPE.fields["velocity"][1] // 4
+    return entities.reshape(-1).view(torch.uint8).view(torch.float32).view(-1, 16)[:, at:at + 3]
 
 
 def flood_infos_to_numpy(infos):
@@ -934,6 +970,48 @@ class Svo:
         elif not out.is_cuda or not out.is_contiguous() or out.numel() * out.element_size() < count * BOX_HIT_DTYPE.itemsize:
             raise TypeError("overlap_boxes: out must be a contiguous CUDA tensor of at least N x 32 bytes")
         _check(lib().vx_overlap_boxes(self._h, C.byref(batch), count, VX_MEM_DEVICE, _vp(out.data_ptr())))
+        return out
+
+    # -- float boxes moved through the world, stopped by blocks (what physics.rs:171-184 asks of the picker fan, of every voxel ahead) ---------------
+    def move_boxes(self, origin, extents, motion, offset=None, scale=1.0, skin=2.0 ** -10, order=VX_MOVE_ORDER_YXZ, only_value=0, out=None, device=False):
+        """vx_move_boxes: each box [origin + offset, origin + offset + extents) moved by motion * scale, axis by axis in `order`, stopped `skin`
+        short of the first counted voxel ahead of its leading face (MOVE_HIT_DTYPE: the origin after the move, moved per axis, contacts -- or
+        VX_MOVE_INVALID --, the stopping voxel's value per axis). The boxes as overlap_boxes takes them; motion: (N, 3) float32 at any row
+        stride, or one (3,) vector for every box (entity_velocities(e) gives vx_entity.velocity in place, with scale = delta_time).
+        Host (NumPy arrays): synchronous; returns `out` or a fresh array of MOVE_HIT_DTYPE.
+        Device (torch CUDA tensors; device=True insists on them): returns after enqueueing, without synchronising -- pair with sync(); the
+        records are `out` or a fresh int32 tensor of shape (N, 12) on the origins' device (move_hits_to_numpy)."""
+        host = isinstance(origin, np.ndarray)
+        if len(origin.shape) != 2 or origin.shape[1] != 3:
+            raise TypeError("move_boxes: origin must have shape (N, 3)")
+        count = int(origin.shape[0])
+        given = [origin, extents, motion] + ([offset] if offset is not None else [])
+        if host and (device or not all(isinstance(x, np.ndarray) for x in given)):
+            raise TypeError("move_boxes: origin, extents, motion and offset must all be NumPy arrays, or -- device=True -- all torch CUDA tensors")
+        if not host and not all(getattr(x, "is_cuda", False) for x in given):
+            raise TypeError("move_boxes: origin, extents, motion and offset must all be NumPy arrays or all torch CUDA tensors")
+        batch = BoxBatch()
+        batch.origin, batch.origin_stride = _ray_vectors("origin", origin, count, 3)
+        batch.extents, batch.extents_stride = _ray_vectors("extents", extents, count, 3)
+        if offset is not None:
+            batch.offset, batch.offset_stride = _ray_vectors("offset", offset, count, 3)
+        batch.only_value = int(only_value)
+        motion_ptr, motion_stride = _ray_vectors("motion", motion, count, 3)
+        shape = MOVE_SHAPE(scale, skin, order)
+        if host:
+            if out is None:
+                out = np.zeros(count, dtype=MOVE_HIT_DTYPE)
+            elif not isinstance(out, np.ndarray) or out.dtype != MOVE_HIT_DTYPE or out.size != count or not out.flags.c_contiguous or not out.flags.writeable:
+                raise TypeError("move_boxes: out must be a writeable C-contiguous array of N hip.MOVE_HIT_DTYPE records")
+            _check(lib().vx_move_boxes(self._h, C.byref(batch), _vp(motion_ptr), motion_stride, count, C.byref(shape), VX_MEM_HOST, out.ctypes.data_as(_vp)))
+            return out
+        import torch
+
+        if out is None:
+            out = torch.empty((count, 12), dtype=torch.int32, device=origin.device)
+        elif not out.is_cuda or not out.is_contiguous() or out.numel() * out.element_size() < count * MOVE_HIT_DTYPE.itemsize:
+            raise TypeError("move_boxes: out must be a contiguous CUDA tensor of at least N x 48 bytes")
+        _check(lib().vx_move_boxes(self._h, C.byref(batch), _vp(motion_ptr), motion_stride, count, C.byref(shape), VX_MEM_DEVICE, _vp(out.data_ptr())))
         return out
 
     # -- step distances through air (a breadth-first search over get_block, gameplay.rs:161-201, for a batch) ----------------------------------------

@@ -925,8 +925,9 @@ uint32_t vx_timeline_read(vx_context* ctx, uint64_t* out, uint32_t capacity_wave
 int vx_image_info(const vx_context* ctx, uint64_t out[4]);
 /* The scheduling knobs this context runs with (they reorder a frame's work and change no pixel): [0] refill threshold, [1] service threshold, [2] cap on
  * the persistent waves per CU (0 = none), [3] length of the sub-tile queue's stretches (0 = by the launch), [4] width of the tile numbering's strips, [5] cost-ordered
- * queue on / off, [6] wave slots per CU left to RCCL (vx_set_comm_headroom), [7] 1 = this is the library's measurement build (the only one that reads the
- * VX_REFILL_MIN / VX_WAVES_PER_CU / VX_QUEUE_STRIPE / VX_TILE_STRIP / VX_HOT_FIRST environment variables). For the tests. */
+ * queue on / off, [6] wave slots per CU left to RCCL (vx_set_comm_headroom), [7] bit 0 = this is the library's measurement build (the only one that reads the
+ * VX_REFILL_MIN / VX_WAVES_PER_CU / VX_QUEUE_STRIPE / VX_TILE_STRIP / VX_HOT_FIRST environment variables), bit 1 = whole frames run the render kernel's
+ * whole-frame build (VX_PLAIN_FRAME, default on). For the tests. */
 int vx_debug_knobs(const vx_context* ctx, uint32_t out[8]);
 /* CSVO worlds rendered from their traversal image: since creation (or the last reset), [0] rays that were led into the voxel they
  * started in and made that walk on the world's own bytes, [1] those of them whose pixel was rendered again on the bytes (the walk

@@ -12,13 +12,15 @@ namespace vxk {
 // world's own bytes: one build per format, it writes hit records and counters where the pointers it is given are not null) or VX_SVO_IMAGE /
 // VX_SVO_IMAGE_WIDE (the traversal image). For an image: hits = the build that also writes hit records (looser register bound); foreign =
 // 0 (the image of an ESVO world), VX_SVO_CSVO (rays led into a voxel walk it on the world's bytes) or kForeignRerun (they are listed and
-// run afterwards); levels = LDS-resident stack levels, 13 or 16; hot = the LDS copy of the top two levels.
+// run afterwards); levels = LDS-resident stack levels, 13 or 16; hot = the LDS copy of the top two levels; plain = the whole-frame build (image-only,
+// byte-offset image: for launches that are vxk::plain_frame, whose seven launch constants it has as literals).
 struct RenderBuild {
     int svo;
     bool hits;
     int foreign;
     int levels;
     bool hot;
+    bool plain;
 };
 const void* render_persistent_fn(const RenderBuild& b);  // null: there is no such build
 size_t render_persistent_lds(const RenderBuild& b);      // dynamic LDS of one wave

@@ -13,6 +13,10 @@
 #ifndef VX_ASM_LOOP
 #define VX_ASM_LOOP 1
 #endif
+// 1 = the kernels that list every inside-voxel ray CALL their second phase (run_listed_rays); 0 = they have it in line, as the walk's kernels do (A/B builds)
+#ifndef VX_LISTED_CALL
+#define VX_LISTED_CALL 1
+#endif
 // 1 = the library's timeline build: the image-only kernels fill in the wave timeline (PersistentArgs::timeline; make tl)
 #ifndef VX_TIMELINE_BUILD
 #define VX_TIMELINE_BUILD 0
@@ -181,6 +185,90 @@ __device__ __forceinline__ uint32_t rank_in(unsigned long long m) { return __bui
 __device__ __forceinline__ uint32_t fbits(float f) { return __float_as_uint(f); }
 __device__ __forceinline__ float bitsf(uint32_t u) { return __uint_as_float(u); }
 
+// render_persistent's arguments as they lie in the kernel-argument segment: in their order, each at its natural alignment. What a device function
+// that the kernel CALLS reads them through -- scalar loads from the segment, where arguments handed on by value would arrive in vector registers.
+struct RenderKernargs {
+    SceneArgs sa;
+    RenderParams p;
+    PersistentArgs a;
+    float4* out;
+    vx_hit* hits;
+    unsigned long long* counters;
+    PixelList todo;
+};
+static_assert(offsetof(RenderKernargs, sa) == 0 && offsetof(RenderKernargs, p) == 152 && offsetof(RenderKernargs, a) == 376 && offsetof(RenderKernargs, out) == 464 &&
+                  offsetof(RenderKernargs, hits) == 472 && offsetof(RenderKernargs, counters) == 480 && offsetof(RenderKernargs, todo) == 488 && sizeof(RenderKernargs) == 512,
+              "the kernel-argument segment of render_persistent (the .args offsets of its code object's metadata)");
+
+// The second phase of an image-only render of a CSVO world: the rays the wave listed (list_rays: `my_chunk` = its newest chunk + 1, wave-uniform), 64 at
+// a time, from their origins on the world's own bytes with the reference's own cursor (a primary ray: the whole pixel). LEVELS: the three-word
+// stack levels that fit the kernel's LDS (the first phase is over).
+template <int LEVELS>
+__device__ __forceinline__ void listed_rays(const SceneArgs& sa, const RenderParams& p, float4* out, const PixelList& todo, uint32_t my_chunk, uint32_t lane, StackSpill* spill) {
+    DevScene sc_bytes = make_scene(sa);
+    sc_bytes.tex.pow2_height = true;  // (as in the first phase: an image kernel is only launched for such textures)
+    Stack<64, false, false, LEVELS> st2;  // (three full words per slot, over the first phase's LDS)
+    st2.init(lane, spill);
+    const float to_light[3] = {-p.u.light_dir[0], -p.u.light_dir[1], -p.u.light_dir[2]};
+    for (uint32_t c = my_chunk; c != 0;) {
+        const uint32_t* chunk = todo.chunks + size_t(c - 1) * kRayChunkDwords;
+        const uint32_t n = __builtin_amdgcn_readfirstlane(chunk[1]);
+        c = __builtin_amdgcn_readfirstlane(chunk[0]);
+        if (lane < n) {
+            const uint4* w = reinterpret_cast<const uint4*>(chunk + kRayChunkHeader + lane * kRayRecordDwords);
+            const uint4 w0 = w[0];
+            const uint32_t index = w0.x & 0x7fffffffu;
+            float color[4];
+            if (w0.x >> 31) {
+                const uint4 w1 = w[1];
+                const float ds = bitsf(w[2].x);
+                // a shadow ray: from its origin on the world's bytes, with the reference's own cursor
+                Trav<VX_SVO_CSVO> tb;
+                tb.init_in_octree_space(sc_bytes, bitsf(w0.y), bitsf(w0.z), bitsf(w0.w), to_light, -1.0f);
+                Result rs;
+                for (;;) {
+                    TravStatus s2 = tb.template step<false, false, false>(sc_bytes, st2, nullptr, nullptr);
+                    if (s2 == kTravAtLeaf) {
+                        const LeafOutcome o = tb.template leaf_test<false, false>(sc_bytes, st2, true, rs, nullptr, nullptr);
+                        if (o == kLeafHit) break;
+                        s2 = o == kLeafPassed ? kTravContinue : kTravFinished;
+                    }
+                    if (s2 == kTravFinished) {
+                        result_miss(rs, tb.inside_voxel());
+                        break;
+                    }
+                }
+                color[0] = bitsf(w1.x); color[1] = bitsf(w1.y); color[2] = bitsf(w1.z); color[3] = bitsf(w1.w);
+                apply_light(p, color, ds, rs.t < 0.0f ? 1.0f : 0.0f);
+            } else {
+                uint32_t x, y;
+                out_index_to_xy(p, index, x, y);
+                shade_pixel<VX_SVO_CSVO, false>(sc_bytes, p, x, y, st2, color, nullptr, nullptr, nullptr, nullptr);
+            }
+            if (out) store_pixel(p, out, index, color);
+        }
+    }
+}
+
+// ... as a function of its own, for the kernels that list every inside-voxel ray (kForeignRerun: the C3 kernel), called behind the render loop by the
+// waves that listed any -- a few dozen rays a frame. Inlined there, its cursor, scene and stack shared the loop's register budget: 19 spilled vector
+// registers and 40 + 22 scratch accesses in that kernel's service phases, 5 and 10 + 5 with the call. It stays in the kernel: the lists are the
+// waves' own, and a second kernel is a second command (profiles/round6). The arguments come from the kernel-argument segment, as scalars.
+// (`kernargs`: the kernel's __builtin_amdgcn_kernarg_segment_ptr() -- in a function that is not a kernel the builtin is a null pointer. An argument
+// arrives in vector registers: made the wave's value again here, the loads through it are scalar loads from the constant address space.)
+typedef const __attribute__((address_space(4))) RenderKernargs* KernargsPtr;
+template <int LEVELS, bool PLAIN>
+__device__ __attribute__((noinline)) void run_listed_rays(KernargsPtr kernargs, uint32_t my_chunk) {
+    const uint64_t bits = reinterpret_cast<uint64_t>(kernargs);
+    const uint64_t uniform = uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(bits))))) |
+                             (uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(bits >> 32))))) << 32);
+    const RenderKernargs& k = *(const RenderKernargs*)reinterpret_cast<KernargsPtr>(uniform);
+    RenderParams p = k.p;
+    if constexpr (PLAIN) { p.tile_count = 1u; p.tile_order = nullptr; p.rgba8 = 0u; p.affine_view = 1u; }
+    StackSpill spill;
+    listed_rays<LEVELS>(k.sa, p, k.out, k.todo, __builtin_amdgcn_readfirstlane(my_chunk), threadIdx.x, &spill);
+}
+
 // IMAGE = the rays walk the traversal image of the world (traversal_image.hpp) instead of its own bytes: a build per way of addressing it (a buffer
 // resource / a 64-bit base). An image kernel is only launched for worlds whose depth its LDS-resident stack levels
 // cover (LV: 13 three-word levels, or 16 with a 16-bit third plane -- image cursors need no more of the third word), so its traversal loop
@@ -192,7 +280,11 @@ __device__ __forceinline__ float bitsf(uint32_t u) { return __uint_as_float(u); 
 // HITS / STATS: hit records and the instrumented counters are written where the pointers are not null; the kernels
 // on the world's own bytes are built once per format with both (they are the fall-back and the instrumented path, not the fast one).
 constexpr int min_waves_of(int svo, bool hits) { return ((svo == VX_SVO_IMAGE || svo == VX_SVO_IMAGE_WIDE) && !hits) ? 4 : 1; }
-template <int SVO, bool HITS, bool STATS, int FOREIGN = 0, int LV = kLdsLevels, bool HOT = false>
+// PLAIN (the image-only kernels on a byte-offset image): the launch is a whole frame as vxk::plain_frame (vx_args.hpp) says -- no tile list, RGBA32F,
+// a target, tickets in the order of their numbers, no cost notes, no excursion counters, an affine view. The seven are literals in this build:
+// the cost notes, the padding pixels, a tile list's index arithmetic, the order table's read, the perspective divide and the excursion atomics
+// are not in its code, and their launch constants take no scalar registers.
+template <int SVO, bool HITS, bool STATS, int FOREIGN = 0, int LV = kLdsLevels, bool HOT = false, bool PLAIN = false>
 __global__ __launch_bounds__(64, min_waves_of(SVO, HITS)) void render_persistent(SceneArgs sa, RenderParams p, PersistentArgs a, float4* __restrict__ out,
                                                         vx_hit* __restrict__ hits, unsigned long long* __restrict__ counters, PixelList todo) {
     constexpr bool IMAGE = SVO == VX_SVO_IMAGE || SVO == VX_SVO_IMAGE_WIDE;
@@ -214,6 +306,12 @@ __global__ __launch_bounds__(64, min_waves_of(SVO, HITS)) void render_persistent
     // with them the ESVO image kernel spilled 123 scalar registers instead of 50 and was 13 % longer (C3 +2 % without: profiles/round3/pass_ag).
     constexpr bool TL = VX_TIMELINE_BUILD != 0 && IMAGE && !HITS && !STATS && !HOT;
     if constexpr (!TL) a.timeline = nullptr;
+    static_assert(!PLAIN || (SVO == VX_SVO_IMAGE && !HITS && !STATS && !HOT), "the whole-frame builds: image-only, byte-offset images");
+    if constexpr (PLAIN) {  // (p and a are this kernel's own copies: what launch_render has checked, said to the compiler)
+        p.tile_count = 1u; p.tile_order = nullptr; p.rgba8 = 0u; p.affine_view = 1u;
+        a.order = nullptr; a.cost_cur = nullptr; a.excursions = nullptr;
+        __builtin_assume(out != nullptr);
+    }
     auto vouched = [](DevScene s) { s.tex.pow2_height = IMAGE; return s; };
     const DevScene sc = vouched(IMAGE ? make_image_scene(sa) : make_scene(sa));
     const uint32_t lane = threadIdx.x;
@@ -715,49 +813,11 @@ __global__ __launch_bounds__(64, min_waves_of(SVO, HITS)) void render_persistent
         row[7] = ((unsigned long long)(walk_phases & 0xfffu) << 52) | ((unsigned long long)(walk_trips & 0xfffffu) << 32) | walk_cycles;  // the walks inside voxels: phases, trips of their loop, cycles
     }
     // ---- second phase (image-only renders of a CSVO world): the rays this wave listed, on the world's own bytes ----
-    if (FOREIGN == kForeignRerun || (FOREIGN == VX_SVO_CSVO && !HITS)) {
-        const DevScene sc_bytes = vouched(make_scene(sa));
-        Stack<64, false, false, int(FullStack::kStackBytes / (64u * 12u))> st2;  // (three full words per slot, over the same LDS: the first phase is over)
-        st2.init(lane, &spill);
-        const float to_light[3] = {-p.u.light_dir[0], -p.u.light_dir[1], -p.u.light_dir[2]};
-        for (uint32_t c = my_chunk; c != 0;) {
-            const uint32_t* chunk = todo.chunks + size_t(c - 1) * kRayChunkDwords;
-            const uint32_t n = __builtin_amdgcn_readfirstlane(chunk[1]);
-            c = __builtin_amdgcn_readfirstlane(chunk[0]);
-            if (lane < n) {
-                const uint4* w = reinterpret_cast<const uint4*>(chunk + kRayChunkHeader + lane * kRayRecordDwords);
-                const uint4 w0 = w[0];
-                const uint32_t index = w0.x & 0x7fffffffu;
-                float color[4];
-                if (w0.x >> 31) {
-                    const uint4 w1 = w[1];
-                    const float ds = bitsf(w[2].x);
-                    // a shadow ray: from its origin on the world's bytes, with the reference's own cursor
-                    Trav<VX_SVO_CSVO> tb;
-                    tb.init_in_octree_space(sc_bytes, bitsf(w0.y), bitsf(w0.z), bitsf(w0.w), to_light, -1.0f);
-                    Result rs;
-                    for (;;) {
-                        TravStatus s2 = tb.template step<false, false, false>(sc_bytes, st2, nullptr, nullptr);
-                        if (s2 == kTravAtLeaf) {
-                            const LeafOutcome o = tb.template leaf_test<false, false>(sc_bytes, st2, true, rs, nullptr, nullptr);
-                            if (o == kLeafHit) break;
-                            s2 = o == kLeafPassed ? kTravContinue : kTravFinished;
-                        }
-                        if (s2 == kTravFinished) {
-                            result_miss(rs, tb.inside_voxel());
-                            break;
-                        }
-                    }
-                    color[0] = bitsf(w1.x); color[1] = bitsf(w1.y); color[2] = bitsf(w1.z); color[3] = bitsf(w1.w);
-                    apply_light(p, color, ds, rs.t < 0.0f ? 1.0f : 0.0f);
-                } else {
-                    uint32_t x, y;
-                    out_index_to_xy(p, index, x, y);
-                    shade_pixel<VX_SVO_CSVO, false>(sc_bytes, p, x, y, st2, color, nullptr, nullptr, nullptr, nullptr);
-                }
-                if (out) store_pixel(p, out, index, color);
-            }
-        }
+    constexpr int kLevels2 = int(FullStack::kStackBytes / (64u * 12u));
+    if constexpr (FOREIGN == kForeignRerun && VX_LISTED_CALL != 0) {
+        if (my_chunk != 0) run_listed_rays<kLevels2, PLAIN>((KernargsPtr)__builtin_amdgcn_kernarg_segment_ptr(), my_chunk);  // (wave-uniform: nearly every wave has listed nothing)
+    } else if constexpr (FOREIGN == kForeignRerun || (FOREIGN == VX_SVO_CSVO && !HITS)) {
+        listed_rays<kLevels2>(sa, p, out, todo, my_chunk, lane, &spill);  // (the walk's kernels: what the walk gave up on; in line, as it was)
     }
     // ---- second phase (FOREIGN = VX_SVO_CSVO, renders with hit records): the pixels this wave gave up on the image, whole, on the world's own bytes ----
     if (FOREIGN == VX_SVO_CSVO && HITS) {
@@ -809,7 +869,7 @@ __global__ __launch_bounds__(64, min_waves_of(SVO, HITS)) void render_persistent
 namespace vxk {
 
 #define VX_K(...) reinterpret_cast<const void*>(&render_persistent<__VA_ARGS__>)
-// The builds that exist (14): on the world's own bytes one per format, with hit records and counters; on a traversal image, image-only: worlds
+// The builds that exist (14, and the four whole-frame ones): on the world's own bytes one per format, with hit records and counters; on a traversal image, image-only: worlds
 // without walks (ESVO) on 13 levels / 16 levels / 16 levels in the wide layout; CSVO worlds whose inside-voxel rays are listed (at most 12
 // levels: 13-level stack) or walk (16 levels, both layouts); with hit records: 16 levels, both layouts, with and without the walk; the LDS
 // copy of the top levels (experiment X1).
@@ -818,6 +878,14 @@ const void* render_persistent_fn(const RenderBuild& b) {
     if (!image) {
         if (b.foreign != 0 || b.hot) return nullptr;
         return b.svo == VX_SVO_ESVO ? VX_K(VX_SVO_ESVO, true, true) : (b.svo == VX_SVO_ESVO_BIG ? VX_K(VX_SVO_ESVO_BIG, true, true) : (b.svo == VX_SVO_CSVO ? VX_K(VX_SVO_CSVO, true, true) : nullptr));
+    }
+    if (b.plain) {  // a whole frame (vxk::plain_frame): the four image-only builds on a byte-offset image
+        if (wide || b.hits || b.hot) return nullptr;
+        if (b.foreign == 0 && b.levels == 16) return VX_K(VX_SVO_IMAGE, false, false, 0, 16, false, true);
+        if (b.foreign == 0 && b.levels == kLdsLevels) return VX_K(VX_SVO_IMAGE, false, false, 0, kLdsLevels, false, true);
+        if (b.foreign == kForeignRerun && b.levels == kLdsLevels) return VX_K(VX_SVO_IMAGE, false, false, kForeignRerun, kLdsLevels, false, true);
+        if (b.foreign == VX_SVO_CSVO && b.levels == 16) return VX_K(VX_SVO_IMAGE, false, false, VX_SVO_CSVO, 16, false, true);
+        return nullptr;
     }
     if (b.hot) return (!wide && !b.hits && b.foreign == 0 && b.levels == kLdsLevels) ? VX_K(VX_SVO_IMAGE, false, false, 0, kLdsLevels, true) : nullptr;
     if (b.hits) {

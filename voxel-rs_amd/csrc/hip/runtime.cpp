@@ -247,15 +247,9 @@ int launch_render(vx_context* ctx, const RenderParams& p, float* out, vx_hit* hi
         // 13 three-word levels where they suffice and no walk wants the room below the leaves; 16 (16-bit third plane) else
         build.levels = !imaged ? kLdsLevels : ((HITS || wide || depth > uint32_t(kLdsLevels) || (csvo && !rerun)) ? 16 : kLdsLevels);
         build.hot = imaged && ctx->hot_levels && !HITS && !wide && !csvo && build.levels == kLdsLevels;
-        const void* fn = vxk::render_persistent_fn(build);
+        const void* fn = vxk::render_persistent_fn(build);  // (the general build: a whole frame's is chosen below, when the launch is known)
         if (!fn) return fail(VX_ERR_STATE, "no render kernel for this world (library built without it)");
         const size_t wave_lds = vxk::render_persistent_lds(build);
-        int& per_cu = ctx->persistent_blocks[fn];
-        if (per_cu == 0) {
-            int n = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 64, wave_lds) != hipSuccess || n <= 0) n = 8;
-            per_cu = n;
-        }
         PersistentArgs a;
         // (`tickets` counts this stream's launches: its sets of dispensers take turns)
         a.work_counter = work_counter + size_t(tickets & 1u) * (kQueues * kQueueStride);
@@ -329,6 +323,19 @@ int launch_render(vx_context* ctx, const RenderParams& p, float* out, vx_hit* hi
         a.stripe_shift = 0xffffffffu;
         for (uint32_t b = 0; b < 32u; ++b)
             if (a.stripe == (1u << b)) a.stripe_shift = b;
+        // A whole frame (vxk::plain_frame: what a game's frames in flight are) runs the build that has the launch's seven constants as literals
+        // (VX_PLAIN_FRAME=0: never) -- there is one for every image-only kernel on a byte-offset image
+        if (ctx->plain_frame && imaged && !wide && !build.hits && !build.hot && vxk::plain_frame(p, a, out)) {
+            build.plain = true;
+            fn = vxk::render_persistent_fn(build);
+            if (!fn) return fail(VX_ERR_STATE, "no whole-frame render kernel for this world (library built without it)");
+        }
+        int& per_cu = ctx->persistent_blocks[fn];
+        if (per_cu == 0) {
+            int n = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 64, wave_lds) != hipSuccess || n <= 0) n = 8;
+            per_cu = n;
+        }
         // Persistent waves per CU: all that fit -- the stacks fill a CU's LDS to the last hundred bytes. A context that gathers its tiles over
         // RCCL leaves `comm_headroom` of them out: LDS of every CU stays free, in one piece, for the communication kernels' workgroups, which
         // otherwise find room only when a whole frame has drained.
@@ -654,8 +661,8 @@ int vx_create(int svo_type, size_t capacity_bytes, int device, vx_context** out)
     CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_excursions), 8 * sizeof(unsigned long long)));
     CREATE_TRY(hipMemset(c->d_excursions, 0, 8 * sizeof(unsigned long long)));
     {
-        // The environment knobs of the product build (eleven; none of them changes a pixel): which kernel, how many frames in flight, the image on /
-        // off / wide / capped / its first buffer, where a CSVO world's inside-voxel rays go, the LDS copy of the top levels, the wave slots left to a communicator,
+        // The environment knobs of the product build (twelve; none of them changes a pixel): which kernel, how many frames in flight, the image on /
+        // off / wide / capped / its first buffer, where a CSVO world's inside-voxel rays go, the LDS copy of the top levels, the whole-frame build, the wave slots left to a communicator,
         // the lockstep threshold, how the tiles are numbered.
         if (const char* e = std::getenv("VX_RENDER_KERNEL")) c->kernel_version = std::atoi(e) == 1 ? 1 : 2;
         if (const char* e = std::getenv("VX_FRAMES_IN_FLIGHT")) c->frames_in_flight = std::atoi(e);
@@ -664,6 +671,7 @@ int vx_create(int svo_type, size_t capacity_bytes, int device, vx_context** out)
         if (const char* e = std::getenv("VX_TRAVERSAL_IMAGE")) c->image_enabled = std::atoi(e) != 0;
         if (const char* e = std::getenv("VX_FOREIGN_RERUN")) c->foreign_rerun = std::atoi(e) != 0 ? 1 : 0;
         if (const char* e = std::getenv("VX_HOT_LEVELS")) c->hot_levels = std::atoi(e) != 0;
+        if (const char* e = std::getenv("VX_PLAIN_FRAME")) c->plain_frame = std::atoi(e) != 0;
         if (const char* e = std::getenv("VX_IMAGE_CAP_BYTES")) c->image_cap_bytes = size_t(std::strtoull(e, nullptr, 10));
         // (tests: a first buffer of a few KB makes a small streamed world's image outgrow it again and again -- the carry-over on the device, commit_now)
         if (const char* e = std::getenv("VX_IMAGE_FIRST_BYTES")) c->image_first_bytes = std::max<size_t>(4096, size_t(std::strtoull(e, nullptr, 10)));
@@ -1555,7 +1563,7 @@ int vx_debug_knobs(const vx_context* ctx, uint32_t out[8]) {
     if (!ctx || !out) return fail(VX_ERR_INVALID_ARGUMENT, "debug_knobs: null argument");
     VX_LOCK(const_cast<vx_context*>(ctx));
     out[0] = ctx->refill_min; out[1] = ctx->service_min; out[2] = uint32_t(ctx->waves_per_cu_cap); out[3] = uint32_t(ctx->queue_stripe);
-    out[4] = uint32_t(ctx->tile_strip); out[5] = ctx->hot_first ? 1u : 0u; out[6] = uint32_t(ctx->comm_headroom); out[7] = vxk::timeline_build() ? 1u : 0u;
+    out[4] = uint32_t(ctx->tile_strip); out[5] = ctx->hot_first ? 1u : 0u; out[6] = uint32_t(ctx->comm_headroom); out[7] = (vxk::timeline_build() ? 1u : 0u) | (ctx->plain_frame ? 2u : 0u);
     return VX_OK;
 }
 

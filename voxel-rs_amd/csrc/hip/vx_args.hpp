@@ -174,6 +174,14 @@ struct PersistentArgs {
     unsigned long long* excursions;  // counted on request only (vx_excursion_counters), else null: [0] rays that walked inside a voxel on the world's bytes, [1] of which were given up and run on the bytes, [2] service phases that ran such walks, [3] loop iterations made on the bytes
 };
 
+// The whole-frame builds of render_persistent (its PLAIN flag; the image-only kernels on a byte-offset image) have seven launch constants fixed
+// at compile time, and what tests them gone from their service phases: a whole image (no tile list: no padding pixels, no list index, no
+// tile_order), RGBA32F rows bottom-up, a target, tickets in the order of their numbers, no cost notes, no excursion counters, an affine view (no
+// perspective divide). This is the launch they may serve -- every condition is needed: launch_render takes the general build otherwise.
+VX_HOST_DEVICE inline bool plain_frame(const vxd::RenderParams& p, const PersistentArgs& a, const void* out) {
+    return p.tile_count == 1u && p.rgba8 == 0u && out != nullptr && a.order == nullptr && a.cost_cur == nullptr && a.excursions == nullptr && p.affine_view != 0u;
+}
+
 // Images of CSVO worlds: what a wave cannot finish on the image goes on a list of its own and is run on the world's own bytes once the
 // tile queue is empty and the wave's rays are done (a second phase of the same kernel, not a second kernel: its registers overlay the
 // first phase's, and a frame stays one command).

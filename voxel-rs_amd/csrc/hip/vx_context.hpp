@@ -136,6 +136,7 @@ struct vx_context {
     bool hot_levels = false;      // VX_HOT_LEVELS=1 (experiment X1): the image's top two levels served from an LDS copy (ESVO worlds of at most 13 levels, image-only renders)
     int foreign_rerun = -1;       // VX_FOREIGN_RERUN=0: image-only renders of a CSVO world never list their inside-voxel rays for the bytes (kForeignRerun)
                                   // but walk them in the render loop; default: worlds of at most 12 levels list them
+    bool plain_frame = true;      // VX_PLAIN_FRAME=0: a whole frame runs the general build of the render kernel too (A/B; vxk::plain_frame)
     bool big = false;             // an ESVO world buffer of 4 GiB and more: kernels on its own bytes use 64-bit addresses (VX_SVO_ESVO_BIG)
     bool image_enabled = true;  // VX_TRAVERSAL_IMAGE=0: traverse the world's own bytes
     bool image_ok = false;

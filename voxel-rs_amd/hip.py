@@ -1271,7 +1271,9 @@ class Svo:
         """vx_debug_knobs: the scheduling knobs the context runs with."""
         out = (_u32 * 8)()
         _check(lib().vx_debug_knobs(self._h, C.byref(out)))
-        return dict(zip(("refill_min", "service_min", "waves_per_cu", "queue_stripe", "tile_strip", "hot_first", "comm_headroom", "measurement_build"), [int(v) for v in out]))
+        v = [int(x) for x in out]
+        v[7:] = [v[7] & 1, (v[7] >> 1) & 1]  # the last word: the measurement build | the whole-frame build in use << 1
+        return dict(zip(("refill_min", "service_min", "waves_per_cu", "queue_stripe", "tile_strip", "hot_first", "comm_headroom", "measurement_build", "plain_frame"), v))
 
     def image_info(self):
         out = (_u64 * 4)()

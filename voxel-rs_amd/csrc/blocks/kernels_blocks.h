@@ -1,6 +1,4 @@
-// What blocks_runtime.cpp knows of the block lookup kernels (kernels_blocks.hip), of the scans along an axis (kernels_scan.hip) and of the
-// list of a box's blocks (kernels_list.hip), of what a batch of float boxes holds (kernels_boxes.hip), of a batch of float boxes moved through the world (kernels_move.hip), of the floods around a batch of positions
-// (kernels_flood.hip), of the light levels of a batch of boxes (kernels_light.hip) and of the walks of ground agents (kernels_walk.hip).
+// What blocks_runtime.cpp knows of the kernels of csrc/blocks (kernels_*.hip): one launcher a kernel, with what it asks of its arguments.
 #pragma once
 
 #include <hip/hip_runtime_api.h>

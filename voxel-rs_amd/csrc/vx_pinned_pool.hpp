@@ -1,4 +1,4 @@
-// Pinned scratch for the synchronous, host-memory calls of the modules beside csrc/hip (csrc/physics, csrc/raycast, csrc/trace): host records travel
+// Pinned scratch for the synchronous, host-memory calls of the modules beside csrc/hip (csrc/physics, csrc/raycast, csrc/trace, csrc/blocks): host records travel
 // through pinned memory the device sees, which the kernel reads and writes directly -- no copy commands, one launch, one wait
 // (vx_raycast in runtime.cpp: a synchronous call costs its round trips). vx_context cannot grow, so the scratch lives here: one grow-only pool
 // per device, shared by that device's contexts and by the modules, whose mutex a host-memory call holds from its copy in to its copy out.
@@ -48,5 +48,21 @@ inline int pinned_pool_reserve(PinnedPool& p, size_t need) {
     p.bytes = cap;
     return VX_OK;
 }
+
+// A host-memory call's hold on the pool of its context's device, created under the context's lock (VX_LOCK: the context first, then the
+// pool) and kept from the copy in to the copy out: reserve, fill host(), launch on dev() -- the device's view of the same bytes --, wait,
+// read host(). A further reserve may move the pool: host() and dev() are asked for again after it, and nothing of the old bytes is kept.
+class PinnedScratch {
+    const vx_context* ctx;
+    PinnedPool& pool;
+    std::lock_guard<std::mutex> lock;
+
+public:
+    explicit PinnedScratch(const vx_context* c) : ctx(c), pool(pinned_pool_of(c->device)), lock(pool.mutex) {}
+    int reserve(size_t bytes) { return pinned_pool_reserve(pool, bytes); }
+    uint8_t* host() const { return pool.host; }
+    uint8_t* dev() const { return pool.dev; }
+    int wait() { HIP_TRY(hipStreamSynchronize(ctx->stream)); return VX_OK; }  // everything queued on the context's stream is through
+};
 
 }  // namespace vxrt

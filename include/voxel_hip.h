@@ -292,6 +292,37 @@ typedef struct vx_walk_info {
     uint32_t _pad;           /* written 0 */
 } vx_walk_info;
 
+#define VX_LABEL_MAX_PIECES 250u
+#define VX_LABEL_MAX_STEPS  4096u
+#define VX_LABEL_AIR   0x00u   /* not solid */
+#define VX_LABEL_MORE  0xFEu   /* solid, neither held nor one of the labelled pieces */
+#define VX_LABEL_HELD  0xFFu   /* solid, connected to an anchor face through solid cells of the box */
+#define VX_LABEL_ALL_FACES 0x3Fu
+#define VX_LABEL_CUT   1u      /* vx_label_info.flags: the step budget ran out */
+/* What every query of a vx_label_boxes call shares; 32 bytes; read on the host during the call. */
+typedef struct vx_label_shape {
+    uint32_t size[3];        /* the box of each query, 1..32 an axis */
+    uint32_t anchor_faces;   /* bits 0..5, numbered like vx_flood_info.faces (-x, +x, -y, +y, -z, +z): a solid cell on such a face of the box
+                                is held */
+    uint32_t max_pieces;     /* 0..VX_LABEL_MAX_PIECES */
+    uint32_t max_steps;      /* 0..VX_LABEL_MAX_STEPS: the budget of all floods of a query together */
+    uint32_t pass_value;     /* 0, or a BlockId that counts as air (vx_flood_shape's) */
+    uint32_t flags;          /* 0 */
+} vx_label_shape;
+/* One loose piece of a box (vx_label_boxes); 16 bytes, one 16-byte store. */
+typedef struct vx_label_piece {
+    uint32_t cells;          /* 0: no such piece (then the whole record is 0) */
+    uint32_t lo, hi;         /* the piece's bounds inside the box, rx | ry << 8 | rz << 16, both inclusive */
+    uint32_t where;          /* its first cell, rx | ry << 8 | rz << 16, | faces << 24: bit f set when a cell of the piece lies on face f of
+                                the box */
+} vx_label_piece;
+/* What the solid cells of a box fall into (vx_label_boxes); 32 bytes, two 16-byte stores. */
+typedef struct vx_label_info {
+    uint32_t solid, held, pieces, loose, more, steps, faces, flags;   /* cell counts: solid == held + loose + more; pieces: the labelled
+                                pieces, loose their cells; steps: the budget used; faces: bit f set when a solid cell lies on face f of the
+                                box; flags: 0 or VX_LABEL_CUT */
+} vx_label_info;
+
 /* Optional per-pixel record of what trace_ray saw (world.glsl:27-90) -- the "hit position, depth" outputs
  * used for parity checks; not part of the reference's surface. */
 typedef struct vx_hit {
@@ -761,6 +792,48 @@ int vx_light_boxes(vx_context* ctx, const void* lo, uint32_t lo_stride, uint32_t
  * 16777216 bytes; a misaligned device output. count == 0: VX_OK (nothing is read or written). Before the first commit: VX_ERR_STATE. */
 int vx_walk_points(vx_context* ctx, const void* pos, uint32_t pos_stride, const void* goal, uint32_t goal_stride, uint32_t count,
                    const vx_walk_shape* shape, int memory, uint8_t* fields, uint32_t field_stride, uint32_t* paths, vx_walk_info* info);
+/* The loose pieces of the blocks in each of `count` boxes of the world the device holds: "a block was removed, so what no longer hangs on
+ * anything?" -- after an explosion, a felled tree or a mined pillar, the connected pieces of solid blocks of a neighbourhood that the rest
+ * of the world does not hold, each with its size and bounds, to fall or to become debris entities. The reference would loop get_block
+ * (gameplay.rs:161-201) over the neighbourhood and label components on the host. Everything is integer and exact.
+ * Boxes. Box k is [lo_k, lo_k + size): lo_k an int32[3] read at lo + k * lo_stride under vx_light_boxes' rules (4-byte aligned, the stride a
+ * multiple of 4 and at least 12), kept modulo 2^32: the box may be negative or overhang the world.
+ * Solid. A cell is solid when vx_block_points' value at its centre is non-zero and differs from a non-zero pass_value (the cells
+ * vx_flood_points does not pass). Outside the world is air; a LOD voxel makes each of its fine voxels solid. Cells outside the box do not
+ * exist.
+ * Connectivity is 6-connected through solid cells of the box: contact along an edge or at a corner does not connect.
+ * Floods and the budget. A flood starts from a set of seed cells; its layer k holds the cells at breadth-first distance k from the seeds
+ * through solid cells that are not yet settled, and its depth is the largest k with a non-empty layer. `used` starts at 0. A flood is
+ * complete when used + depth <= max_steps, and then used += depth. Otherwise it is cut: used = max_steps, VX_LABEL_CUT is set, and no further
+ * flood is run.
+ * Held. The first flood's seeds are the solid cells on the faces of the box that anchor_faces names. Its cells are VX_LABEL_HELD and
+ * settled. If it is cut, the layers the budget still covered stay VX_LABEL_HELD: each of those cells really is connected to an anchor.
+ * Pieces. While fewer than max_pieces pieces are labelled, nothing was cut and an unsettled solid cell exists: the seed is the unsettled
+ * solid cell that comes first in the field's order (least rz, then ry, then rx); the flood from it, when complete, gives its cells the next
+ * label -- 1, 2, ... -- settles them and writes the piece's record; when cut, none of its cells are labelled. Every solid cell still
+ * unsettled at the end is VX_LABEL_MORE.
+ * The record. solid, held, loose and more are cell counts, loose of the cells with labels 1..pieces: solid == held + loose + more. steps is
+ * `used`; faces has bit f set when any solid cell lies on face f; flags is 0 or VX_LABEL_CUT. With max_pieces == 0 the call is the cheap
+ * "does anything hang loose, and how much": `more` holds the answer.
+ * Outputs. At least one of fields, pieces and info is given. Query k's field is a byte a cell in vx_read_region's layout (x fastest) at
+ * fields + k * field_stride; field_stride follows vx_flood_points' rule (0: the voxel count rounded up to 16, else a multiple of 16 and at
+ * least the voxel count); the bytes from the voxel count up to its multiple of 16 are written VX_LABEL_AIR, bytes beyond are not touched.
+ * Query k's piece records are max_pieces records at pieces + k * max_pieces; those of pieces that do not exist are written all 0. `pieces`
+ * together with max_pieces == 0 is an error.
+ * One workgroup of four waves a query, one launch: the box's solid cells as rows of 32 bits (each brick of 8 x 8 x 8 voxels entered once), a
+ * flood step a handful of shifts and ORs a row; no workgroup waits for another.
+ * Memory kinds, ordering and fences are vx_flood_points'. VX_MEM_HOST: synchronous, through pinned memory; one launch, one wait.
+ * VX_MEM_DEVICE (fields, pieces and info aligned to 16 bytes): enqueued on the context's stream, ordered behind the commits made so far and
+ * earlier batch calls; later commits wait for it; the fence is vx_sync. `shape` itself is read during the call.
+ * VX_ERR_INVALID_ARGUMENT (its message names the field; nothing is written): a null ctx; an unknown memory kind; with count > 0: a null
+ * shape or lo; fields, pieces and info all null; a stride or an alignment that breaks the rules above; a size component of 0 or above 32; an
+ * anchor_faces bit above bit 5; max_pieces > VX_LABEL_MAX_PIECES; max_steps > VX_LABEL_MAX_STEPS; flags != 0; pieces with max_pieces == 0;
+ * a field_stride that breaks the rule; count > 1048576 (2^20) -- not the other calls' 2^24: a query may run thousands of steps, and the
+ * launch must end in bounded time --; count * field_stride or count * max_pieces * 16 above 16777216 (2^24) bytes; a misaligned device
+ * output; an output whose bytes, from its first to its last, overlap those of lo or of another output. count == 0: VX_OK (nothing is read
+ * or written). Before the first commit: VX_ERR_STATE. */
+int vx_label_boxes(vx_context* ctx, const void* lo, uint32_t lo_stride, uint32_t count, const vx_label_shape* shape, int memory,
+                   uint8_t* fields, uint32_t field_stride, vx_label_piece* pieces, vx_label_info* info);
 /* Physics::step_many (src/systems/physics.rs:122-136) `steps` times over `count` entities in ONE kernel launch, against the world as last
  * committed: per step and entity the AABB's fan of axis-parallel picker rays (Aabb::generate_picker_tasks, svo_picker.rs:183-243: max_dst
  * 10), folded into six contact distances (parse_picker_results, svo_picker.rs:245-299), then Physics::update_entity and

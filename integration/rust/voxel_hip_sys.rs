@@ -333,6 +333,54 @@ pub const VX_WALK_STOP_AT_GOAL: u32 = 0x1;
 /// no cell, no step count: `vx_walk_info::start_ry`, `goal_ry`, `path_steps`, and a path's entries beyond its end
 pub const VX_WALK_NONE: u32 = u32::MAX;
 
+/// What every query of a `vx_label_boxes` call shares: the box of each query (1..=32 cells an axis), the faces of the box (bits 0..=5: -x, +x,
+/// -y, +y, -z, +z) on which a solid cell is held, the most pieces to label (0..=VX_LABEL_MAX_PIECES), the step budget of all floods of a query
+/// together (0..=VX_LABEL_MAX_STEPS), a block id that counts as air (0: none), and flags (0).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct vx_label_shape {
+    pub size: [u32; 3],
+    pub anchor_faces: u32,
+    pub max_pieces: u32,
+    pub max_steps: u32,
+    pub pass_value: u32,
+    pub flags: u32,
+}
+/// One loose piece of a box (`vx_label_boxes`): its cells (0: no such piece, the whole record is 0), its bounds inside the box as
+/// rx | ry << 8 | rz << 16 (both inclusive), and its first cell in the same form | faces << 24 (bit f: a cell of it lies on face f of the box).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct vx_label_piece {
+    pub cells: u32,
+    pub lo: u32,
+    pub hi: u32,
+    pub r#where: u32,
+}
+/// What the solid cells of a box fall into (`vx_label_boxes`): `solid == held + loose + more`; `pieces` labelled pieces of `loose` cells; the
+/// budget used; the faces of the box a solid cell lies on; 0 or VX_LABEL_CUT.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct vx_label_info {
+    pub solid: u32,
+    pub held: u32,
+    pub pieces: u32,
+    pub loose: u32,
+    pub more: u32,
+    pub steps: u32,
+    pub faces: u32,
+    pub flags: u32,
+}
+/// the header's VX_LABEL_* (250 and 4,096, written in hexadecimal here)
+pub const VX_LABEL_MAX_PIECES: u32 = 0xFA;
+pub const VX_LABEL_MAX_STEPS: u32 = 0x1000;
+/// a field's bytes: not solid; 1..=pieces: the piece's label; solid but neither held nor labelled; held
+pub const VX_LABEL_AIR: u8 = 0x00;
+pub const VX_LABEL_MORE: u8 = 0xFE;
+pub const VX_LABEL_HELD: u8 = 0xFF;
+pub const VX_LABEL_ALL_FACES: u32 = 0x3F;
+/// `vx_label_info::flags`: the step budget ran out
+pub const VX_LABEL_CUT: u32 = 0x1;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct vx_stats {
@@ -372,6 +420,9 @@ const _: () = assert!(std::mem::size_of::<vx_light_shape>() == 32);
 const _: () = assert!(std::mem::size_of::<vx_light_info>() == 16);
 const _: () = assert!(std::mem::size_of::<vx_walk_shape>() == 52);
 const _: () = assert!(std::mem::size_of::<vx_walk_info>() == 32);
+const _: () = assert!(std::mem::size_of::<vx_label_shape>() == 32);
+const _: () = assert!(std::mem::size_of::<vx_label_piece>() == 16);
+const _: () = assert!(std::mem::size_of::<vx_label_info>() == 32);
 const _: () = assert!(std::mem::size_of::<MaterialInstance>() == 32); // svo_registry.rs:29-40 is #[repr(C)]
 const _: () = assert!(std::mem::size_of::<PickerTask>() == 48 && std::mem::size_of::<PickerResult>() == 48); // svo_picker.rs:13-32
 
@@ -450,6 +501,12 @@ extern "C" {
     /// VX_MEM_HOST / VX_MEM_DEVICE (all three aligned to 16)
     pub fn vx_walk_points(ctx: *mut vx_context, pos: *const c_void, pos_stride: u32, goal: *const c_void, goal_stride: u32, count: u32,
                           shape: *const vx_walk_shape, memory: c_int, fields: *mut u8, field_stride: u32, paths: *mut u32, info: *mut vx_walk_info) -> c_int;
+    /// the loose pieces of the solid cells of the boxes [lo_k, lo_k + shape.size), lo_k an int32[3] at lo + k * lo_stride: held from the anchor
+    /// faces, then labelled 1, 2, ... in the field's order within the step budget; box k's field (a byte a cell, x fastest) at fields + k *
+    /// field_stride (a multiple of 16, 0 = the voxel count rounded up to 16), its shape.max_pieces piece records at pieces + k *
+    /// shape.max_pieces, its record at info[k]; any output may be null, not all; `memory`: VX_MEM_HOST / VX_MEM_DEVICE (all three aligned to 16)
+    pub fn vx_label_boxes(ctx: *mut vx_context, lo: *const c_void, lo_stride: u32, count: u32, shape: *const vx_label_shape, memory: c_int,
+                          fields: *mut u8, field_stride: u32, pieces: *mut vx_label_piece, info: *mut vx_label_info) -> c_int;
     /// Physics::step_many (physics.rs:122-136) `steps` times for `count` entities in one launch; `memory`: VX_MEM_HOST / VX_MEM_DEVICE
     pub fn vx_physics_step(ctx: *mut vx_context, entities: *mut vx_entity, count: u32, memory: c_int, delta_time: f32, steps: u32,
                            contacts: *mut vx_aabb_result) -> c_int;

@@ -1,4 +1,4 @@
-// libvoxelhip.so, the block entry points of include/voxel_hip.h (vx_block_points to vx_walk_points): each one's argument checks (the rules of
+// libvoxelhip.so, the block entry points of include/voxel_hip.h (vx_block_points to vx_label_boxes): each one's argument checks (the rules of
 // the vx_*.hpp beside this file), the launches of its kernel (kernels_blocks.h), and for a host-memory call the pinned scratch the kernel
 // reads and writes through (csrc/vx_pinned_pool.hpp), laid out and packed by vx_block_scratch.hpp: lay out, pack, launch, wait, copy out.
 // A further translation unit on the context, like raycast_runtime.cpp: what it needs of the context is vx_context.hpp's (runtime.cpp).
@@ -430,6 +430,38 @@ int vx_walk_points(vx_context* ctx, const void* pos, uint32_t pos_stride, const 
     if (int rc = s.wait()) return rc;  // synchronous, like vx_flood_points' host-memory call
     if (info) std::memcpy(info, s.host() + at_info, info_bytes);
     if (paths) std::memcpy(paths, s.host() + at_paths, path_bytes);
+    if (fields) vxb::spread_fields(fields, stride, s.host() + at_fields, packed, count);
+    return VX_OK;
+}
+
+int vx_label_boxes(vx_context* ctx, const void* lo, uint32_t lo_stride, uint32_t count, const vx_label_shape* shape, int memory, uint8_t* fields,
+                   uint32_t field_stride, vx_label_piece* pieces, vx_label_info* info) {
+    static_assert(sizeof(vx_label_info) == 32 && sizeof(vx_label_piece) == 16 && sizeof(vx_label_shape) == 32, "the ABI's record sizes");
+    const char* refused = vxb::check_label(lo, lo_stride, count, shape, fields, field_stride, pieces, info);
+    if (int rc = enter("label_boxes", memory, refused, count && memory == VX_MEM_DEVICE, {{fields, 16, "fields"}, {pieces, 16, "pieces"}, {info, 16, "info"}}, ctx)) return rc;
+    VX_LOCK(ctx);
+    if (count == 0) return VX_OK;
+    const uint32_t packed = vxb::flood_round16(vxb::label_voxels(*shape)), stride = field_stride ? field_stride : packed;
+    const OnBytes w(ctx);
+
+    if (memory == VX_MEM_DEVICE) return enqueued(ctx, vxk::launch_label_boxes(w.variant, ctx->stream, w.scene, lo, lo_stride, count, *shape, fields, stride, pieces, info));
+
+    // the boxes packed at stride 12 | the records | the piece records | the fields, each the voxel count rounded up to 16: the bytes a query
+    // writes, which go to the caller's stride from there (every part behind the boxes at a multiple of 16)
+    vxb::ScratchLayout lay;
+    const size_t at_lo = lay.take(vxb::packed3_bytes(lo, lo_stride, count));
+    const size_t info_bytes = info ? size_t(count) * sizeof(vx_label_info) : 0, at_info = lay.take(info_bytes, 16);
+    const size_t piece_bytes = pieces ? size_t(count) * shape->max_pieces * sizeof(vx_label_piece) : 0, at_pieces = lay.take(piece_bytes, 16);
+    const size_t at_fields = lay.take(fields ? size_t(count) * packed : 0, 16);
+    vxrt::PinnedScratch s(ctx);
+    if (int rc = s.reserve(lay.end)) return rc;
+    vxb::pack3(s.host() + at_lo, lo, lo_stride, count);
+    HIP_TRY(vxk::launch_label_boxes(w.variant, ctx->stream, w.scene, s.dev() + at_lo, 12, count, *shape, fields ? s.dev() + at_fields : nullptr, packed,
+                                    pieces ? reinterpret_cast<vx_label_piece*>(s.dev() + at_pieces) : nullptr,
+                                    info ? reinterpret_cast<vx_label_info*>(s.dev() + at_info) : nullptr));
+    if (int rc = s.wait()) return rc;  // synchronous, like vx_light_boxes' host-memory call
+    if (info) std::memcpy(info, s.host() + at_info, info_bytes);
+    if (pieces) std::memcpy(pieces, s.host() + at_pieces, piece_bytes);
     if (fields) vxb::spread_fields(fields, stride, s.host() + at_fields, packed, count);
     return VX_OK;
 }

@@ -7,6 +7,7 @@
 #include "vx_blocks.hpp"
 #include "vx_boxes.hpp"
 #include "vx_flood.hpp"
+#include "vx_label.hpp"
 #include "vx_light.hpp"
 #include "vx_list.hpp"
 #include "vx_move.hpp"
@@ -80,5 +81,13 @@ hipError_t launch_light_boxes(int svo, hipStream_t stream, const vxd::SceneArgs&
 // bytes, 16-byte aligned. Device-visible memory that overlaps no input.
 hipError_t launch_walk_points(int svo, hipStream_t stream, const vxd::SceneArgs& sc, const void* pos, uint32_t pos_stride, const void* goal, uint32_t goal_stride,
                               uint32_t count, const vx_walk_shape& shape, uint8_t* fields, uint32_t field_stride, uint32_t* paths, vx_walk_info* info);
+
+// `count` (1..2^20) workgroups of 256 threads, one box a workgroup: an int32[3] at lo + i * lo_stride (4-byte aligned, the stride a multiple of
+// 4 and at least 12); shape: within vxb::check_label's rules (refused here too: the kernel indexes LDS by its size and ends its loops by
+// max_steps and max_pieces); fields as launch_flood_points'; pieces (may be null; not with shape.max_pieces == 0): 16-byte aligned, box i's
+// shape.max_pieces records at pieces + i * shape.max_pieces, all of them written; info (may be null, not all three): `count` records of 32
+// bytes, 16-byte aligned. Device-visible memory that overlaps no input.
+hipError_t launch_label_boxes(int svo, hipStream_t stream, const vxd::SceneArgs& sc, const void* lo, uint32_t lo_stride, uint32_t count, const vx_label_shape& shape,
+                              uint8_t* fields, uint32_t field_stride, vx_label_piece* pieces, vx_label_info* info);
 
 }  // namespace vxk

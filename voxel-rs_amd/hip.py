@@ -69,6 +69,13 @@ WALK_INFO_DTYPE = np.dtype([("reached", "<u4"), ("farthest", "<u4"), ("faces", "
                             ("path_steps", "<u4"), ("_pad", "<u4")])
 VX_WALK_MAX_STEPS, VX_WALK_NO_POSITION, VX_WALK_UNREACHED, VX_WALK_NO_STAND = 250, 0xFD, 0xFE, 0xFF
 VX_WALK_STOP_AT_GOAL, VX_WALK_NONE = 1, 0xFFFFFFFF
+# vx_label_piece and vx_label_info (vx_label_boxes): a loose piece -- its cells, its bounds inside the box (rx | ry << 8 | rz << 16, inclusive), its
+# first cell | faces << 24 -- and what the solid cells of a box fall into: solid == held + loose + more. A field is one byte a cell:
+# VX_LABEL_AIR, the piece's label 1..pieces, VX_LABEL_MORE or VX_LABEL_HELD
+LABEL_PIECE_DTYPE = np.dtype([("cells", "<u4"), ("lo", "<u4"), ("hi", "<u4"), ("where", "<u4")])
+LABEL_INFO_DTYPE = np.dtype([("solid", "<u4"), ("held", "<u4"), ("pieces", "<u4"), ("loose", "<u4"), ("more", "<u4"), ("steps", "<u4"), ("faces", "<u4"),
+                             ("flags", "<u4")])
+VX_LABEL_MAX_PIECES, VX_LABEL_MAX_STEPS, VX_LABEL_AIR, VX_LABEL_MORE, VX_LABEL_HELD, VX_LABEL_ALL_FACES, VX_LABEL_CUT = 250, 4096, 0x00, 0xFE, 0xFF, 0x3F, 1
 VX_DIR_NEG_X, VX_DIR_POS_X, VX_DIR_NEG_Y, VX_DIR_POS_Y, VX_DIR_NEG_Z, VX_DIR_POS_Z = range(6)
 VX_SCAN_NONE = -0x80000000
 VX_SCAN_TO_EDGE = 0xFFFFFFFF
@@ -76,7 +83,7 @@ FACE_NORMALS = np.array([[-1, 0, 0], [1, 0, 0], [0, -1, 0], [0, 1, 0], [0, 0, -1
 assert HIT_DTYPE.itemsize == 48 and PICKER_TASK_DTYPE.itemsize == 48 and PICKER_RESULT_DTYPE.itemsize == 48 and FRAME_DTYPE.itemsize == 36
 assert ENTITY_DTYPE.itemsize == 64 and AABB_RESULT_DTYPE.itemsize == 24 and RAY_HIT_DTYPE.itemsize == 32 and SCAN_HIT_DTYPE.itemsize == 16
 assert BLOCK_AT_DTYPE.itemsize == 8 and BOX_HIT_DTYPE.itemsize == 32 and FLOOD_INFO_DTYPE.itemsize == 16 and LIGHT_INFO_DTYPE.itemsize == 16
-assert WALK_INFO_DTYPE.itemsize == 32 and MOVE_HIT_DTYPE.itemsize == 48
+assert WALK_INFO_DTYPE.itemsize == 32 and MOVE_HIT_DTYPE.itemsize == 48 and LABEL_PIECE_DTYPE.itemsize == 16 and LABEL_INFO_DTYPE.itemsize == 32
 
 COUNTER_FIELDS = ["rays", "iterations", "pushes", "leaf_tests", "leaf_tests_trilinear", "boundaries", "csvo_header_bytes", "csvo_pointer_bytes",
                   "pixels", "lit_pixels", "shadow_rays", "wave_steps", "services", "refills", "tail_wave_steps", "tail_iterations"]
@@ -129,6 +136,12 @@ class LightShape(C.Structure):
     _fields_ = [("size", C.c_uint32 * 3), ("flags", C.c_uint32), ("props", C.c_void_p), ("props_count", C.c_uint32)]
 
 
+class LabelShape(C.Structure):
+    """vx_label_shape"""
+    _fields_ = [("size", C.c_uint32 * 3), ("anchor_faces", C.c_uint32), ("max_pieces", C.c_uint32), ("max_steps", C.c_uint32), ("pass_value", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
 class Result(C.Structure):
     _fields_ = [("t", C.c_float), ("value", C.c_uint32), ("face_id", C.c_int32), ("pos", C.c_float * 3), ("uv", C.c_float * 2),
                 ("color", C.c_float * 4), ("lod", C.c_float), ("inside_voxel", C.c_int32)]
@@ -174,6 +187,7 @@ SYMBOLS = {
     "vx_flood_points": (_int, [_vp, _vp, _u32, _u32, C.POINTER(FloodShape), _int, _vp, _u32, _vp]),
     "vx_light_boxes": (_int, [_vp, _vp, _u32, _u32, C.POINTER(LightShape), _int, _vp, _u32, _vp]),
     "vx_walk_points": (_int, [_vp, _vp, _u32, _vp, _u32, _u32, C.POINTER(WalkShape), _int, _vp, _u32, _vp, _vp]),
+    "vx_label_boxes": (_int, [_vp, _vp, _u32, _u32, C.POINTER(LabelShape), _int, _vp, _u32, _vp, _vp]),
     "vx_physics_step": (_int, [_vp, _vp, _u32, _int, C.c_float, _u32, _vp]),
     "vx_debug_trace": (_int, [_vp, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.c_float, _int, C.POINTER(Result), _vp, _u32, C.POINTER(_u32)]),
     "vx_sync": (_int, [_vp]),
@@ -408,6 +422,21 @@ def walk_shape(size, seed_at=None, max_steps=VX_WALK_MAX_STEPS, pass_value=0, he
 def light_infos_to_numpy(infos):
     """A device record tensor of Svo.light_boxes as LIGHT_INFO_DTYPE records (copies to the host: synchronise first)."""
     return infos.cpu().numpy().view(np.uint8).reshape(-1).view(LIGHT_INFO_DTYPE)
+
+
+def label_pieces_to_numpy(pieces):
+    """A device piece tensor of Svo.label_boxes as LABEL_PIECE_DTYPE records [N, max_pieces] (copies to the host: synchronise first)."""
+    return pieces.cpu().numpy().view(np.uint8).reshape(pieces.shape[0], -1).view(LABEL_PIECE_DTYPE)
+
+
+def label_infos_to_numpy(infos):
+    """A device record tensor of Svo.label_boxes as LABEL_INFO_DTYPE records (copies to the host: synchronise first)."""
+    return infos.cpu().numpy().view(np.uint8).reshape(-1).view(LABEL_INFO_DTYPE)
+
+
+def label_shape(size, anchor_faces=VX_LABEL_ALL_FACES, max_pieces=VX_LABEL_MAX_PIECES, max_steps=VX_LABEL_MAX_STEPS, pass_value=0, flags=0):
+    """A vx_label_shape."""
+    return LabelShape((C.c_uint32 * 3)(*size), int(anchor_faces), int(max_pieces), int(max_steps), int(pass_value), int(flags))
 
 
 def light_shape(size, props, flags=0):
@@ -1120,6 +1149,74 @@ class Svo:
                                     int(field_stride), None if info is None else _vp(info.data_ptr())))
         del table  # (read during the call)
         return fields, info
+
+    # -- loose pieces (connected components over get_block, gameplay.rs:161-201, for a batch of boxes) -----------------------------------------------
+    def label_boxes(self, lo, size, anchor_faces=VX_LABEL_ALL_FACES, max_pieces=VX_LABEL_MAX_PIECES, max_steps=VX_LABEL_MAX_STEPS, pass_value=0, fields=None,
+                    pieces=None, info=None, field_stride=0):
+        """vx_label_boxes: the solid cells of the boxes [lo_k, lo_k + size) (1..32 cells an axis) that hang on nothing -- held from the faces
+        anchor_faces names, the loose pieces labelled 1, 2, ... in the field's order, the rest VX_LABEL_MORE. lo: as light_boxes takes it.
+        Returns (fields, pieces, info), each None when not asked for: fields -- uint8 [N, field_stride], of which the first size.x * size.y *
+        size.z bytes of a row are the box's cells, x fastest; field_stride 0: the voxel count rounded up to 16 --, pieces -- LABEL_PIECE_DTYPE
+        records [N, max_pieces] (none with max_pieces == 0) -- and info -- LABEL_INFO_DTYPE records. fields, pieces and info: None (or True)
+        for fresh memory, False for none, or the memory to write to.
+        Host (a NumPy array): synchronous.
+        Device (a torch CUDA tensor): returns after enqueueing, without synchronising -- pair with sync(); fields is a uint8 tensor, pieces an
+        int32 tensor of shape (N, max_pieces, 4) and info one of shape (N, 8) on lo's device (label_pieces_to_numpy, label_infos_to_numpy)."""
+        host = isinstance(lo, np.ndarray)
+        if len(lo.shape) != 2 or lo.shape[1] != 3:
+            raise TypeError("label_boxes: lo must have shape (N, 3)")
+        count = int(lo.shape[0])
+        if not host and not getattr(lo, "is_cuda", False):
+            raise TypeError("label_boxes: lo must be a NumPy array or a torch CUDA tensor")
+        shape = label_shape(size, anchor_faces, max_pieces, max_steps, pass_value)
+        voxels = int(shape.size[0]) * int(shape.size[1]) * int(shape.size[2])
+        stride = int(field_stride) if field_stride else (voxels + 15) // 16 * 16
+        fields = True if fields is None else (None if fields is False else fields)
+        pieces = (True if shape.max_pieces else None) if pieces is None else (None if pieces is False else pieces)
+        info = True if info is None else (None if info is False else info)
+        if host:
+            if lo.dtype != np.int32 or (count and (lo.strides[1] != 4 or lo.strides[0] % 4 or lo.strides[0] < 12)):
+                raise TypeError("label_boxes: lo must be int32 rows at a stride that is a multiple of 4 bytes and at least 12")
+            ptr, lo_stride = lo.ctypes.data, int(lo.strides[0]) if count else 12
+            if fields is True:
+                fields = np.zeros((count, stride), dtype=np.uint8)
+            elif fields is not None and (not isinstance(fields, np.ndarray) or fields.dtype != np.uint8 or fields.size < count * stride or not fields.flags.c_contiguous
+                                         or not fields.flags.writeable):
+                raise TypeError("label_boxes: fields must be a writeable C-contiguous uint8 array of at least N x field_stride bytes")
+            if pieces is True:
+                pieces = np.zeros((count, shape.max_pieces), dtype=LABEL_PIECE_DTYPE)
+            elif pieces is not None and (not isinstance(pieces, np.ndarray) or pieces.dtype != LABEL_PIECE_DTYPE or pieces.size != count * shape.max_pieces
+                                         or not pieces.flags.c_contiguous or not pieces.flags.writeable):
+                raise TypeError("label_boxes: pieces must be a writeable C-contiguous array of N x max_pieces hip.LABEL_PIECE_DTYPE records")
+            if info is True:
+                info = np.zeros(count, dtype=LABEL_INFO_DTYPE)
+            elif info is not None and (not isinstance(info, np.ndarray) or info.dtype != LABEL_INFO_DTYPE or info.size != count or not info.flags.c_contiguous
+                                       or not info.flags.writeable):
+                raise TypeError("label_boxes: info must be a writeable C-contiguous array of N hip.LABEL_INFO_DTYPE records")
+            _check(lib().vx_label_boxes(self._h, _vp(ptr), lo_stride, count, C.byref(shape), VX_MEM_HOST, None if fields is None else fields.ctypes.data_as(_vp),
+                                        int(field_stride), None if pieces is None else pieces.ctypes.data_as(_vp), None if info is None else info.ctypes.data_as(_vp)))
+            return fields, pieces, info
+        import torch
+
+        if lo.dtype != torch.int32 or (count and (lo.stride(1) != 1 or lo.stride(0) < 3)):
+            raise TypeError("label_boxes: lo must be int32 rows whose last axis is contiguous, at a stride of at least 3 elements")
+        ptr, lo_stride = lo.data_ptr(), 4 * int(lo.stride(0)) if count else 12
+        if fields is True:
+            fields = torch.empty((count, stride), dtype=torch.uint8, device=lo.device)
+        elif fields is not None and (not fields.is_cuda or not fields.is_contiguous() or fields.numel() * fields.element_size() < count * stride):
+            raise TypeError("label_boxes: fields must be a contiguous CUDA tensor of at least N x field_stride bytes")
+        if pieces is True:
+            pieces = torch.empty((count, shape.max_pieces, 4), dtype=torch.int32, device=lo.device)
+        elif pieces is not None and (not pieces.is_cuda or not pieces.is_contiguous()
+                                     or pieces.numel() * pieces.element_size() < count * shape.max_pieces * LABEL_PIECE_DTYPE.itemsize):
+            raise TypeError("label_boxes: pieces must be a contiguous CUDA tensor of at least N x max_pieces x 16 bytes")
+        if info is True:
+            info = torch.empty((count, 8), dtype=torch.int32, device=lo.device)
+        elif info is not None and (not info.is_cuda or not info.is_contiguous() or info.numel() * info.element_size() < count * LABEL_INFO_DTYPE.itemsize):
+            raise TypeError("label_boxes: info must be a contiguous CUDA tensor of at least N x 32 bytes")
+        _check(lib().vx_label_boxes(self._h, _vp(ptr), lo_stride, count, C.byref(shape), VX_MEM_DEVICE, None if fields is None else _vp(fields.data_ptr()),
+                                    int(field_stride), None if pieces is None else _vp(pieces.data_ptr()), None if info is None else _vp(info.data_ptr())))
+        return fields, pieces, info
 
     # -- walking distances and paths (a search over get_block, gameplay.rs:161-201, on the walking graph, for a batch) --------------------------------
     def walk_points(self, positions, size, goals=None, seed_at=None, max_steps=VX_WALK_MAX_STEPS, pass_value=0, height=2, climb=1, drop=3, path_capacity=0, flags=0,

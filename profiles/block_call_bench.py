@@ -11,7 +11,12 @@ the driver stops at the first child that fails. On a depth-9 heightfield, per ch
     the host clock around the call and the vx_sync behind it (profiles/boxes_bench.py's call_sync): REPS samples after WARMUP calls
 A row pools a build's samples over its rounds: median, p10, p90, and the median of each round. `inside_parent_band`: the branch's median lies
 within the parent's p10..p90 of that same run -- the margin is the parent's own spread, there is no other threshold. At 1 item every figure
-is the latency of one launch and one wait."""
+is the latency of one launch and one wait.
+
+    python profiles/block_call_bench.py --parent-tree DIR [--out profiles/block_call/binding.json]
+
+For a change to the Python binding instead: the parent's children run DIR/profiles/block_call_bench.py --case, a checkout of the commit to
+compare against, with the branch's libraries (or --parent-lib), so that the two sides differ only in voxel-rs_amd/hip.py."""
 import argparse
 import json
 import os
@@ -86,6 +91,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", action="store_true")
     ap.add_argument("--parent-lib")
+    ap.add_argument("--parent-tree")
     ap.add_argument("--branch-lib", default=str(ROOT / "voxel-rs_amd" / "lib"))
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--out", default=str(ROOT / "profiles" / "block_call" / "results.json"))
@@ -94,13 +100,15 @@ def main():
     if args.case:
         case()
         return 0
-    if not args.parent_lib:
-        ap.error("--parent-lib is required")
+    if not args.parent_lib and not args.parent_tree:
+        ap.error("--parent-lib or --parent-tree is required")
+    args.parent_lib = args.parent_lib or args.branch_lib  # (a tree alone: one build of the libraries under both)
     libs = {"parent": str(Path(args.parent_lib).resolve()), "branch": str(Path(args.branch_lib).resolve())}
+    scripts = {"parent": str(Path(args.parent_tree).resolve() / "profiles" / "block_call_bench.py") if args.parent_tree else __file__, "branch": __file__}
     samples = {}  # (call, memory, items) -> build -> one list a round
     for rnd in range(args.rounds):
         for build, lib in libs.items():
-            r = subprocess.run(["timeout", "-k", "10", str(args.timeout), sys.executable, __file__, "--case"], stdout=subprocess.PIPE, text=True,
+            r = subprocess.run(["timeout", "-k", "10", str(args.timeout), sys.executable, scripts[build], "--case"], stdout=subprocess.PIPE, text=True,
                                env=dict(os.environ, VX_LIB_DIR=lib))
             if r.returncode != 0:
                 print(f"round {rnd}, build {build} ended with status {r.returncode}: stopping", file=sys.stderr)
@@ -116,6 +124,7 @@ def main():
             row[build] = dict(stats([v for r in rounds for v in r]), round_medians=[stats(r)["median"] for r in rounds])
         row["branch_over_parent"] = round(row["branch"]["median"] / row["parent"]["median"], 3)
         row["inside_parent_band"] = row["parent"]["p10"] <= row["branch"]["median"] <= row["parent"]["p90"]
+        row["above_parent_band"] = row["branch"]["median"] > row["parent"]["p90"]  # (below the band is fine)
         print(json.dumps(row), flush=True)
         cases.append(row)
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)

@@ -335,44 +335,24 @@ def entities_to_rows(entities):
 def entity_positions(entities):
     """The positions inside vx_entity records as the origins of a ray batch (Svo.raycast_batch): an (N, 3) float32 view at a stride of 64
     bytes -- of a NumPy array of ENTITY_DTYPE, or of a contiguous torch tensor whose bytes are vx_entity records. No copy."""
-    if isinstance(entities, np.ndarray):
-        if entities.dtype != ENTITY_DTYPE:
-            raise TypeError("entity_positions: a host array must be of hip.ENTITY_DTYPE")
-        return entities.reshape(-1)["position"]
-    import torch
-
-    nbytes = entities.numel() * entities.element_size()
-    if nbytes % ENTITY_DTYPE.itemsize or not entities.is_contiguous():
-        raise TypeError("entity_positions: a device tensor must be contiguous and hold whole 64-byte vx_entity records")
-    return entities.reshape(-1).view(torch.uint8).view(torch.float32).view(-1, 16)[:, 0:3]
+    return _record_vectors("entity_positions", "vx_entity", entities, ENTITY_DTYPE, "position")[0]
 
 
 def entity_boxes(entities):
     """The boxes inside vx_entity records as the arguments of Svo.overlap_boxes: (origin, extents, offset) -- position, aabb_extents and
     aabb_offset as (N, 3) float32 views at a stride of 64 bytes, of a NumPy array of ENTITY_DTYPE or of a contiguous torch tensor whose
     bytes are vx_entity records. No copy: svo.overlap_boxes(*entity_boxes(e)) reads the records in place."""
-    if isinstance(entities, np.ndarray):
-        if entities.dtype != ENTITY_DTYPE:
-            raise TypeError("entity_boxes: a host array must be of hip.ENTITY_DTYPE")
-        e = entities.reshape(-1)
-        return e["position"], e["aabb_extents"], e["aabb_offset"]
-    import torch
-
-    nbytes = entities.numel() * entities.element_size()
-    if nbytes % ENTITY_DTYPE.itemsize or not entities.is_contiguous():
-        raise TypeError("entity_boxes: a device tensor must be contiguous and hold whole 64-byte vx_entity records")
-    f = entities.reshape(-1).view(torch.uint8).view(torch.float32).view(-1, 16)
-    return f[:, 0:3], f[:, 9:12], f[:, 6:9]
+    return _record_vectors("entity_boxes", "vx_entity", entities, ENTITY_DTYPE, "position", "aabb_extents", "aabb_offset")
 
 
 def box_hits_to_numpy(hits):
     """A device record tensor of Svo.overlap_boxes as BOX_HIT_DTYPE records (copies to the host: synchronise first)."""
-    return hits.cpu().numpy().view(np.uint8).reshape(-1).view(BOX_HIT_DTYPE)
+    return _to_numpy(hits, BOX_HIT_DTYPE)
 
 
 def move_hits_to_numpy(hits):
     """A device record tensor of Svo.move_boxes as MOVE_HIT_DTYPE records (copies to the host: synchronise first)."""
-    return hits.cpu().numpy().view(np.uint8).reshape(-1).view(MOVE_HIT_DTYPE)
+    return _to_numpy(hits, MOVE_HIT_DTYPE)
 
 
 def MOVE_SHAPE(scale=1.0, skin=2.0 ** -10, order=VX_MOVE_ORDER_YXZ, flags=0):
@@ -382,22 +362,12 @@ def MOVE_SHAPE(scale=1.0, skin=2.0 ** -10, order=VX_MOVE_ORDER_YXZ, flags=0):
 
 def entity_velocities(entities):
     """vx_entity.velocity as the `motion` of Svo.move_boxes: an (N, 3) float32 view at a stride of 64 bytes, of what entity_boxes takes."""
-    if isinstance(entities, np.ndarray):
-        if entities.dtype != ENTITY_DTYPE:
-            raise TypeError("entity_velocities: a host array must be of hip.ENTITY_DTYPE")
-        return entities.reshape(-1)["velocity"]
-    import torch
-
-    nbytes = entities.numel() * entities.element_size()
-    if nbytes % ENTITY_DTYPE.itemsize or not entities.is_contiguous():
-        raise TypeError("entity_velocities: a device tensor must be contiguous and hold whole 64-byte vx_entity records")
-    at = ENTITY_DTYPE.fields["velocity"][1] // 4
-    return entities.reshape(-1).view(torch.uint8).view(torch.float32).view(-1, 16)[:, at:at + 3]
+    return _record_vectors("entity_velocities", "vx_entity", entities, ENTITY_DTYPE, "velocity")[0]
 
 
 def flood_infos_to_numpy(infos):
     """A device record tensor of Svo.flood_points as FLOOD_INFO_DTYPE records (copies to the host: synchronise first)."""
-    return infos.cpu().numpy().view(np.uint8).reshape(-1).view(FLOOD_INFO_DTYPE)
+    return _to_numpy(infos, FLOOD_INFO_DTYPE)
 
 
 def flood_shape(size, seed_at=None, max_steps=VX_FLOOD_MAX_STEPS, pass_value=0, flags=0):
@@ -409,7 +379,7 @@ def flood_shape(size, seed_at=None, max_steps=VX_FLOOD_MAX_STEPS, pass_value=0, 
 
 def walk_infos_to_numpy(infos):
     """A device record tensor of Svo.walk_points as WALK_INFO_DTYPE records (copies to the host: synchronise first)."""
-    return infos.cpu().numpy().view(np.uint8).reshape(-1).view(WALK_INFO_DTYPE)
+    return _to_numpy(infos, WALK_INFO_DTYPE)
 
 
 def walk_shape(size, seed_at=None, max_steps=VX_WALK_MAX_STEPS, pass_value=0, height=2, climb=1, drop=3, path_capacity=0, flags=0):
@@ -421,17 +391,17 @@ def walk_shape(size, seed_at=None, max_steps=VX_WALK_MAX_STEPS, pass_value=0, he
 
 def light_infos_to_numpy(infos):
     """A device record tensor of Svo.light_boxes as LIGHT_INFO_DTYPE records (copies to the host: synchronise first)."""
-    return infos.cpu().numpy().view(np.uint8).reshape(-1).view(LIGHT_INFO_DTYPE)
+    return _to_numpy(infos, LIGHT_INFO_DTYPE)
 
 
 def label_pieces_to_numpy(pieces):
     """A device piece tensor of Svo.label_boxes as LABEL_PIECE_DTYPE records [N, max_pieces] (copies to the host: synchronise first)."""
-    return pieces.cpu().numpy().view(np.uint8).reshape(pieces.shape[0], -1).view(LABEL_PIECE_DTYPE)
+    return _to_numpy(pieces, LABEL_PIECE_DTYPE).reshape(pieces.shape[0], -1)
 
 
 def label_infos_to_numpy(infos):
     """A device record tensor of Svo.label_boxes as LABEL_INFO_DTYPE records (copies to the host: synchronise first)."""
-    return infos.cpu().numpy().view(np.uint8).reshape(-1).view(LABEL_INFO_DTYPE)
+    return _to_numpy(infos, LABEL_INFO_DTYPE)
 
 
 def label_shape(size, anchor_faces=VX_LABEL_ALL_FACES, max_pieces=VX_LABEL_MAX_PIECES, max_steps=VX_LABEL_MAX_STEPS, pass_value=0, flags=0):
@@ -448,37 +418,28 @@ def light_shape(size, props, flags=0):
 
 def ray_hits_to_numpy(hits):
     """A device hit tensor of Svo.raycast_batch as RAY_HIT_DTYPE records (copies to the host: synchronise first)."""
-    return hits.cpu().numpy().view(np.uint8).reshape(-1).view(RAY_HIT_DTYPE)
+    return _to_numpy(hits, RAY_HIT_DTYPE)
 
 
 def trace_hits_to_numpy(hits):
     """A device record tensor of Svo.trace_rays as HIT_DTYPE records (copies to the host: synchronise first)."""
-    return hits.cpu().numpy().view(np.uint8).reshape(-1).view(HIT_DTYPE)
+    return _to_numpy(hits, HIT_DTYPE)
 
 
 def ray_hit_positions(hits):
     """The positions inside vx_ray_hit records as the points of Svo.block_points: an (N, 3) float32 view at a stride of 32 bytes -- of a
     NumPy array of RAY_HIT_DTYPE, or of a device hit tensor of Svo.raycast_batch. No copy."""
-    if isinstance(hits, np.ndarray):
-        if hits.dtype != RAY_HIT_DTYPE:
-            raise TypeError("ray_hit_positions: a host array must be of hip.RAY_HIT_DTYPE")
-        return hits.reshape(-1)["pos"]
-    import torch
-
-    nbytes = hits.numel() * hits.element_size()
-    if nbytes % RAY_HIT_DTYPE.itemsize or not hits.is_contiguous():
-        raise TypeError("ray_hit_positions: a device tensor must be contiguous and hold whole 32-byte vx_ray_hit records")
-    return hits.reshape(-1).view(torch.uint8).view(torch.float32).view(-1, 8)[:, 4:7]
+    return _record_vectors("ray_hit_positions", "vx_ray_hit", hits, RAY_HIT_DTYPE, "pos")[0]
 
 
 def block_cells_to_numpy(cells):
     """A device record tensor of Svo.block_points as BLOCK_CELL_DTYPE records (copies to the host: synchronise first)."""
-    return cells.cpu().numpy().view(np.uint8).reshape(-1).view(BLOCK_CELL_DTYPE)
+    return _to_numpy(cells, BLOCK_CELL_DTYPE)
 
 
 def block_ats_to_numpy(records):
     """A device record tensor of Svo.list_region as BLOCK_AT_DTYPE records (copies to the host: synchronise first)."""
-    return records.cpu().numpy().view(np.uint8).reshape(-1).view(BLOCK_AT_DTYPE)
+    return _to_numpy(records, BLOCK_AT_DTYPE)
 
 
 def split_where(where):
@@ -490,29 +451,194 @@ def split_where(where):
 def scan_hits_to_numpy(hits):
     """A device record tensor of Svo.scan_points or Svo.scan_columns as SCAN_HIT_DTYPE records, in the tensor's shape without its last axis
     (copies to the host: synchronise first)."""
-    return hits.cpu().numpy().view(np.uint8).reshape(-1).view(SCAN_HIT_DTYPE).reshape(tuple(hits.shape[:-1]))
+    return _to_numpy(hits, SCAN_HIT_DTYPE).reshape(tuple(hits.shape[:-1]))
 
 
-def _ray_vectors(name, x, count, width):
+# ---- what the batch and block methods of Svo share: every one of them is its docstring, these, one call of the library and a return ----------
+_U8, _U32 = np.dtype(np.uint8), np.dtype(np.uint32)
+_DTYPE_NAMES = {v: k for k, v in list(globals().items()) if isinstance(v, np.dtype) and k.endswith("_DTYPE")}
+
+
+def _to_numpy(records, dtype):
+    """A device tensor's bytes as records of `dtype`, flat (copies to the host)."""
+    return records.cpu().numpy().view(np.uint8).reshape(-1).view(dtype)
+
+
+def _record_vectors(caller, c_name, records, dtype, *fields):
+    """The (N, 3) float32 vectors that the named fields of `dtype` records are, as views at the records' stride: of a NumPy array of `dtype`, or
+    of a contiguous torch tensor whose bytes are such records. No copy."""
+    if isinstance(records, np.ndarray):
+        if records.dtype != dtype:
+            raise TypeError(f"{caller}: a host array must be of hip.{_DTYPE_NAMES[dtype]}")
+        flat = records.reshape(-1)
+        return tuple(flat[f] for f in fields)
+    import torch
+
+    nbytes = records.numel() * records.element_size()
+    if nbytes % dtype.itemsize or not records.is_contiguous():
+        raise TypeError(f"{caller}: a device tensor must be contiguous and hold whole {dtype.itemsize}-byte {c_name} records")
+    rows = records.reshape(-1).view(torch.uint8).view(torch.float32).view(nbytes // dtype.itemsize, dtype.itemsize // 4)
+    return tuple(rows[:, dtype.fields[f][1] // 4:dtype.fields[f][1] // 4 + 3] for f in fields)
+
+
+def _ray_vectors(name, x, count, width, method="raycast_batch"):
     """(address, stride in bytes) of float32 vectors of `width` adjacent floats in a NumPy array or a torch tensor: `count` of them at the
-    array's own row stride (shape (count, width); (count,) for width 1), or -- width 3 -- a single one (shape (3,)) with stride 0."""
+    array's own row stride (shape (count, width); (count,) for width 1), or -- width 3 -- a single one (shape (3,)) with stride 0.
+    method: the caller a refusal names."""
     is_np = isinstance(x, np.ndarray)
     if str(x.dtype) not in ("float32", "torch.float32"):
-        raise TypeError(f"raycast_batch: {name} must be float32")
+        raise TypeError(f"{method}: {name} must be float32")
     shape = tuple(x.shape)
     strides = tuple(x.strides) if is_np else tuple(4 * st for st in x.stride())
     ptr = x.ctypes.data if is_np else x.data_ptr()
     if width > 1 and shape[-1:] == (width,) and strides[-1] != 4:
-        raise TypeError(f"raycast_batch: the components of {name} must be adjacent floats")
+        raise TypeError(f"{method}: the components of {name} must be adjacent floats")
     if width > 1 and shape == (width,):
         return ptr, 0
     if shape != ((count, width) if width > 1 else (count,)):
-        raise TypeError(f"raycast_batch: {name} has shape {shape} for {count} rays")
+        raise TypeError(f"{method}: {name} has shape {shape} for {count} rays")
     if count <= 1:
         return ptr, 4 * width  # (nobody steps by it)
     if strides[0] < 0:
-        raise TypeError(f"raycast_batch: {name} has a negative stride")
+        raise TypeError(f"{method}: {name} has a negative stride")
     return ptr, strides[0]
+
+
+def _points(method, name, x):
+    """(memory kind, count, address, stride in bytes) of an (N, 3) float32 batch at any row stride, a NumPy array or a torch CUDA tensor."""
+    host = isinstance(x, np.ndarray)
+    if len(x.shape) != 2 or x.shape[1] != 3:
+        raise TypeError(f"{method}: {name} must have shape (N, 3)")
+    if not host and not getattr(x, "is_cuda", False):
+        raise TypeError(f"{method}: {name} must be a NumPy array or a torch CUDA tensor")
+    count = int(x.shape[0])
+    ptr, stride = _ray_vectors(name, x, count, 3, method)
+    return VX_MEM_HOST if host else VX_MEM_DEVICE, count, _vp(ptr), stride
+
+
+def _lo_rows(method, lo):
+    """(memory kind, count, address, stride in bytes) of the int32 (N, 3) corners of light_boxes and label_boxes."""
+    host = isinstance(lo, np.ndarray)
+    if len(lo.shape) != 2 or lo.shape[1] != 3:
+        raise TypeError(f"{method}: lo must have shape (N, 3)")
+    if not host and not getattr(lo, "is_cuda", False):
+        raise TypeError(f"{method}: lo must be a NumPy array or a torch CUDA tensor")
+    count = int(lo.shape[0])
+    if host:
+        if lo.dtype != np.int32 or (count and (lo.strides[1] != 4 or lo.strides[0] % 4 or lo.strides[0] < 12)):
+            raise TypeError(f"{method}: lo must be int32 rows at a stride that is a multiple of 4 bytes and at least 12")
+        return VX_MEM_HOST, count, _vp(lo.ctypes.data), int(lo.strides[0]) if count else 12
+    if str(lo.dtype) != "torch.int32" or (count and (lo.stride(1) != 1 or lo.stride(0) < 3)):
+        raise TypeError(f"{method}: lo must be int32 rows whose last axis is contiguous, at a stride of at least 3 elements")
+    return VX_MEM_DEVICE, count, _vp(lo.data_ptr()), 4 * int(lo.stride(0)) if count else 12
+
+
+def _box_batch(method, names, origin, extents, offset, only_value, device, *more):
+    """(vx_box_batch, count, memory kind) of overlap_boxes' and move_boxes' boxes; `more`: what else has to lie where they lie."""
+    host = isinstance(origin, np.ndarray)
+    if len(origin.shape) != 2 or origin.shape[1] != 3:
+        raise TypeError(f"{method}: origin must have shape (N, 3)")
+    count = int(origin.shape[0])
+    given = [origin, extents, *more] + ([offset] if offset is not None else [])
+    if host and (device or not all(isinstance(x, np.ndarray) for x in given)):
+        raise TypeError(f"{method}: {names} must all be NumPy arrays, or -- device=True -- all torch CUDA tensors")
+    if not host and not all(getattr(x, "is_cuda", False) for x in given):
+        raise TypeError(f"{method}: {names} must all be NumPy arrays or all torch CUDA tensors")
+    batch = BoxBatch()
+    batch.origin, batch.origin_stride = _ray_vectors("origin", origin, count, 3, method)
+    batch.extents, batch.extents_stride = _ray_vectors("extents", extents, count, 3, method)
+    if offset is not None:
+        batch.offset, batch.offset_stride = _ray_vectors("offset", offset, count, 3, method)
+    batch.only_value = int(only_value)
+    return batch, count, VX_MEM_HOST if host else VX_MEM_DEVICE
+
+
+def _region(lo, size, out, device):
+    """(lo, size, memory kind) of a region call: the box as the library reads it; the host's memory unless device=True or `out` is no NumPy array."""
+    host = not device and (out is None or isinstance(out, np.ndarray))
+    return (C.c_int32 * 3)(*(int(v) for v in lo)), (_u32 * 3)(*(int(v) for v in size)), VX_MEM_HOST if host else VX_MEM_DEVICE
+
+
+def _ptr(x):
+    """None, or where a NumPy array's or a torch tensor's first byte lies, as the library takes it."""
+    if x is None:
+        return None
+    return _vp(x.ctypes.data if isinstance(x, np.ndarray) else x.data_ptr())
+
+
+def _asked(x, none):
+    """What a fields, info, pieces or paths argument asks for: None -- no output --, True -- fresh memory -- or the memory to write to. `none`: what
+    None stands for in this method (flood_points and walk_points: none; light_boxes and label_boxes: fresh memory; False is none everywhere)."""
+    if x is None:
+        x = none
+    return None if x is False else x
+
+
+def _out(where, out, mem, count, dtype, shape, on, exact=True, what="N", unit="values"):
+    """An output of `count` items of `dtype`. None: none. True: fresh memory -- a NumPy array of `shape`, or for device memory, on the device of
+    `on` (a tensor, or a device's name), an int32 tensor of shape + (a record's words,), of `shape` for plain numbers (uint8 for bytes). Else
+    the caller's, which has to be contiguous, writeable and of the dtype (a NumPy array) or on the device (a tensor), and hold exactly `count`
+    items (exact=True), exactly in host memory and at least in device memory ("host"), or at least (False). where, what, unit: for the refusal."""
+    if out is None:
+        return None
+    size, host = dtype.itemsize, mem == VX_MEM_HOST
+    if out is True:
+        if host:
+            return np.zeros(shape, dtype=dtype)
+        import torch
+
+        return torch.empty(shape + (size // 4,) if dtype.names else shape, dtype=torch.uint8 if size == 1 else torch.int32, device=getattr(on, "device", on))
+    if host:
+        ok = isinstance(out, np.ndarray) and out.dtype == dtype and (out.size == count if exact else out.size >= count) and out.flags.c_contiguous and out.flags.writeable
+    else:
+        ok = getattr(out, "is_cuda", False) and out.is_contiguous()
+        if ok:
+            nbytes = out.numel() * out.element_size()
+            ok = nbytes == count * size if exact is True else nbytes >= count * size
+    if not ok:
+        least = "" if exact is True or (exact and host) else "at least "
+        if not host:
+            raise TypeError(f"{where} must be a contiguous CUDA tensor of {least}{what}{f' x {size}' if size > 1 else ''} bytes")
+        kind = f"array of {what} hip.{_DTYPE_NAMES[dtype]} records" if dtype.names else f"{dtype.name} array of {least}{what} {unit}"
+        raise TypeError(f"{where} must be a writeable C-contiguous {kind}")
+    return out
+
+
+def _fields_out(method, fields, mem, count, shape, field_stride, on):
+    """The `fields` of a field call (_out's None, True or the caller's): a row of bytes a query, field_stride apart -- 0: the shape's cells rounded
+    up to 16."""
+    stride = int(field_stride) if field_stride else (int(shape.size[0]) * int(shape.size[1]) * int(shape.size[2]) + 15) // 16 * 16
+    return _out(f"{method}: fields", fields, mem, count * stride, _U8, (count, stride), on, False, "N x field_stride", "bytes")
+
+
+def _trace_outputs(method, what, out, mem, count, px_shape, hit_shape, fmt, want_rgba, want_hits, on):
+    """(pixels, records) of trace_rays and trace_views, None for what is not wanted: the members of `out`, which may be longer than `count`
+    pixels or records, or fresh memory where one is None -- as _out's, but for the pixels, float32 or uint8 by fmt."""
+    if not want_rgba and not want_hits:
+        raise TypeError(f"{method}: nothing asked for")
+    rgba, hits = out if out is not None else (None, None)
+    host, bytes8 = mem == VX_MEM_HOST, fmt == VX_FORMAT_RGBA8
+    if not want_rgba:
+        rgba = None
+    elif rgba is None:
+        if host:
+            rgba = np.zeros(px_shape, dtype=np.uint8 if bytes8 else np.float32)
+        else:
+            import torch
+
+            rgba = torch.empty(px_shape, dtype=torch.uint8 if bytes8 else torch.float32, device=getattr(on, "device", on))
+    if not want_hits:
+        hits = None
+    elif hits is None:
+        hits = _out(None, True, mem, count, HIT_DTYPE, hit_shape, on)
+    for a, size in ((rgba, 4 if bytes8 else 16), (hits, HIT_DTYPE.itemsize)):
+        if a is None:
+            continue
+        if host and not (isinstance(a, np.ndarray) and a.nbytes >= count * size and a.flags.c_contiguous and a.flags.writeable):
+            raise TypeError(f"{method}: an output must be a writeable C-contiguous array of at least {what} pixels / records")
+        if not host and not (getattr(a, "is_cuda", False) and a.is_contiguous() and a.numel() * a.element_size() >= count * size):
+            raise TypeError(f"{method}: an output must be a contiguous CUDA tensor of at least {what} pixels / records")
+    return rgba, hits
 
 
 def _device_ptr(x):
@@ -690,26 +816,14 @@ class Svo:
         Host (NumPy arrays): synchronous; returns `out` or a fresh array of RAY_HIT_DTYPE.
         Device (torch CUDA tensors): returns after enqueueing, without synchronising -- pair with sync(); the hits are `out` or a fresh
         int32 tensor of shape (N, 8) on the rays' device, whose rows are vx_ray_hit records (ray_hits_to_numpy)."""
-        b, count, host = self._ray_batch(origins, dirs, max_dst)
+        b, count, mem = self._ray_batch(origins, dirs, max_dst, "raycast_batch")
         b.flags = VX_RAYS_TRANSLUCENT if translucent else 0
-        if host:
-            if out is None:
-                out = np.zeros(count, dtype=RAY_HIT_DTYPE)
-            elif not isinstance(out, np.ndarray) or out.dtype != RAY_HIT_DTYPE or out.size != count or not out.flags.c_contiguous or not out.flags.writeable:
-                raise TypeError("raycast_batch: out must be a writeable C-contiguous array of N hip.RAY_HIT_DTYPE records")
-            _check(lib().vx_raycast_batch(self._h, C.byref(b), count, VX_MEM_HOST, out.ctypes.data_as(_vp)))
-            return out
-        import torch
-
-        if out is None:
-            out = torch.empty((count, 8), dtype=torch.int32, device=origins.device)
-        elif not out.is_cuda or not out.is_contiguous() or out.numel() * out.element_size() != count * RAY_HIT_DTYPE.itemsize:
-            raise TypeError("raycast_batch: out must be a contiguous CUDA tensor of N x 32 bytes")
-        _check(lib().vx_raycast_batch(self._h, C.byref(b), count, VX_MEM_DEVICE, _vp(out.data_ptr())))
+        out = _out("raycast_batch: out", True if out is None else out, mem, count, RAY_HIT_DTYPE, (count,), origins)
+        _check(lib().vx_raycast_batch(self._h, C.byref(b), count, mem, _ptr(out)))
         return out
 
-    def _ray_batch(self, origins, dirs, max_dst):
-        """(vx_ray_batch, count, host?) of raycast_batch's three ray arguments."""
+    def _ray_batch(self, origins, dirs, max_dst, method):
+        """(vx_ray_batch, count, memory kind) of raycast_batch's three ray arguments."""
         host = isinstance(origins, np.ndarray)
         count = int(origins.shape[0]) if len(origins.shape) == 2 else -1
         if count < 0 or origins.shape[1] != 3:
@@ -719,13 +833,13 @@ class Svo:
         arrays = [origins, dirs] + ([max_dst] if per_ray else [])
         if any(isinstance(a, np.ndarray) != host for a in arrays) or (not host and not all(getattr(a, "is_cuda", False) for a in arrays)):
             raise TypeError("raycast_batch: origins, dirs and max_dst must all be NumPy arrays or all be torch CUDA tensors")
-        b.origin, b.origin_stride = _ray_vectors("origins", origins, count, 3)
-        b.dir, b.dir_stride = _ray_vectors("dirs", dirs, count, 3)
+        b.origin, b.origin_stride = _ray_vectors("origins", origins, count, 3, method)
+        b.dir, b.dir_stride = _ray_vectors("dirs", dirs, count, 3, method)
         if per_ray:
-            b.max_dst, b.max_dst_stride = _ray_vectors("max_dst", max_dst, count, 1)
+            b.max_dst, b.max_dst_stride = _ray_vectors("max_dst", max_dst, count, 1, method)
         else:
             b.max_dst, b.max_dst_stride, b.max_dst_all = None, 0, float(max_dst)
-        return b, count, host
+        return b, count, VX_MEM_HOST if host else VX_MEM_DEVICE
 
     def trace_rays(self, uniforms, origins, dirs, max_dst=-1.0, want_hits=False, fmt=VX_FORMAT_RGBA32F, out=None, want_rgba=True):
         """vx_trace_rays: world.glsl's trace_ray, or the sky, for rays read where they lie (the arguments of raycast_batch: NumPy arrays, or
@@ -733,34 +847,10 @@ class Svo:
         records: vx_hit (HIT_DTYPE) when want_hits, else None. out: (pixels, records) to write into instead of fresh arrays (either may be
         None to have a fresh one; they may be longer than N).
         Host: synchronous. Device: returns after enqueueing -- pair with sync(); records are an int32 tensor of shape (N, 12) (trace_hits_to_numpy)."""
-        b, count, host = self._ray_batch(origins, dirs, max_dst)
-        if not want_rgba and not want_hits:
-            raise TypeError("trace_rays: nothing asked for")
-        rgba, hits = out if out is not None else (None, None)
-        px_dt, px_bytes = (np.uint8, 4) if fmt == VX_FORMAT_RGBA8 else (np.float32, 16)
-        if host:
-            if want_rgba and rgba is None:
-                rgba = np.zeros((count, 4), dtype=px_dt)
-            if want_hits and hits is None:
-                hits = np.zeros(count, dtype=HIT_DTYPE)
-            for a, size in ((rgba if want_rgba else None, px_bytes), (hits if want_hits else None, HIT_DTYPE.itemsize)):
-                if a is not None and (not isinstance(a, np.ndarray) or a.nbytes < count * size or not a.flags.c_contiguous or not a.flags.writeable):
-                    raise TypeError("trace_rays: an output must be a writeable C-contiguous array of at least N pixels / records")
-            _check(lib().vx_trace_rays(self._h, C.byref(uniforms), C.byref(b), count, VX_MEM_HOST, rgba.ctypes.data_as(_vp) if want_rgba else None, fmt,
-                                       hits.ctypes.data_as(_vp) if want_hits else None))
-            return (rgba if want_rgba else None), (hits if want_hits else None)
-        import torch
-
-        if want_rgba and rgba is None:
-            rgba = torch.empty((count, 4), dtype=torch.uint8 if fmt == VX_FORMAT_RGBA8 else torch.float32, device=origins.device)
-        if want_hits and hits is None:
-            hits = torch.empty((count, 12), dtype=torch.int32, device=origins.device)
-        for a, size in ((rgba if want_rgba else None, px_bytes), (hits if want_hits else None, HIT_DTYPE.itemsize)):
-            if a is not None and (not a.is_cuda or not a.is_contiguous() or a.numel() * a.element_size() < count * size):
-                raise TypeError("trace_rays: an output must be a contiguous CUDA tensor of at least N pixels / records")
-        _check(lib().vx_trace_rays(self._h, C.byref(uniforms), C.byref(b), count, VX_MEM_DEVICE, _vp(rgba.data_ptr()) if want_rgba else None, fmt,
-                                   _vp(hits.data_ptr()) if want_hits else None))
-        return (rgba if want_rgba else None), (hits if want_hits else None)
+        b, count, mem = self._ray_batch(origins, dirs, max_dst, "trace_rays")
+        rgba, hits = _trace_outputs("trace_rays", "N", out, mem, count, (count, 4), (count,), fmt, want_rgba, want_hits, origins)
+        _check(lib().vx_trace_rays(self._h, C.byref(uniforms), C.byref(b), count, mem, _ptr(rgba), fmt, _ptr(hits)))
+        return rgba, hits
 
     def trace_views(self, views, width, height, want_hits=False, want_rgba=True, fmt=VX_FORMAT_RGBA32F, out=None, device=False):
         """vx_trace_views: world.glsl's main for every pixel of many small views in one launch. views: a list of Uniforms or a ctypes array of
@@ -774,37 +864,16 @@ class Svo:
             raise TypeError("trace_views: nothing asked for")
         table = views if isinstance(views, C.Array) else (Uniforms * max(len(views), 1))(*views)
         count = len(views)
-        n = count * width * height
-        rgba, hits = out if out is not None else (None, None)
-        px_dt, px_bytes = (np.uint8, 4) if fmt == VX_FORMAT_RGBA8 else (np.float32, 16)
-        given = [a for a in (rgba, hits) if a is not None]
+        given = [a for a in (out or ()) if a is not None]
         if given and any(isinstance(a, np.ndarray) != isinstance(given[0], np.ndarray) for a in given):
             raise TypeError("trace_views: the outputs must both be NumPy arrays or both be torch CUDA tensors")
         if given:
             device = not isinstance(given[0], np.ndarray)
-        if not device:
-            if want_rgba and rgba is None:
-                rgba = np.zeros((count, height, width, 4), dtype=px_dt)
-            if want_hits and hits is None:
-                hits = np.zeros((count, height * width), dtype=HIT_DTYPE)
-            for a, size in ((rgba if want_rgba else None, px_bytes), (hits if want_hits else None, HIT_DTYPE.itemsize)):
-                if a is not None and (not isinstance(a, np.ndarray) or a.nbytes < n * size or not a.flags.c_contiguous or not a.flags.writeable):
-                    raise TypeError("trace_views: an output must be a writeable C-contiguous array of at least count * H * W pixels / records")
-            _check(lib().vx_trace_views(self._h, table, count, width, height, VX_MEM_HOST, rgba.ctypes.data_as(_vp) if want_rgba else None, fmt,
-                                        hits.ctypes.data_as(_vp) if want_hits else None))
-            return (rgba if want_rgba else None), (hits if want_hits else None)
-        import torch
-
-        if want_rgba and rgba is None:
-            rgba = torch.empty((count, height, width, 4), dtype=torch.uint8 if fmt == VX_FORMAT_RGBA8 else torch.float32, device="cuda")
-        if want_hits and hits is None:
-            hits = torch.empty((count, height * width, 12), dtype=torch.int32, device="cuda")
-        for a, size in ((rgba if want_rgba else None, px_bytes), (hits if want_hits else None, HIT_DTYPE.itemsize)):
-            if a is not None and (not a.is_cuda or not a.is_contiguous() or a.numel() * a.element_size() < n * size):
-                raise TypeError("trace_views: an output must be a contiguous CUDA tensor of at least count * H * W pixels / records")
-        _check(lib().vx_trace_views(self._h, table, count, width, height, VX_MEM_DEVICE, _vp(rgba.data_ptr()) if want_rgba else None, fmt,
-                                    _vp(hits.data_ptr()) if want_hits else None))
-        return (rgba if want_rgba else None), (hits if want_hits else None)
+        mem = VX_MEM_DEVICE if device else VX_MEM_HOST
+        rgba, hits = _trace_outputs("trace_views", "count * H * W", out, mem, count * width * height, (count, height, width, 4), (count, height * width), fmt,
+                                    want_rgba, want_hits, "cuda")
+        _check(lib().vx_trace_views(self._h, table, count, width, height, mem, _ptr(rgba), fmt, _ptr(hits)))
+        return rgba, hits
 
     # -- block ids read from the device (gameplay.rs:161-201: get_block(floor(pos)), asked of the world the device holds) -----------------------
     def block_points(self, positions, out=None):
@@ -813,27 +882,9 @@ class Svo:
         Host (a NumPy array): synchronous; returns `out` or a fresh array of BLOCK_CELL_DTYPE.
         Device (a torch CUDA tensor): returns after enqueueing, without synchronising -- pair with sync(); the records are `out` or a fresh
         int32 tensor of shape (N, 2) on the positions' device (block_cells_to_numpy)."""
-        host = isinstance(positions, np.ndarray)
-        if len(positions.shape) != 2 or positions.shape[1] != 3:
-            raise TypeError("block_points: positions must have shape (N, 3)")
-        count = int(positions.shape[0])
-        if not host and not getattr(positions, "is_cuda", False):
-            raise TypeError("block_points: positions must be a NumPy array or a torch CUDA tensor")
-        ptr, stride = _ray_vectors("positions", positions, count, 3)
-        if host:
-            if out is None:
-                out = np.zeros(count, dtype=BLOCK_CELL_DTYPE)
-            elif not isinstance(out, np.ndarray) or out.dtype != BLOCK_CELL_DTYPE or out.size != count or not out.flags.c_contiguous or not out.flags.writeable:
-                raise TypeError("block_points: out must be a writeable C-contiguous array of N hip.BLOCK_CELL_DTYPE records")
-            _check(lib().vx_block_points(self._h, _vp(ptr), stride, count, VX_MEM_HOST, out.ctypes.data_as(_vp)))
-            return out
-        import torch
-
-        if out is None:
-            out = torch.empty((count, 2), dtype=torch.int32, device=positions.device)
-        elif not out.is_cuda or not out.is_contiguous() or out.numel() * out.element_size() != count * BLOCK_CELL_DTYPE.itemsize:
-            raise TypeError("block_points: out must be a contiguous CUDA tensor of N x 8 bytes")
-        _check(lib().vx_block_points(self._h, _vp(ptr), stride, count, VX_MEM_DEVICE, _vp(out.data_ptr())))
+        mem, count, ptr, stride = _points("block_points", "positions", positions)
+        out = _out("block_points: out", True if out is None else out, mem, count, BLOCK_CELL_DTYPE, (count,), positions)
+        _check(lib().vx_block_points(self._h, ptr, stride, count, mem, _ptr(out)))
         return out
 
     def read_region(self, lo, size, out=None, device=False):
@@ -842,23 +893,10 @@ class Svo:
         Host (default): synchronous; returns `out` or a fresh NumPy array of shape (size.z, size.y, size.x).
         Device (device=True, or `out` a torch CUDA tensor): returns after enqueueing, without synchronising -- pair with sync(); the ids
         are `out` or a fresh int32 tensor of that shape (the bits of the uint32 ids)."""
-        lo3, size3 = (C.c_int32 * 3)(*(int(v) for v in lo)), (_u32 * 3)(*(int(v) for v in size))
+        lo3, size3, mem = _region(lo, size, out, device)
         shape = (int(size[2]), int(size[1]), int(size[0]))
-        voxels = shape[0] * shape[1] * shape[2]
-        if not device and (out is None or isinstance(out, np.ndarray)):
-            if out is None:
-                out = np.zeros(shape, dtype=np.uint32)
-            elif out.dtype != np.uint32 or out.size != voxels or not out.flags.c_contiguous or not out.flags.writeable:
-                raise TypeError("read_region: out must be a writeable C-contiguous uint32 array of size.x * size.y * size.z values")
-            _check(lib().vx_read_region(self._h, C.byref(lo3), C.byref(size3), VX_MEM_HOST, out.ctypes.data_as(_vp)))
-            return out
-        import torch
-
-        if out is None:
-            out = torch.empty(shape, dtype=torch.int32, device="cuda")
-        elif not getattr(out, "is_cuda", False) or not out.is_contiguous() or out.numel() * out.element_size() != voxels * 4:
-            raise TypeError("read_region: out must be a contiguous CUDA tensor of size.x * size.y * size.z x 4 bytes")
-        _check(lib().vx_read_region(self._h, C.byref(lo3), C.byref(size3), VX_MEM_DEVICE, _vp(out.data_ptr())))
+        out = _out("read_region: out", True if out is None else out, mem, shape[0] * shape[1] * shape[2], _U32, shape, "cuda", True, "size.x * size.y * size.z", "values")
+        _check(lib().vx_read_region(self._h, C.byref(lo3), C.byref(size3), mem, _ptr(out)))
         return out
 
     def list_region(self, lo, size, flags=0, capacity=None, out=None, device=False):
@@ -870,38 +908,34 @@ class Svo:
         Device (device=True, or `out` a torch CUDA tensor): returns after enqueueing, without synchronising -- pair with sync(); the records
         are `out` or a fresh int32 tensor of shape (capacity, 2), of which the first min(total, capacity) rows are written
         (block_ats_to_numpy); total is an int32 tensor of one element on the device."""
-        lo3, size3 = (C.c_int32 * 3)(*(int(v) for v in lo)), (_u32 * 3)(*(int(v) for v in size))
+        lo3, size3, mem = _region(lo, size, out, device)
         voxels = int(size[0]) * int(size[1]) * int(size[2])
-        if not device and (out is None or isinstance(out, np.ndarray)):
+        if mem == VX_MEM_HOST:
             if out is not None and (out.dtype != BLOCK_AT_DTYPE or not out.flags.c_contiguous or not out.flags.writeable):
                 raise TypeError("list_region: out must be a writeable C-contiguous array of hip.BLOCK_AT_DTYPE records")
             total = _u32(0)
             if out is None:
                 if capacity is None:  # count first: the array is as long as the list
-                    _check(lib().vx_list_region(self._h, C.byref(lo3), C.byref(size3), int(flags), VX_MEM_HOST, None, 0, C.byref(total)))
+                    _check(lib().vx_list_region(self._h, C.byref(lo3), C.byref(size3), int(flags), mem, None, 0, C.byref(total)))
                     capacity = total.value
                 capacity = min(int(capacity), voxels)  # (a box has no more records than voxels)
                 out = np.zeros(capacity, dtype=BLOCK_AT_DTYPE)
-            capacity = out.size if capacity is None else int(capacity)
-            if capacity > out.size:
-                raise TypeError("list_region: out holds fewer than `capacity` records")
-            _check(lib().vx_list_region(self._h, C.byref(lo3), C.byref(size3), int(flags), VX_MEM_HOST, out.ctypes.data_as(_vp) if capacity else None,
-                                        capacity, C.byref(total)))
-            return out.reshape(-1)[:min(total.value, capacity)], total.value
-        import torch
+            held = out.size
+        else:
+            import torch
 
-        if out is None:
-            out = torch.empty((voxels if capacity is None else int(capacity), 2), dtype=torch.int32, device="cuda")
-        elif not getattr(out, "is_cuda", False) or not out.is_contiguous() or (out.numel() * out.element_size()) % BLOCK_AT_DTYPE.itemsize:
-            raise TypeError("list_region: out must be a contiguous CUDA tensor of whole 8-byte records")
-        held = out.numel() * out.element_size() // BLOCK_AT_DTYPE.itemsize
+            if out is None:
+                out = torch.empty((voxels if capacity is None else int(capacity), 2), dtype=torch.int32, device="cuda")
+            elif not getattr(out, "is_cuda", False) or not out.is_contiguous() or (out.numel() * out.element_size()) % BLOCK_AT_DTYPE.itemsize:
+                raise TypeError("list_region: out must be a contiguous CUDA tensor of whole 8-byte records")
+            held = out.numel() * out.element_size() // BLOCK_AT_DTYPE.itemsize
+            total = torch.zeros(1, dtype=torch.int32, device=out.device)
         capacity = held if capacity is None else int(capacity)
         if capacity > held:
             raise TypeError("list_region: out holds fewer than `capacity` records")
-        total = torch.zeros(1, dtype=torch.int32, device=out.device)
-        _check(lib().vx_list_region(self._h, C.byref(lo3), C.byref(size3), int(flags), VX_MEM_DEVICE, _vp(out.data_ptr()) if capacity else None, capacity,
-                                    _vp(total.data_ptr())))
-        return out, total
+        _check(lib().vx_list_region(self._h, C.byref(lo3), C.byref(size3), int(flags), mem, _ptr(out) if capacity else None, capacity,
+                                    C.byref(total) if mem == VX_MEM_HOST else _ptr(total)))
+        return (out.reshape(-1)[:min(total.value, capacity)], total.value) if mem == VX_MEM_HOST else (out, total)
 
     # -- the first block along an axis (get_block, gameplay.rs:161-201, looped along it) ----------------------------------------------------------
     def scan_points(self, positions, direction, reach=VX_SCAN_TO_EDGE, out=None):
@@ -910,27 +944,9 @@ class Svo:
         Host (a NumPy array): synchronous; returns `out` or a fresh array of SCAN_HIT_DTYPE.
         Device (a torch CUDA tensor): returns after enqueueing, without synchronising -- pair with sync(); the records are `out` or a fresh
         int32 tensor of shape (N, 4) on the positions' device (scan_hits_to_numpy)."""
-        host = isinstance(positions, np.ndarray)
-        if len(positions.shape) != 2 or positions.shape[1] != 3:
-            raise TypeError("scan_points: positions must have shape (N, 3)")
-        count = int(positions.shape[0])
-        if not host and not getattr(positions, "is_cuda", False):
-            raise TypeError("scan_points: positions must be a NumPy array or a torch CUDA tensor")
-        ptr, stride = _ray_vectors("positions", positions, count, 3)
-        if host:
-            if out is None:
-                out = np.zeros(count, dtype=SCAN_HIT_DTYPE)
-            elif not isinstance(out, np.ndarray) or out.dtype != SCAN_HIT_DTYPE or out.size != count or not out.flags.c_contiguous or not out.flags.writeable:
-                raise TypeError("scan_points: out must be a writeable C-contiguous array of N hip.SCAN_HIT_DTYPE records")
-            _check(lib().vx_scan_points(self._h, _vp(ptr), stride, count, int(direction), int(reach), VX_MEM_HOST, out.ctypes.data_as(_vp)))
-            return out
-        import torch
-
-        if out is None:
-            out = torch.empty((count, 4), dtype=torch.int32, device=positions.device)
-        elif not out.is_cuda or not out.is_contiguous() or out.numel() * out.element_size() != count * SCAN_HIT_DTYPE.itemsize:
-            raise TypeError("scan_points: out must be a contiguous CUDA tensor of N x 16 bytes")
-        _check(lib().vx_scan_points(self._h, _vp(ptr), stride, count, int(direction), int(reach), VX_MEM_DEVICE, _vp(out.data_ptr())))
+        mem, count, ptr, stride = _points("scan_points", "positions", positions)
+        out = _out("scan_points: out", True if out is None else out, mem, count, SCAN_HIT_DTYPE, (count,), positions)
+        _check(lib().vx_scan_points(self._h, ptr, stride, count, int(direction), int(reach), mem, _ptr(out)))
         return out
 
     def scan_columns(self, lo, size, direction, out=None, device=False):
@@ -940,25 +956,12 @@ class Svo:
         Host (default): synchronous; returns `out` or a fresh NumPy array of shape (size.v, size.u).
         Device (device=True, or `out` a torch CUDA tensor): returns after enqueueing, without synchronising -- pair with sync(); the records
         are `out` or a fresh int32 tensor of shape (size.v, size.u, 4) (scan_hits_to_numpy)."""
-        lo3, size3 = (C.c_int32 * 3)(*(int(v) for v in lo)), (_u32 * 3)(*(int(v) for v in size))
+        lo3, size3, mem = _region(lo, size, out, device)
         a = int(direction) >> 1
         u, v = (1 if a == 0 else 0), (1 if a == 2 else 2)
-        shape = (int(size[v]), int(size[u])) if 0 <= a <= 2 else (0, 0)
-        columns = shape[0] * shape[1] if all(int(n) for n in size) else 0
-        if not device and (out is None or isinstance(out, np.ndarray)):
-            if out is None:
-                out = np.zeros(shape if columns else (0, 0), dtype=SCAN_HIT_DTYPE)
-            elif out.dtype != SCAN_HIT_DTYPE or out.size != columns or not out.flags.c_contiguous or not out.flags.writeable:
-                raise TypeError("scan_columns: out must be a writeable C-contiguous array of size.u * size.v hip.SCAN_HIT_DTYPE records")
-            _check(lib().vx_scan_columns(self._h, C.byref(lo3), C.byref(size3), int(direction), VX_MEM_HOST, out.ctypes.data_as(_vp)))
-            return out
-        import torch
-
-        if out is None:
-            out = torch.empty((shape if columns else (0, 0)) + (4,), dtype=torch.int32, device="cuda")
-        elif not getattr(out, "is_cuda", False) or not out.is_contiguous() or out.numel() * out.element_size() != columns * SCAN_HIT_DTYPE.itemsize:
-            raise TypeError("scan_columns: out must be a contiguous CUDA tensor of size.u * size.v x 16 bytes")
-        _check(lib().vx_scan_columns(self._h, C.byref(lo3), C.byref(size3), int(direction), VX_MEM_DEVICE, _vp(out.data_ptr())))
+        shape = (int(size[v]), int(size[u])) if 0 <= a <= 2 and all(int(n) for n in size) else (0, 0)
+        out = _out("scan_columns: out", True if out is None else out, mem, shape[0] * shape[1], SCAN_HIT_DTYPE, shape, "cuda", True, "size.u * size.v")
+        _check(lib().vx_scan_columns(self._h, C.byref(lo3), C.byref(size3), int(direction), mem, _ptr(out)))
         return out
 
     # -- what float boxes hold (gameplay.rs:211-222: the player's AABB against a voxel, for a batch) -----------------------------------------------
@@ -970,35 +973,9 @@ class Svo:
         Host (NumPy arrays): synchronous; returns `out` or a fresh array of BOX_HIT_DTYPE.
         Device (torch CUDA tensors; device=True insists on them): returns after enqueueing, without synchronising -- pair with sync(); the
         records are `out` or a fresh int32 tensor of shape (N, 8) on the origins' device (box_hits_to_numpy)."""
-        host = isinstance(origin, np.ndarray)
-        if len(origin.shape) != 2 or origin.shape[1] != 3:
-            raise TypeError("overlap_boxes: origin must have shape (N, 3)")
-        count = int(origin.shape[0])
-        given = [origin, extents] + ([offset] if offset is not None else [])
-        if host and (device or not all(isinstance(x, np.ndarray) for x in given)):
-            raise TypeError("overlap_boxes: origin, extents and offset must all be NumPy arrays, or -- device=True -- all torch CUDA tensors")
-        if not host and not all(getattr(x, "is_cuda", False) for x in given):
-            raise TypeError("overlap_boxes: origin, extents and offset must all be NumPy arrays or all torch CUDA tensors")
-        batch = BoxBatch()
-        batch.origin, batch.origin_stride = _ray_vectors("origin", origin, count, 3)
-        batch.extents, batch.extents_stride = _ray_vectors("extents", extents, count, 3)
-        if offset is not None:
-            batch.offset, batch.offset_stride = _ray_vectors("offset", offset, count, 3)
-        batch.only_value = int(only_value)
-        if host:
-            if out is None:
-                out = np.zeros(count, dtype=BOX_HIT_DTYPE)
-            elif not isinstance(out, np.ndarray) or out.dtype != BOX_HIT_DTYPE or out.size != count or not out.flags.c_contiguous or not out.flags.writeable:
-                raise TypeError("overlap_boxes: out must be a writeable C-contiguous array of N hip.BOX_HIT_DTYPE records")
-            _check(lib().vx_overlap_boxes(self._h, C.byref(batch), count, VX_MEM_HOST, out.ctypes.data_as(_vp)))
-            return out
-        import torch
-
-        if out is None:
-            out = torch.empty((count, 8), dtype=torch.int32, device=origin.device)
-        elif not out.is_cuda or not out.is_contiguous() or out.numel() * out.element_size() < count * BOX_HIT_DTYPE.itemsize:
-            raise TypeError("overlap_boxes: out must be a contiguous CUDA tensor of at least N x 32 bytes")
-        _check(lib().vx_overlap_boxes(self._h, C.byref(batch), count, VX_MEM_DEVICE, _vp(out.data_ptr())))
+        batch, count, mem = _box_batch("overlap_boxes", "origin, extents and offset", origin, extents, offset, only_value, device)
+        out = _out("overlap_boxes: out", True if out is None else out, mem, count, BOX_HIT_DTYPE, (count,), origin, "host")
+        _check(lib().vx_overlap_boxes(self._h, C.byref(batch), count, mem, _ptr(out)))
         return out
 
     # -- float boxes moved through the world, stopped by blocks (what physics.rs:171-184 asks of the picker fan, of every voxel ahead) ---------------
@@ -1010,37 +987,11 @@ class Svo:
         Host (NumPy arrays): synchronous; returns `out` or a fresh array of MOVE_HIT_DTYPE.
         Device (torch CUDA tensors; device=True insists on them): returns after enqueueing, without synchronising -- pair with sync(); the
         records are `out` or a fresh int32 tensor of shape (N, 12) on the origins' device (move_hits_to_numpy)."""
-        host = isinstance(origin, np.ndarray)
-        if len(origin.shape) != 2 or origin.shape[1] != 3:
-            raise TypeError("move_boxes: origin must have shape (N, 3)")
-        count = int(origin.shape[0])
-        given = [origin, extents, motion] + ([offset] if offset is not None else [])
-        if host and (device or not all(isinstance(x, np.ndarray) for x in given)):
-            raise TypeError("move_boxes: origin, extents, motion and offset must all be NumPy arrays, or -- device=True -- all torch CUDA tensors")
-        if not host and not all(getattr(x, "is_cuda", False) for x in given):
-            raise TypeError("move_boxes: origin, extents, motion and offset must all be NumPy arrays or all torch CUDA tensors")
-        batch = BoxBatch()
-        batch.origin, batch.origin_stride = _ray_vectors("origin", origin, count, 3)
-        batch.extents, batch.extents_stride = _ray_vectors("extents", extents, count, 3)
-        if offset is not None:
-            batch.offset, batch.offset_stride = _ray_vectors("offset", offset, count, 3)
-        batch.only_value = int(only_value)
-        motion_ptr, motion_stride = _ray_vectors("motion", motion, count, 3)
+        batch, count, mem = _box_batch("move_boxes", "origin, extents, motion and offset", origin, extents, offset, only_value, device, motion)
+        motion_ptr, motion_stride = _ray_vectors("motion", motion, count, 3, "move_boxes")
         shape = MOVE_SHAPE(scale, skin, order)
-        if host:
-            if out is None:
-                out = np.zeros(count, dtype=MOVE_HIT_DTYPE)
-            elif not isinstance(out, np.ndarray) or out.dtype != MOVE_HIT_DTYPE or out.size != count or not out.flags.c_contiguous or not out.flags.writeable:
-                raise TypeError("move_boxes: out must be a writeable C-contiguous array of N hip.MOVE_HIT_DTYPE records")
-            _check(lib().vx_move_boxes(self._h, C.byref(batch), _vp(motion_ptr), motion_stride, count, C.byref(shape), VX_MEM_HOST, out.ctypes.data_as(_vp)))
-            return out
-        import torch
-
-        if out is None:
-            out = torch.empty((count, 12), dtype=torch.int32, device=origin.device)
-        elif not out.is_cuda or not out.is_contiguous() or out.numel() * out.element_size() < count * MOVE_HIT_DTYPE.itemsize:
-            raise TypeError("move_boxes: out must be a contiguous CUDA tensor of at least N x 48 bytes")
-        _check(lib().vx_move_boxes(self._h, C.byref(batch), _vp(motion_ptr), motion_stride, count, C.byref(shape), VX_MEM_DEVICE, _vp(out.data_ptr())))
+        out = _out("move_boxes: out", True if out is None else out, mem, count, MOVE_HIT_DTYPE, (count,), origin, "host")
+        _check(lib().vx_move_boxes(self._h, C.byref(batch), _vp(motion_ptr), motion_stride, count, C.byref(shape), mem, _ptr(out)))
         return out
 
     # -- step distances through air (a breadth-first search over get_block, gameplay.rs:161-201, for a batch) ----------------------------------------
@@ -1053,44 +1004,11 @@ class Svo:
         Host (a NumPy array): synchronous.
         Device (a torch CUDA tensor): returns after enqueueing, without synchronising -- pair with sync(); fields is a uint8 tensor and info
         an int32 tensor of shape (N, 4) on the positions' device (flood_infos_to_numpy)."""
-        host = isinstance(positions, np.ndarray)
-        if len(positions.shape) != 2 or positions.shape[1] != 3:
-            raise TypeError("flood_points: positions must have shape (N, 3)")
-        count = int(positions.shape[0])
-        if not host and not getattr(positions, "is_cuda", False):
-            raise TypeError("flood_points: positions must be a NumPy array or a torch CUDA tensor")
+        mem, count, ptr, stride = _points("flood_points", "positions", positions)
         shape = flood_shape(size, seed_at, max_steps, pass_value, flags)
-        voxels = int(shape.size[0]) * int(shape.size[1]) * int(shape.size[2])
-        stride = int(field_stride) if field_stride else (voxels + 15) // 16 * 16
-        ptr, pos_stride = _ray_vectors("positions", positions, count, 3)
-        fields = None if fields is False else fields
-        info = None if info is False else info
-        if host:
-            if fields is True:
-                fields = np.zeros((count, stride), dtype=np.uint8)
-            elif fields is not None and (not isinstance(fields, np.ndarray) or fields.dtype != np.uint8 or fields.size < count * stride or not fields.flags.c_contiguous
-                                         or not fields.flags.writeable):
-                raise TypeError("flood_points: fields must be a writeable C-contiguous uint8 array of at least N x field_stride bytes")
-            if info is True:
-                info = np.zeros(count, dtype=FLOOD_INFO_DTYPE)
-            elif info is not None and (not isinstance(info, np.ndarray) or info.dtype != FLOOD_INFO_DTYPE or info.size != count or not info.flags.c_contiguous
-                                       or not info.flags.writeable):
-                raise TypeError("flood_points: info must be a writeable C-contiguous array of N hip.FLOOD_INFO_DTYPE records")
-            _check(lib().vx_flood_points(self._h, _vp(ptr), pos_stride, count, C.byref(shape), VX_MEM_HOST, None if fields is None else fields.ctypes.data_as(_vp),
-                                         int(field_stride), None if info is None else info.ctypes.data_as(_vp)))
-            return fields, info
-        import torch
-
-        if fields is True:
-            fields = torch.empty((count, stride), dtype=torch.uint8, device=positions.device)
-        elif fields is not None and (not fields.is_cuda or not fields.is_contiguous() or fields.numel() * fields.element_size() < count * stride):
-            raise TypeError("flood_points: fields must be a contiguous CUDA tensor of at least N x field_stride bytes")
-        if info is True:
-            info = torch.empty((count, 4), dtype=torch.int32, device=positions.device)
-        elif info is not None and (not info.is_cuda or not info.is_contiguous() or info.numel() * info.element_size() < count * FLOOD_INFO_DTYPE.itemsize):
-            raise TypeError("flood_points: info must be a contiguous CUDA tensor of at least N x 16 bytes")
-        _check(lib().vx_flood_points(self._h, _vp(ptr), pos_stride, count, C.byref(shape), VX_MEM_DEVICE, None if fields is None else _vp(fields.data_ptr()),
-                                     int(field_stride), None if info is None else _vp(info.data_ptr())))
+        fields = _fields_out("flood_points", _asked(fields, None), mem, count, shape, field_stride, positions)
+        info = _out("flood_points: info", _asked(info, None), mem, count, FLOOD_INFO_DTYPE, (count,), positions, "host")
+        _check(lib().vx_flood_points(self._h, ptr, stride, count, C.byref(shape), mem, _ptr(fields), int(field_stride), _ptr(info)))
         return fields, info
 
     # -- light levels (two breadth-first searches over get_block, gameplay.rs:161-201, for a batch of boxes) --------------------------------------------
@@ -1104,49 +1022,11 @@ class Svo:
         Host (a NumPy array): synchronous.
         Device (a torch CUDA tensor): returns after enqueueing, without synchronising -- pair with sync(); fields is a uint8 tensor and info
         an int32 tensor of shape (N, 4) on lo's device (light_infos_to_numpy)."""
-        host = isinstance(lo, np.ndarray)
-        if len(lo.shape) != 2 or lo.shape[1] != 3:
-            raise TypeError("light_boxes: lo must have shape (N, 3)")
-        count = int(lo.shape[0])
-        if not host and not getattr(lo, "is_cuda", False):
-            raise TypeError("light_boxes: lo must be a NumPy array or a torch CUDA tensor")
+        mem, count, ptr, stride = _lo_rows("light_boxes", lo)
         shape, table = light_shape(size, props, flags)
-        voxels = int(shape.size[0]) * int(shape.size[1]) * int(shape.size[2])
-        stride = int(field_stride) if field_stride else (voxels + 15) // 16 * 16
-        fields = True if fields is None else (None if fields is False else fields)
-        info = True if info is None else (None if info is False else info)
-        if host:
-            if lo.dtype != np.int32 or (count and (lo.strides[1] != 4 or lo.strides[0] % 4 or lo.strides[0] < 12)):
-                raise TypeError("light_boxes: lo must be int32 rows at a stride that is a multiple of 4 bytes and at least 12")
-            ptr, lo_stride = lo.ctypes.data, int(lo.strides[0]) if count else 12
-            if fields is True:
-                fields = np.zeros((count, stride), dtype=np.uint8)
-            elif fields is not None and (not isinstance(fields, np.ndarray) or fields.dtype != np.uint8 or fields.size < count * stride or not fields.flags.c_contiguous
-                                         or not fields.flags.writeable):
-                raise TypeError("light_boxes: fields must be a writeable C-contiguous uint8 array of at least N x field_stride bytes")
-            if info is True:
-                info = np.zeros(count, dtype=LIGHT_INFO_DTYPE)
-            elif info is not None and (not isinstance(info, np.ndarray) or info.dtype != LIGHT_INFO_DTYPE or info.size != count or not info.flags.c_contiguous
-                                       or not info.flags.writeable):
-                raise TypeError("light_boxes: info must be a writeable C-contiguous array of N hip.LIGHT_INFO_DTYPE records")
-            _check(lib().vx_light_boxes(self._h, _vp(ptr), lo_stride, count, C.byref(shape), VX_MEM_HOST, None if fields is None else fields.ctypes.data_as(_vp),
-                                        int(field_stride), None if info is None else info.ctypes.data_as(_vp)))
-            return fields, info
-        import torch
-
-        if lo.dtype != torch.int32 or (count and (lo.stride(1) != 1 or lo.stride(0) < 3)):
-            raise TypeError("light_boxes: lo must be int32 rows whose last axis is contiguous, at a stride of at least 3 elements")
-        ptr, lo_stride = lo.data_ptr(), 4 * int(lo.stride(0)) if count else 12
-        if fields is True:
-            fields = torch.empty((count, stride), dtype=torch.uint8, device=lo.device)
-        elif fields is not None and (not fields.is_cuda or not fields.is_contiguous() or fields.numel() * fields.element_size() < count * stride):
-            raise TypeError("light_boxes: fields must be a contiguous CUDA tensor of at least N x field_stride bytes")
-        if info is True:
-            info = torch.empty((count, 4), dtype=torch.int32, device=lo.device)
-        elif info is not None and (not info.is_cuda or not info.is_contiguous() or info.numel() * info.element_size() < count * LIGHT_INFO_DTYPE.itemsize):
-            raise TypeError("light_boxes: info must be a contiguous CUDA tensor of at least N x 16 bytes")
-        _check(lib().vx_light_boxes(self._h, _vp(ptr), lo_stride, count, C.byref(shape), VX_MEM_DEVICE, None if fields is None else _vp(fields.data_ptr()),
-                                    int(field_stride), None if info is None else _vp(info.data_ptr())))
+        fields = _fields_out("light_boxes", _asked(fields, True), mem, count, shape, field_stride, lo)
+        info = _out("light_boxes: info", _asked(info, True), mem, count, LIGHT_INFO_DTYPE, (count,), lo, "host")
+        _check(lib().vx_light_boxes(self._h, ptr, stride, count, C.byref(shape), mem, _ptr(fields), int(field_stride), _ptr(info)))
         del table  # (read during the call)
         return fields, info
 
@@ -1162,60 +1042,13 @@ class Svo:
         Host (a NumPy array): synchronous.
         Device (a torch CUDA tensor): returns after enqueueing, without synchronising -- pair with sync(); fields is a uint8 tensor, pieces an
         int32 tensor of shape (N, max_pieces, 4) and info one of shape (N, 8) on lo's device (label_pieces_to_numpy, label_infos_to_numpy)."""
-        host = isinstance(lo, np.ndarray)
-        if len(lo.shape) != 2 or lo.shape[1] != 3:
-            raise TypeError("label_boxes: lo must have shape (N, 3)")
-        count = int(lo.shape[0])
-        if not host and not getattr(lo, "is_cuda", False):
-            raise TypeError("label_boxes: lo must be a NumPy array or a torch CUDA tensor")
+        mem, count, ptr, stride = _lo_rows("label_boxes", lo)
         shape = label_shape(size, anchor_faces, max_pieces, max_steps, pass_value)
-        voxels = int(shape.size[0]) * int(shape.size[1]) * int(shape.size[2])
-        stride = int(field_stride) if field_stride else (voxels + 15) // 16 * 16
-        fields = True if fields is None else (None if fields is False else fields)
-        pieces = (True if shape.max_pieces else None) if pieces is None else (None if pieces is False else pieces)
-        info = True if info is None else (None if info is False else info)
-        if host:
-            if lo.dtype != np.int32 or (count and (lo.strides[1] != 4 or lo.strides[0] % 4 or lo.strides[0] < 12)):
-                raise TypeError("label_boxes: lo must be int32 rows at a stride that is a multiple of 4 bytes and at least 12")
-            ptr, lo_stride = lo.ctypes.data, int(lo.strides[0]) if count else 12
-            if fields is True:
-                fields = np.zeros((count, stride), dtype=np.uint8)
-            elif fields is not None and (not isinstance(fields, np.ndarray) or fields.dtype != np.uint8 or fields.size < count * stride or not fields.flags.c_contiguous
-                                         or not fields.flags.writeable):
-                raise TypeError("label_boxes: fields must be a writeable C-contiguous uint8 array of at least N x field_stride bytes")
-            if pieces is True:
-                pieces = np.zeros((count, shape.max_pieces), dtype=LABEL_PIECE_DTYPE)
-            elif pieces is not None and (not isinstance(pieces, np.ndarray) or pieces.dtype != LABEL_PIECE_DTYPE or pieces.size != count * shape.max_pieces
-                                         or not pieces.flags.c_contiguous or not pieces.flags.writeable):
-                raise TypeError("label_boxes: pieces must be a writeable C-contiguous array of N x max_pieces hip.LABEL_PIECE_DTYPE records")
-            if info is True:
-                info = np.zeros(count, dtype=LABEL_INFO_DTYPE)
-            elif info is not None and (not isinstance(info, np.ndarray) or info.dtype != LABEL_INFO_DTYPE or info.size != count or not info.flags.c_contiguous
-                                       or not info.flags.writeable):
-                raise TypeError("label_boxes: info must be a writeable C-contiguous array of N hip.LABEL_INFO_DTYPE records")
-            _check(lib().vx_label_boxes(self._h, _vp(ptr), lo_stride, count, C.byref(shape), VX_MEM_HOST, None if fields is None else fields.ctypes.data_as(_vp),
-                                        int(field_stride), None if pieces is None else pieces.ctypes.data_as(_vp), None if info is None else info.ctypes.data_as(_vp)))
-            return fields, pieces, info
-        import torch
-
-        if lo.dtype != torch.int32 or (count and (lo.stride(1) != 1 or lo.stride(0) < 3)):
-            raise TypeError("label_boxes: lo must be int32 rows whose last axis is contiguous, at a stride of at least 3 elements")
-        ptr, lo_stride = lo.data_ptr(), 4 * int(lo.stride(0)) if count else 12
-        if fields is True:
-            fields = torch.empty((count, stride), dtype=torch.uint8, device=lo.device)
-        elif fields is not None and (not fields.is_cuda or not fields.is_contiguous() or fields.numel() * fields.element_size() < count * stride):
-            raise TypeError("label_boxes: fields must be a contiguous CUDA tensor of at least N x field_stride bytes")
-        if pieces is True:
-            pieces = torch.empty((count, shape.max_pieces, 4), dtype=torch.int32, device=lo.device)
-        elif pieces is not None and (not pieces.is_cuda or not pieces.is_contiguous()
-                                     or pieces.numel() * pieces.element_size() < count * shape.max_pieces * LABEL_PIECE_DTYPE.itemsize):
-            raise TypeError("label_boxes: pieces must be a contiguous CUDA tensor of at least N x max_pieces x 16 bytes")
-        if info is True:
-            info = torch.empty((count, 8), dtype=torch.int32, device=lo.device)
-        elif info is not None and (not info.is_cuda or not info.is_contiguous() or info.numel() * info.element_size() < count * LABEL_INFO_DTYPE.itemsize):
-            raise TypeError("label_boxes: info must be a contiguous CUDA tensor of at least N x 32 bytes")
-        _check(lib().vx_label_boxes(self._h, _vp(ptr), lo_stride, count, C.byref(shape), VX_MEM_DEVICE, None if fields is None else _vp(fields.data_ptr()),
-                                    int(field_stride), None if pieces is None else _vp(pieces.data_ptr()), None if info is None else _vp(info.data_ptr())))
+        most = shape.max_pieces
+        fields = _fields_out("label_boxes", _asked(fields, True), mem, count, shape, field_stride, lo)
+        pieces = _out("label_boxes: pieces", _asked(pieces, most > 0), mem, count * most, LABEL_PIECE_DTYPE, (count, most), lo, "host", "N x max_pieces")
+        info = _out("label_boxes: info", _asked(info, True), mem, count, LABEL_INFO_DTYPE, (count,), lo, "host")
+        _check(lib().vx_label_boxes(self._h, ptr, stride, count, C.byref(shape), mem, _ptr(fields), int(field_stride), _ptr(pieces), _ptr(info)))
         return fields, pieces, info
 
     # -- walking distances and paths (a search over get_block, gameplay.rs:161-201, on the walking graph, for a batch) --------------------------------
@@ -1231,62 +1064,17 @@ class Svo:
         Host (a NumPy array): synchronous.
         Device (a torch CUDA tensor): returns after enqueueing, without synchronising -- pair with sync(); fields is a uint8 tensor, info an
         int32 tensor of shape (N, 8) (walk_infos_to_numpy) and paths an int32 tensor of shape (N, path_capacity) on the positions' device."""
-        host = isinstance(positions, np.ndarray)
-        if len(positions.shape) != 2 or positions.shape[1] != 3:
-            raise TypeError("walk_points: positions must have shape (N, 3)")
-        count = int(positions.shape[0])
-        if not host and not getattr(positions, "is_cuda", False):
-            raise TypeError("walk_points: positions must be a NumPy array or a torch CUDA tensor")
-        if goals is not None and isinstance(goals, np.ndarray) != host:
+        mem, count, ptr, stride = _points("walk_points", "positions", positions)
+        if goals is not None and isinstance(goals, np.ndarray) != (mem == VX_MEM_HOST):
             raise TypeError("walk_points: goals must lie where the positions lie")
         shape = walk_shape(size, seed_at, max_steps, pass_value, height, climb, drop, path_capacity, flags)
-        voxels = int(shape.size[0]) * int(shape.size[1]) * int(shape.size[2])
-        stride = int(field_stride) if field_stride else (voxels + 15) // 16 * 16
-        ptr, pos_stride = _ray_vectors("positions", positions, count, 3)
-        goal_ptr, goal_stride = (None, 0) if goals is None else _ray_vectors("goals", goals, count, 3)
-        fields = None if fields is False else fields
-        info = None if info is False else info
-        if paths is None:
-            paths = goals is not None and int(path_capacity) > 0
-        paths = None if paths is False else paths
+        goal_ptr, goal_stride = (None, 0) if goals is None else _ray_vectors("goals", goals, count, 3, "walk_points")
         cap = int(path_capacity)
-        if host:
-            if fields is True:
-                fields = np.zeros((count, stride), dtype=np.uint8)
-            elif fields is not None and (not isinstance(fields, np.ndarray) or fields.dtype != np.uint8 or fields.size < count * stride or not fields.flags.c_contiguous
-                                         or not fields.flags.writeable):
-                raise TypeError("walk_points: fields must be a writeable C-contiguous uint8 array of at least N x field_stride bytes")
-            if info is True:
-                info = np.zeros(count, dtype=WALK_INFO_DTYPE)
-            elif info is not None and (not isinstance(info, np.ndarray) or info.dtype != WALK_INFO_DTYPE or info.size != count or not info.flags.c_contiguous
-                                       or not info.flags.writeable):
-                raise TypeError("walk_points: info must be a writeable C-contiguous array of N hip.WALK_INFO_DTYPE records")
-            if paths is True:
-                paths = np.zeros((count, cap), dtype=np.uint32)
-            elif paths is not None and (not isinstance(paths, np.ndarray) or paths.dtype != np.uint32 or paths.size < count * cap or not paths.flags.c_contiguous
-                                        or not paths.flags.writeable):
-                raise TypeError("walk_points: paths must be a writeable C-contiguous uint32 array of at least N x path_capacity entries")
-            _check(lib().vx_walk_points(self._h, _vp(ptr), pos_stride, None if goal_ptr is None else _vp(goal_ptr), goal_stride, count, C.byref(shape), VX_MEM_HOST,
-                                        None if fields is None else fields.ctypes.data_as(_vp), int(field_stride), None if paths is None else paths.ctypes.data_as(_vp),
-                                        None if info is None else info.ctypes.data_as(_vp)))
-            return fields, info, paths
-        import torch
-
-        if fields is True:
-            fields = torch.empty((count, stride), dtype=torch.uint8, device=positions.device)
-        elif fields is not None and (not fields.is_cuda or not fields.is_contiguous() or fields.numel() * fields.element_size() < count * stride):
-            raise TypeError("walk_points: fields must be a contiguous CUDA tensor of at least N x field_stride bytes")
-        if info is True:
-            info = torch.empty((count, 8), dtype=torch.int32, device=positions.device)
-        elif info is not None and (not info.is_cuda or not info.is_contiguous() or info.numel() * info.element_size() < count * WALK_INFO_DTYPE.itemsize):
-            raise TypeError("walk_points: info must be a contiguous CUDA tensor of at least N x 32 bytes")
-        if paths is True:
-            paths = torch.empty((count, cap), dtype=torch.int32, device=positions.device)
-        elif paths is not None and (not paths.is_cuda or not paths.is_contiguous() or paths.numel() * paths.element_size() < count * cap * 4):
-            raise TypeError("walk_points: paths must be a contiguous CUDA tensor of at least N x path_capacity x 4 bytes")
-        _check(lib().vx_walk_points(self._h, _vp(ptr), pos_stride, None if goal_ptr is None else _vp(goal_ptr), goal_stride, count, C.byref(shape), VX_MEM_DEVICE,
-                                    None if fields is None else _vp(fields.data_ptr()), int(field_stride), None if paths is None else _vp(paths.data_ptr()),
-                                    None if info is None else _vp(info.data_ptr())))
+        fields = _fields_out("walk_points", _asked(fields, None), mem, count, shape, field_stride, positions)
+        info = _out("walk_points: info", _asked(info, None), mem, count, WALK_INFO_DTYPE, (count,), positions, "host")
+        paths = _out("walk_points: paths", _asked(paths, goals is not None and cap > 0), mem, count * cap, _U32, (count, cap), positions, False, "N x path_capacity", "entries")
+        _check(lib().vx_walk_points(self._h, ptr, stride, None if goal_ptr is None else _vp(goal_ptr), goal_stride, count, C.byref(shape), mem, _ptr(fields),
+                                    int(field_stride), _ptr(paths), _ptr(info)))
         return fields, info, paths
 
     # -- Physics::step_many (src/systems/physics.rs:122-136), on the device ---------------------------------------

@@ -12,8 +12,9 @@ ROOT = Path(__file__).resolve().parents[2]
 sys.path.insert(0, str(ROOT))
 from _pkg import csrc_hash  # noqa: E402
 
-out = {"_comment": "HBM-side traffic and instruction counts of the render kernel per launch, from separate rocprofv3 --pmc passes (profiles/round6/profile_r6.sh: "
-                   "C3, bench.py --frames-in-flight 1; profiles/round6/c4_counters.sh: C4, deep_frames.py, VX_FRAMES_IN_FLIGHT=1; summaries next to this file). "
+out = {"_comment": "HBM-side traffic and instruction counts of the render kernel per launch, from separate rocprofv3 --pmc passes, one counter group a run (the groups of "
+                   "profiles/round6/profile_r6.sh: C3, bench.py --frames-in-flight 1, the mean of a run's launches; those of profiles/round6/c4_counters.sh: C4, "
+                   "deep_frames.py, VX_FRAMES_IN_FLIGHT=1, the mean of a run's last four launches -- pmc_summary.py). "
                    "read_bytes = 128 x TCC_EA0_RDREQ_128B + 64 x TCC_EA0_RDREQ_64B + 32 x TCC_EA0_RDREQ_32B: the memory side's read requests by their size -- nearly "
                    "all of this kernel's are 128-byte requests, which FETCH_SIZE (KB, x 1024) tallies at 64 bytes each: MI355X_MICROARCH.md's gfx950 correction "
                    "(double it) applies to these 8-byte gathers too (round 5 argued it did not; the request-size counters settle it). WRITE_SIZE (KB) is exact "

@@ -435,6 +435,14 @@ __global__ __launch_bounds__(64, min_waves_of(SVO, HITS)) void render_persistent
                 if (why) {
                     state = LaneState(why);
                     tr.iter &= 0x8fffffffu;
+                    // (the listed build's trip parks a ray that is led into the voxel it started in as at-a-leaf too -- vx_loop_gfx950.hpp, VX_LOOP_ONE_EXIT: it
+                    // is the one whose t_min is not above 0, and its iteration is taken back, as the compiler's loop reports it)
+                    if constexpr (FOREIGN == kForeignRerun && VX_LOOP_ONE_EXIT != 0) {
+                        if (state == kLeaf && !(tr.t_min > 0.0f)) {
+                            state = kForeign;
+                            --tr.iter;
+                        }
+                    }
                 }
             }
         } else

@@ -9,14 +9,17 @@
 // costs the SIMD about 2 cycles -- a scalar mask operation 3.4, a taken branch 8, a compare into a scalar pair 3.4, a select out of
 // one 3.0 -- and the traversal loop as the compiler lays it out (78-81 vector + 41-50 scalar instructions per trip, most of the scalar
 // ones execution-mask bookkeeping around its PUSH / ADVANCE / POP regions, compares parked in scalar pairs) runs at 91 % of what
-// that mix costs: the loop is issue bound, and the way to a faster frame is fewer and cheaper instructions per trip. Here a trip is
-// 72 vector + 13 scalar + 6 memory instructions:
+// that mix costs: the loop is issue bound, and the way to a faster frame is fewer and cheaper instructions per trip. Here a trip of
+// the merged tail is 62 vector + 14 scalar + 6 memory instructions, POP and loop control included (ESVO world, 13 levels, in lockstep;
+// the build that lists a CSVO world's inside-voxel rays: 60 + 14 + 6; profiles/loop_diet/static_count.py counts them from the assembly):
 //   * compares go to VCC and are consumed by the next instruction (v_cndmask_e32, v_cmpx), one mask (`push`) lives in a scalar pair;
 //   * "is a child AND ..." is folded into the compared value (t_min or +inf) instead of and-ing masks;
 //   * lanes that stop traversing (at a leaf / led into a voxel / out of the octree) are marked in `iter` itself -- bit 31 = parked,
 //     bits 28..30 = the TravStatus -- by one v_add under a narrowed execution mask; the caller decodes it once per service phase;
 //   * the cell size is derived from the scale (one shift-add) instead of being carried and selected;
-//   * PUSH's five register updates and POP's run under their lanes' execution masks as plain moves / loads into the state registers.
+//   * PUSH's five register updates and POP's run under their lanes' execution masks as plain moves / loads into the state registers;
+//   * in the build that lists inside-voxel rays the trip has one leaf exit for both kinds of lane that stop there, and the caller tells
+//     them apart once a service phase (VX_LOOP_ONE_EXIT).
 // Variants: the image read through a buffer resource of 8-byte records or (beyond 4 GiB) a 64-bit base; a stack of 13 three-word levels or of 16 levels with
 // a 16-bit third plane; worlds in ESVO or CSVO (what happens to a ray that is led into a voxel); with or without a trip counter.
 // Hazards (no hazard recognizer looks inside an asm block): no DPP / SDWA / packed / transcendental / lane-access instructions, no SGPR
@@ -24,6 +27,12 @@
 #pragma once
 
 #include "vx_device.hpp"
+
+// 1 = the listed build's trip parks every lane at a reached leaf as kTravAtLeaf and render_persistent tells the rays that were led into their voxel
+// apart once a service phase; 0 = the trip tells them apart itself, three instructions more (A/B builds)
+#ifndef VX_LOOP_ONE_EXIT
+#define VX_LOOP_ONE_EXIT 1
+#endif
 
 namespace vxd {
 
@@ -45,13 +54,21 @@ __device__ __forceinline__ constexpr uint32_t loop_exit_bits(TravStatus s) { ret
     "s_or_b64 %[waiting], %[waiting], vcc\n"                                                                                       \
     "s_andn2_b64 exec, %[s_trav], %[s_save]\n"
 // (worlds of at most 12 levels, whose rays led into a voxel are LISTED and run on the world's bytes afterwards -- render_persistent's kForeignRerun build, C3's:
-// nothing waits for anything, so nothing is counted and the loop has no second exit: five instructions a trip less than the walk's build)
+// nothing waits for anything, so nothing is counted and the loop has no second exit. Both kinds of lane leave the loop in this trip and differ only in the
+// code they would carry away, so the trip parks them all as at-a-leaf; render_persistent, behind the loop call, makes a lane whose t_min is not above 0
+// kForeign and takes its iteration back, once a service phase: two instructions a trip instead of the walk's build's seven)
+#if VX_LOOP_ONE_EXIT
+#define VX_LEAF_EXITS_CSVO_LISTED                                                                                                  \
+    "v_add_u32_e32 %[iter], 0xa0000000, %[iter]\n"               /* parked | kTravAtLeaf << 28 (or kTravForeign: the caller tells) */ \
+    "s_andn2_b64 exec, %[s_trav], exec\n"
+#else
 #define VX_LEAF_EXITS_CSVO_LISTED                                                                                                  \
     "s_mov_b64 %[s_save], exec\n"                                                                                                  \
     "v_add_u32_e32 %[iter], 0xdfffffff, %[iter]\n"               /* parked | kTravForeign << 28, and the iteration taken back */   \
     "v_cmpx_lt_f32_e32 vcc, 0, %[tmin]\n"                                                                                          \
     "v_add_u32_e32 %[iter], 0xc0000001, %[iter]\n"               /* t_min > 0 after all: parked | kTravAtLeaf << 28, the iteration counted */ \
     "s_andn2_b64 exec, %[s_trav], %[s_save]\n"
+#endif
 // ... and as soon as one of them waits (`waiting`: a mask; at entry non-zero if lanes wait from earlier rounds), the wave leaves the loop for the service phase that walks them together (the others' rays pause
 // where they are): a shadow ray that starts inside its voxel gets there after `depth` trips, all such rays of a batch in the same trip --
 // waiting for the other rays to END first would run the batch's two halves one after the other

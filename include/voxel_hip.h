@@ -323,6 +323,24 @@ typedef struct vx_label_info {
                                 box; flags: 0 or VX_LABEL_CUT */
 } vx_label_info;
 
+#define VX_DISTANCE_NONE   0xFFFFu   /* a field's entry, and vx_distance_info.farthest: the box holds no target */
+#define VX_DISTANCE_TO_AIR 1u        /* flags: the target set is complemented within the box */
+/* What every query of a vx_distance_boxes call shares; 32 bytes; read on the host during the call. */
+typedef struct vx_distance_shape {
+    uint32_t size[3];        /* the box of each query, 1..32 an axis */
+    uint32_t pass_value;     /* 0, or a BlockId that counts as air (vx_label_shape's); 0 with a match_value */
+    uint32_t match_value;    /* 0: every solid cell is a target; else only the cells of this BlockId are */
+    uint32_t flags;          /* 0 or VX_DISTANCE_TO_AIR */
+    uint32_t _pad[2];        /* ignored */
+} vx_distance_shape;
+/* What the distances of a box amount to (vx_distance_boxes); 16 bytes, one 16-byte store. */
+typedef struct vx_distance_info {
+    uint32_t targets;        /* the number of target cells */
+    uint32_t farthest;       /* the largest value of the field; VX_DISTANCE_NONE: no target */
+    uint32_t where;          /* rx | ry << 8 | rz << 16 of the first cell in the field's order that holds `farthest`: the roomiest cell */
+    uint32_t faces;          /* bit f set when a target lies on face f of the box, numbered like vx_flood_info.faces */
+} vx_distance_info;
+
 /* Optional per-pixel record of what trace_ray saw (world.glsl:27-90) -- the "hit position, depth" outputs
  * used for parity checks; not part of the reference's surface. */
 typedef struct vx_hit {
@@ -834,6 +852,44 @@ int vx_walk_points(vx_context* ctx, const void* pos, uint32_t pos_stride, const 
  * or written). Before the first commit: VX_ERR_STATE. */
 int vx_label_boxes(vx_context* ctx, const void* lo, uint32_t lo_stride, uint32_t count, const vx_label_shape* shape, int memory,
                    uint8_t* fields, uint32_t field_stride, vx_label_piece* pieces, vx_label_info* info);
+/* The squared distance to the nearest block, per cell, in each of `count` boxes of the world the device holds: "does a creature of radius r
+ * fit here, and where is the roomiest cell", "how deep inside the rock is this ore", "how far is the nearest lava" -- the straight-line
+ * metric from every block at once, where vx_flood_points counts 6-connected steps from one seed. The reference would loop get_block
+ * (gameplay.rs:161-201) over the neighbourhood and run a distance transform on the host. Everything is integer and exact.
+ * Boxes. Box k is [lo_k, lo_k + size): lo_k an int32[3] read at lo + k * lo_stride under vx_light_boxes' rules (4-byte aligned, the stride a
+ * multiple of 4 and at least 12, the memory kind of the call), kept modulo 2^32: the box may be negative or overhang the world. Each size
+ * component is 1..32. Cells outside the box do not exist: the box bounds the search.
+ * Targets. A cell holds vx_block_points' value at its centre; outside the world is 0; a LOD voxel gives its value to each of its fine
+ * voxels. With match_value == 0 a cell is a target when it is solid by vx_label_boxes' rule: non-zero and different from a non-zero
+ * pass_value. With match_value != 0 a cell is a target when its value equals match_value; pass_value must then be 0. Under
+ * VX_DISTANCE_TO_AIR the target set is complemented within the box: the distance to the nearest cell that is NOT such a block, which is
+ * the depth inside rock.
+ * The field. `fields` points at uint16_t entries (a void*, as a binding may hold them as either 16-bit integer kind): one a cell, x fastest, in
+ * vx_read_region's layout, the least (rx-tx)^2 + (ry-ty)^2 + (rz-tz)^2 over the target cells (tx, ty, tz) of the box. A target cell has 0; the
+ * largest possible value is 3 * 31^2 = 2883. With no target in the box every cell is VX_DISTANCE_NONE. Query k's field is at (uint8_t*)fields +
+ * k * field_stride; field_stride is in BYTES, a multiple of 16 and at least 2 * voxels, or 0: 2 * voxels rounded up to 16. The entries from the
+ * voxel count up to that multiple of 16 bytes are written VX_DISTANCE_NONE; bytes beyond are not touched.
+ * What holds across box choices. Let g be a cell's distance in cells to the outside of the box: the least of rx + 1, size.x - rx and the
+ * same for y and z. A value v <= g^2 is the value ANY larger box would give -- a nearer target outside the box would lie at least g cells
+ * away along some axis. A caller who wants exact values up to radius r inside a section asks for the section with a margin of r, as
+ * vx_light_boxes' caller asks for a margin of 15.
+ * The record. targets: the number of target cells. farthest: the largest value of the field, VX_DISTANCE_NONE with no target. where: rx |
+ * ry << 8 | rz << 16 of the first cell in the field's order (least rz, then ry, then rx) that holds `farthest` -- the roomiest cell; with
+ * no target that is cell 0. faces: bit f set when a target lies on face f of the box, numbered like vx_flood_info.faces.
+ * Outputs. At least one of fields and info is given; with fields == NULL only the records are written.
+ * One workgroup of four waves a box, one launch: the box's targets as rows of 32 bits (each brick of 8 x 8 x 8 voxels entered once), the
+ * distance along x read off a row's bits, then one exact min-plus pass along y and one along z (squared Euclidean distance separates
+ * exactly in integers). No loop depends on the world: a query's time is bounded whatever the world holds. No workgroup waits for another.
+ * Memory kinds, ordering and fences are vx_label_boxes'. VX_MEM_HOST: synchronous, through pinned memory; one launch, one wait.
+ * VX_MEM_DEVICE (fields and info aligned to 16 bytes): enqueued on the context's stream, ordered behind the commits made so far and
+ * earlier batch calls; later commits wait for it; the fence is vx_sync. `shape` itself is read during the call.
+ * VX_ERR_INVALID_ARGUMENT (its message names the field; nothing is written): a null ctx; an unknown memory kind; with count > 0: a null
+ * shape or lo; fields and info both null; a stride or an alignment that breaks the rules above; a size component of 0 or above 32; an
+ * unknown flag bit; match_value != 0 together with pass_value != 0; a field_stride that breaks the rule; count > 1048576 (2^20); count *
+ * field_stride above 16777216 (2^24) bytes; a misaligned device output; an output whose bytes, from its first to its last, overlap those
+ * of lo or of the other output. count == 0: VX_OK (nothing is read or written). Before the first commit: VX_ERR_STATE. */
+int vx_distance_boxes(vx_context* ctx, const void* lo, uint32_t lo_stride, uint32_t count, const vx_distance_shape* shape, int memory,
+                      void* fields, uint32_t field_stride, vx_distance_info* info);
 /* Physics::step_many (src/systems/physics.rs:122-136) `steps` times over `count` entities in ONE kernel launch, against the world as last
  * committed: per step and entity the AABB's fan of axis-parallel picker rays (Aabb::generate_picker_tasks, svo_picker.rs:183-243: max_dst
  * 10), folded into six contact distances (parse_picker_results, svo_picker.rs:245-299), then Physics::update_entity and

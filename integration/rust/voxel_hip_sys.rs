@@ -381,6 +381,32 @@ pub const VX_LABEL_ALL_FACES: u32 = 0x3F;
 /// `vx_label_info::flags`: the step budget ran out
 pub const VX_LABEL_CUT: u32 = 0x1;
 
+/// What every query of a `vx_distance_boxes` call shares: the box of each query (1..=32 cells an axis), a block id that counts as air (0: none;
+/// 0 with a match_value), the block id whose cells are the targets (0: every solid cell), and flags (0 or VX_DISTANCE_TO_AIR).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct vx_distance_shape {
+    pub size: [u32; 3],
+    pub pass_value: u32,
+    pub match_value: u32,
+    pub flags: u32,
+    pub _pad: [u32; 2],
+}
+/// What the distances of a box amount to (`vx_distance_boxes`): the target cells, the largest value of the field (VX_DISTANCE_NONE: no
+/// target), the first cell in the field's order that holds it as rx | ry << 8 | rz << 16, and the faces of the box a target lies on.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct vx_distance_info {
+    pub targets: u32,
+    pub farthest: u32,
+    pub r#where: u32,
+    pub faces: u32,
+}
+/// a field's entry, and `vx_distance_info::farthest`, when the box holds no target (the header's value, written in hexadecimal as there)
+pub const VX_DISTANCE_NONE: u16 = 0xFFFF;
+/// `vx_distance_shape::flags`: the target set is complemented within the box
+pub const VX_DISTANCE_TO_AIR: u32 = 0x1;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct vx_stats {
@@ -423,6 +449,8 @@ const _: () = assert!(std::mem::size_of::<vx_walk_info>() == 32);
 const _: () = assert!(std::mem::size_of::<vx_label_shape>() == 32);
 const _: () = assert!(std::mem::size_of::<vx_label_piece>() == 16);
 const _: () = assert!(std::mem::size_of::<vx_label_info>() == 32);
+const _: () = assert!(std::mem::size_of::<vx_distance_shape>() == 32);
+const _: () = assert!(std::mem::size_of::<vx_distance_info>() == 16);
 const _: () = assert!(std::mem::size_of::<MaterialInstance>() == 32); // svo_registry.rs:29-40 is #[repr(C)]
 const _: () = assert!(std::mem::size_of::<PickerTask>() == 48 && std::mem::size_of::<PickerResult>() == 48); // svo_picker.rs:13-32
 
@@ -507,6 +535,12 @@ extern "C" {
     /// shape.max_pieces, its record at info[k]; any output may be null, not all; `memory`: VX_MEM_HOST / VX_MEM_DEVICE (all three aligned to 16)
     pub fn vx_label_boxes(ctx: *mut vx_context, lo: *const c_void, lo_stride: u32, count: u32, shape: *const vx_label_shape, memory: c_int,
                           fields: *mut u8, field_stride: u32, pieces: *mut vx_label_piece, info: *mut vx_label_info) -> c_int;
+    /// the squared distance from every cell of the boxes [lo_k, lo_k + shape.size), lo_k an int32[3] at lo + k * lo_stride, to the nearest target
+    /// cell of the box; box k's field (a u16 a cell, x fastest, VX_DISTANCE_NONE without a target) at fields + k * field_stride BYTES (a multiple of
+    /// 16, 0 = twice the voxel count rounded up to 16), its record at info[k]; either output may be null, not both; `memory`: VX_MEM_HOST /
+    /// VX_MEM_DEVICE (both aligned to 16)
+    pub fn vx_distance_boxes(ctx: *mut vx_context, lo: *const c_void, lo_stride: u32, count: u32, shape: *const vx_distance_shape, memory: c_int,
+                             fields: *mut c_void, field_stride: u32, info: *mut vx_distance_info) -> c_int;
     /// Physics::step_many (physics.rs:122-136) `steps` times for `count` entities in one launch; `memory`: VX_MEM_HOST / VX_MEM_DEVICE
     pub fn vx_physics_step(ctx: *mut vx_context, entities: *mut vx_entity, count: u32, memory: c_int, delta_time: f32, steps: u32,
                            contacts: *mut vx_aabb_result) -> c_int;

@@ -1,4 +1,4 @@
-// libvoxelhip.so, the block entry points of include/voxel_hip.h (vx_block_points to vx_label_boxes): each one's argument checks (the rules of
+// libvoxelhip.so, the block entry points of include/voxel_hip.h (vx_block_points to vx_distance_boxes): each one's argument checks (the rules of
 // the vx_*.hpp beside this file), the launches of its kernel (kernels_blocks.h), and for a host-memory call the pinned scratch the kernel
 // reads and writes through (csrc/vx_pinned_pool.hpp), laid out and packed by vx_block_scratch.hpp: lay out, pack, launch, wait, copy out.
 // A further translation unit on the context, like raycast_runtime.cpp: what it needs of the context is vx_context.hpp's (runtime.cpp).
@@ -463,5 +463,35 @@ int vx_label_boxes(vx_context* ctx, const void* lo, uint32_t lo_stride, uint32_t
     if (info) std::memcpy(info, s.host() + at_info, info_bytes);
     if (pieces) std::memcpy(pieces, s.host() + at_pieces, piece_bytes);
     if (fields) vxb::spread_fields(fields, stride, s.host() + at_fields, packed, count);
+    return VX_OK;
+}
+
+int vx_distance_boxes(vx_context* ctx, const void* lo, uint32_t lo_stride, uint32_t count, const vx_distance_shape* shape, int memory, void* fields,
+                      uint32_t field_stride, vx_distance_info* info) {
+    static_assert(sizeof(vx_distance_info) == 16 && sizeof(vx_distance_shape) == 32, "the ABI's record sizes");
+    const char* refused = vxb::check_distance(lo, lo_stride, count, shape, fields, field_stride, info);
+    if (int rc = enter("distance_boxes", memory, refused, count && memory == VX_MEM_DEVICE, {{fields, 16, "fields"}, {info, 16, "info"}}, ctx)) return rc;
+    VX_LOCK(ctx);
+    if (count == 0) return VX_OK;
+    const uint32_t packed = vxb::distance_field_bytes(*shape), stride = field_stride ? field_stride : packed;  // (bytes)
+    const OnBytes w(ctx);
+
+    if (memory == VX_MEM_DEVICE) return enqueued(ctx, vxk::launch_distance_boxes(w.variant, ctx->stream, w.scene, lo, lo_stride, count, *shape, static_cast<uint16_t*>(fields), stride, info));
+
+    // the boxes packed at stride 12 | the records | the fields, each twice the voxel count rounded up to 16: the bytes a query writes, which
+    // go to the caller's stride from there (every part behind the boxes at a multiple of 16)
+    vxb::ScratchLayout lay;
+    const size_t at_lo = lay.take(vxb::packed3_bytes(lo, lo_stride, count));
+    const size_t info_bytes = info ? size_t(count) * sizeof(vx_distance_info) : 0, at_info = lay.take(info_bytes, 16);
+    const size_t at_fields = lay.take(fields ? size_t(count) * packed : 0, 16);
+    vxrt::PinnedScratch s(ctx);
+    if (int rc = s.reserve(lay.end)) return rc;
+    vxb::pack3(s.host() + at_lo, lo, lo_stride, count);
+    HIP_TRY(vxk::launch_distance_boxes(w.variant, ctx->stream, w.scene, s.dev() + at_lo, 12, count, *shape,
+                                       fields ? reinterpret_cast<uint16_t*>(s.dev() + at_fields) : nullptr, packed,
+                                       info ? reinterpret_cast<vx_distance_info*>(s.dev() + at_info) : nullptr));
+    if (int rc = s.wait()) return rc;  // synchronous, like vx_label_boxes' host-memory call
+    if (info) std::memcpy(info, s.host() + at_info, info_bytes);
+    if (fields) vxb::spread_fields(static_cast<uint8_t*>(fields), stride, s.host() + at_fields, packed, count);
     return VX_OK;
 }

@@ -6,6 +6,7 @@
 #include "vx_args.hpp"
 #include "vx_blocks.hpp"
 #include "vx_boxes.hpp"
+#include "vx_distance.hpp"
 #include "vx_flood.hpp"
 #include "vx_label.hpp"
 #include "vx_light.hpp"
@@ -89,5 +90,13 @@ hipError_t launch_walk_points(int svo, hipStream_t stream, const vxd::SceneArgs&
 // bytes, 16-byte aligned. Device-visible memory that overlaps no input.
 hipError_t launch_label_boxes(int svo, hipStream_t stream, const vxd::SceneArgs& sc, const void* lo, uint32_t lo_stride, uint32_t count, const vx_label_shape& shape,
                               uint8_t* fields, uint32_t field_stride, vx_label_piece* pieces, vx_label_info* info);
+
+// `count` (1..2^20) workgroups of 256 threads, one box a workgroup: an int32[3] at lo + i * lo_stride (4-byte aligned, the stride a multiple of
+// 4 and at least 12); shape: within vxb::check_distance's rules (refused here too: the kernel indexes LDS by its size); fields (may be null:
+// records only): 16-byte aligned, box i's entries at (uint8_t*)fields + i * field_stride, field_stride in bytes, a multiple of 16 and at least
+// twice the voxel count, of which twice the voxel count rounded up to 16 are written; info (may be null, not both): `count` records of 16
+// bytes, 16-byte aligned. Device-visible memory that overlaps no input.
+hipError_t launch_distance_boxes(int svo, hipStream_t stream, const vxd::SceneArgs& sc, const void* lo, uint32_t lo_stride, uint32_t count,
+                                 const vx_distance_shape& shape, uint16_t* fields, uint32_t field_stride, vx_distance_info* info);
 
 }  // namespace vxk

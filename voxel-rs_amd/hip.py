@@ -76,6 +76,11 @@ LABEL_PIECE_DTYPE = np.dtype([("cells", "<u4"), ("lo", "<u4"), ("hi", "<u4"), ("
 LABEL_INFO_DTYPE = np.dtype([("solid", "<u4"), ("held", "<u4"), ("pieces", "<u4"), ("loose", "<u4"), ("more", "<u4"), ("steps", "<u4"), ("faces", "<u4"),
                              ("flags", "<u4")])
 VX_LABEL_MAX_PIECES, VX_LABEL_MAX_STEPS, VX_LABEL_AIR, VX_LABEL_MORE, VX_LABEL_HELD, VX_LABEL_ALL_FACES, VX_LABEL_CUT = 250, 4096, 0x00, 0xFE, 0xFF, 0x3F, 1
+# vx_distance_info (vx_distance_boxes): what the distances of a box amount to -- the target cells, the largest value of the field, the first cell in
+# the field's order that holds it (rx | ry << 8 | rz << 16), the faces of the box a target lies on. A field is one uint16 a cell: the squared
+# distance to the nearest target cell of the box, or VX_DISTANCE_NONE
+DISTANCE_INFO_DTYPE = np.dtype([("targets", "<u4"), ("farthest", "<u4"), ("where", "<u4"), ("faces", "<u4")])
+VX_DISTANCE_NONE, VX_DISTANCE_TO_AIR = 0xFFFF, 1
 VX_DIR_NEG_X, VX_DIR_POS_X, VX_DIR_NEG_Y, VX_DIR_POS_Y, VX_DIR_NEG_Z, VX_DIR_POS_Z = range(6)
 VX_SCAN_NONE = -0x80000000
 VX_SCAN_TO_EDGE = 0xFFFFFFFF
@@ -84,6 +89,7 @@ assert HIT_DTYPE.itemsize == 48 and PICKER_TASK_DTYPE.itemsize == 48 and PICKER_
 assert ENTITY_DTYPE.itemsize == 64 and AABB_RESULT_DTYPE.itemsize == 24 and RAY_HIT_DTYPE.itemsize == 32 and SCAN_HIT_DTYPE.itemsize == 16
 assert BLOCK_AT_DTYPE.itemsize == 8 and BOX_HIT_DTYPE.itemsize == 32 and FLOOD_INFO_DTYPE.itemsize == 16 and LIGHT_INFO_DTYPE.itemsize == 16
 assert WALK_INFO_DTYPE.itemsize == 32 and MOVE_HIT_DTYPE.itemsize == 48 and LABEL_PIECE_DTYPE.itemsize == 16 and LABEL_INFO_DTYPE.itemsize == 32
+assert DISTANCE_INFO_DTYPE.itemsize == 16
 
 COUNTER_FIELDS = ["rays", "iterations", "pushes", "leaf_tests", "leaf_tests_trilinear", "boundaries", "csvo_header_bytes", "csvo_pointer_bytes",
                   "pixels", "lit_pixels", "shadow_rays", "wave_steps", "services", "refills", "tail_wave_steps", "tail_iterations"]
@@ -142,6 +148,11 @@ class LabelShape(C.Structure):
                 ("flags", C.c_uint32)]
 
 
+class DistanceShape(C.Structure):
+    """vx_distance_shape"""
+    _fields_ = [("size", C.c_uint32 * 3), ("pass_value", C.c_uint32), ("match_value", C.c_uint32), ("flags", C.c_uint32), ("_pad", C.c_uint32 * 2)]
+
+
 class Result(C.Structure):
     _fields_ = [("t", C.c_float), ("value", C.c_uint32), ("face_id", C.c_int32), ("pos", C.c_float * 3), ("uv", C.c_float * 2),
                 ("color", C.c_float * 4), ("lod", C.c_float), ("inside_voxel", C.c_int32)]
@@ -188,6 +199,7 @@ SYMBOLS = {
     "vx_light_boxes": (_int, [_vp, _vp, _u32, _u32, C.POINTER(LightShape), _int, _vp, _u32, _vp]),
     "vx_walk_points": (_int, [_vp, _vp, _u32, _vp, _u32, _u32, C.POINTER(WalkShape), _int, _vp, _u32, _vp, _vp]),
     "vx_label_boxes": (_int, [_vp, _vp, _u32, _u32, C.POINTER(LabelShape), _int, _vp, _u32, _vp, _vp]),
+    "vx_distance_boxes": (_int, [_vp, _vp, _u32, _u32, C.POINTER(DistanceShape), _int, _vp, _u32, _vp]),
     "vx_physics_step": (_int, [_vp, _vp, _u32, _int, C.c_float, _u32, _vp]),
     "vx_debug_trace": (_int, [_vp, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.c_float, _int, C.POINTER(Result), _vp, _u32, C.POINTER(_u32)]),
     "vx_sync": (_int, [_vp]),
@@ -409,6 +421,22 @@ def label_shape(size, anchor_faces=VX_LABEL_ALL_FACES, max_pieces=VX_LABEL_MAX_P
     return LabelShape((C.c_uint32 * 3)(*size), int(anchor_faces), int(max_pieces), int(max_steps), int(pass_value), int(flags))
 
 
+def distance_infos_to_numpy(infos):
+    """A device record tensor of Svo.distance_boxes as DISTANCE_INFO_DTYPE records (copies to the host: synchronise first)."""
+    return _to_numpy(infos, DISTANCE_INFO_DTYPE)
+
+
+def distance_fields_to_numpy(fields):
+    """A device field tensor of Svo.distance_boxes (int16 [N, field_stride / 2]) as a uint16 array of its shape, in which VX_DISTANCE_NONE reads as
+    itself and not as -1 (copies to the host: synchronise first)."""
+    return fields.cpu().numpy().view(np.uint16)
+
+
+def distance_shape(size, pass_value=0, match_value=0, flags=0):
+    """A vx_distance_shape."""
+    return DistanceShape((C.c_uint32 * 3)(*(int(v) for v in size)), int(pass_value), int(match_value), int(flags))
+
+
 def light_shape(size, props, flags=0):
     """(a vx_light_shape, the array its props pointer points into: keep it until the call has returned). props: uint8, at most 4,096 of them."""
     table = np.ascontiguousarray(np.asarray(props, dtype=np.uint8).reshape(-1))
@@ -455,7 +483,7 @@ def scan_hits_to_numpy(hits):
 
 
 # ---- what the batch and block methods of Svo share: every one of them is its docstring, these, one call of the library and a return ----------
-_U8, _U32 = np.dtype(np.uint8), np.dtype(np.uint32)
+_U8, _U16, _U32 = np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.uint32)
 _DTYPE_NAMES = {v: k for k, v in list(globals().items()) if isinstance(v, np.dtype) and k.endswith("_DTYPE")}
 
 
@@ -1050,6 +1078,31 @@ class Svo:
         info = _out("label_boxes: info", _asked(info, True), mem, count, LABEL_INFO_DTYPE, (count,), lo, "host")
         _check(lib().vx_label_boxes(self._h, ptr, stride, count, C.byref(shape), mem, _ptr(fields), int(field_stride), _ptr(pieces), _ptr(info)))
         return fields, pieces, info
+
+    # -- squared distances to the nearest block (a distance transform over get_block, gameplay.rs:161-201, for a batch of boxes) -------------------------
+    def distance_boxes(self, lo, size, pass_value=0, match_value=0, flags=0, fields=None, info=None, field_stride=0):
+        """vx_distance_boxes: for every cell of the boxes [lo_k, lo_k + size) (1..32 cells an axis) the squared distance, in cells, to the nearest
+        target cell of the box -- a solid cell (non-zero and not pass_value), or with match_value the cells of that id; under VX_DISTANCE_TO_AIR
+        the others. lo: as light_boxes takes it. Returns (fields, info), either None when not asked for: fields -- uint16 [N, field_stride / 2],
+        of which the first size.x * size.y * size.z entries of a row are the box's cells, x fastest, VX_DISTANCE_NONE everywhere when the box
+        holds no target; field_stride, in BYTES, 0: twice the voxel count rounded up to 16 -- and info -- DISTANCE_INFO_DTYPE records. fields and
+        info: None (or True) for fresh memory, False for none, or the memory to write to.
+        Host (a NumPy array): synchronous.
+        Device (a torch CUDA tensor): returns after enqueueing, without synchronising -- pair with sync(); fields is an int16 tensor, in which
+        VX_DISTANCE_NONE reads as -1 (distance_fields_to_numpy), and info an int32 tensor of shape (N, 4) on lo's device
+        (distance_infos_to_numpy)."""
+        mem, count, ptr, stride = _lo_rows("distance_boxes", lo)
+        shape = distance_shape(size, pass_value, match_value, flags)
+        entries = (int(field_stride) if field_stride else (2 * int(shape.size[0]) * int(shape.size[1]) * int(shape.size[2]) + 15) // 16 * 16) // 2
+        fields = _asked(fields, True)
+        if fields is True and mem == VX_MEM_DEVICE:
+            import torch
+
+            fields = torch.empty((count, entries), dtype=torch.int16, device=lo.device)
+        fields = _out("distance_boxes: fields", fields, mem, count * entries, _U16, (count, entries), lo, False, "N x field_stride / 2", "entries")
+        info = _out("distance_boxes: info", _asked(info, True), mem, count, DISTANCE_INFO_DTYPE, (count,), lo, "host")
+        _check(lib().vx_distance_boxes(self._h, ptr, stride, count, C.byref(shape), mem, _ptr(fields), int(field_stride), _ptr(info)))
+        return fields, info
 
     # -- walking distances and paths (a search over get_block, gameplay.rs:161-201, on the walking graph, for a batch) --------------------------------
     def walk_points(self, positions, size, goals=None, seed_at=None, max_steps=VX_WALK_MAX_STEPS, pass_value=0, height=2, climb=1, drop=3, path_capacity=0, flags=0,

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels_blocks.h"
+#include "kernels_shared.hpp"
 #include "vx_device.hpp"
 #include "vx_ray_batch.hpp"
 #include "vx_world_bytes.hpp"
@@ -60,26 +61,14 @@ hipError_t launch_block_points(int svo, hipStream_t stream, const SceneArgs& sc,
     static_assert(sizeof(vx_block_cell) == 8, "one 8-byte store");
     const dim3 grid((count + 63u) / 64u), block(64);
     const uint8_t* p = static_cast<const uint8_t*>(pos);
-#define VX_LAUNCH_POINTS(S) hipLaunchKernelGGL((block_points_kernel<S>), grid, block, 0, stream, sc, p, pos_stride, count, out)
-    if (svo == VX_SVO_ESVO_BIG) VX_LAUNCH_POINTS(VX_SVO_ESVO_BIG);
-    else if (svo == VX_SVO_ESVO) VX_LAUNCH_POINTS(VX_SVO_ESVO);
-    else if (svo == VX_SVO_CSVO) VX_LAUNCH_POINTS(VX_SVO_CSVO);
-    else return hipErrorInvalidValue;
-#undef VX_LAUNCH_POINTS
-    return hipGetLastError();
+    return for_format(svo, [&](auto f) { hipLaunchKernelGGL((block_points_kernel<decltype(f)::value>), grid, block, 0, stream, sc, p, pos_stride, count, out); });
 }
 
 hipError_t launch_read_region(int svo, hipStream_t stream, const SceneArgs& sc, const vxb::Region& r, uint32_t* out) {
     const uint64_t bricks = vxb::region_bricks(r);
     if (bricks == 0 || bricks > 0x7fffffffull) return hipErrorInvalidValue;  // (a region of 2^24 voxels has fewer than 2^24 bricks)
     const dim3 grid(static_cast<uint32_t>(bricks), 1, 1), block(64);
-#define VX_LAUNCH_REGION(S) hipLaunchKernelGGL((read_region_kernel<S>), grid, block, 0, stream, sc, r, out)
-    if (svo == VX_SVO_ESVO_BIG) VX_LAUNCH_REGION(VX_SVO_ESVO_BIG);
-    else if (svo == VX_SVO_ESVO) VX_LAUNCH_REGION(VX_SVO_ESVO);
-    else if (svo == VX_SVO_CSVO) VX_LAUNCH_REGION(VX_SVO_CSVO);
-    else return hipErrorInvalidValue;
-#undef VX_LAUNCH_REGION
-    return hipGetLastError();
+    return for_format(svo, [&](auto f) { hipLaunchKernelGGL((read_region_kernel<decltype(f)::value>), grid, block, 0, stream, sc, r, out); });
 }
 
 }  // namespace vxk

@@ -16,24 +16,23 @@
 //   5  lane 0 writes the record as two 16-byte stores.
 // Registers (hipcc -Rpass-analysis=kernel-resource-usage, ESVO / CSVO / ESVO beyond 4 GiB): 76 / 87 / 74 VGPRs, 67 / 83 / 66 SGPRs.
 // No spill, no scratch, no LDS in any of the three.
+// The fold and the record's store below are deliberately the ones from before kernels_shared.hpp (uniform(), load3_at and the launcher come
+// from the header): on fold_wave and store_record one row of profiles/boxes_bench.py (ESVO, 256 boxes of 64^3) ran 1 % slower in two
+// visits (profiles/box_kernels/README.md), and the cause was not found in the generated code.
 #include <hip/hip_runtime.h>
 
 #include "kernels_blocks.h"
+#include "kernels_shared.hpp"
 #include "vx_device.hpp"
 #include "vx_world_bytes.hpp"
 
 using namespace vxd;
 using vxk::kFormat;
 using vxk::WorldBytes;
+using vxk::load3_at;
+using vxk::uniform;
 
 namespace {
-
-__device__ __forceinline__ uint32_t uniform(uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
-
-__device__ __forceinline__ void load3_at(const uint8_t* base, size_t at, float out[3]) {
-    const float* p = reinterpret_cast<const float*>(base + at);
-    out[0] = p[0]; out[1] = p[1]; out[2] = p[2];
-}
 
 __device__ __forceinline__ void store_record(vx_box_hit* out, const vx_box_hit& h) {
     uint4* const o = reinterpret_cast<uint4*>(out);
@@ -111,14 +110,10 @@ hipError_t launch_overlap_boxes(int svo, hipStream_t stream, const SceneArgs& sc
     const dim3 grid(count, 1, 1), block(64);  // (a grid's x may be as large as 2^31 - 1)
     const uint8_t *po = static_cast<const uint8_t*>(origin), *pf = static_cast<const uint8_t*>(offset), *pe = static_cast<const uint8_t*>(extents);
     const uint32_t has_offset = offset ? 1u : 0u;
-#define VX_LAUNCH_BOXES(S) \
-    hipLaunchKernelGGL((overlap_boxes_kernel<S>), grid, block, 0, stream, sc, po, pf, pe, origin_stride, offset_stride, extents_stride, has_offset, only_value, out)
-    if (svo == VX_SVO_ESVO_BIG) VX_LAUNCH_BOXES(VX_SVO_ESVO_BIG);
-    else if (svo == VX_SVO_ESVO) VX_LAUNCH_BOXES(VX_SVO_ESVO);
-    else if (svo == VX_SVO_CSVO) VX_LAUNCH_BOXES(VX_SVO_CSVO);
-    else return hipErrorInvalidValue;
-#undef VX_LAUNCH_BOXES
-    return hipGetLastError();
+    return for_format(svo, [&](auto f) {
+        hipLaunchKernelGGL((overlap_boxes_kernel<decltype(f)::value>), grid, block, 0, stream, sc, po, pf, pe, origin_stride, offset_stride, extents_stride, has_offset,
+                           only_value, out);
+    });
 }
 
 }  // namespace vxk

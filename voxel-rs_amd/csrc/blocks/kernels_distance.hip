@@ -9,16 +9,16 @@
 //   2  loading, as kernels_flood.hip loads: wave v takes the brick rows v, v + 4, ... of the cover, enters each brick once (enter_brick_at)
 //      and has lane l read the column along x at (y, z) = (l & 7, l >> 3) (vxb::flood_brick_lane; with a match_value a second time under
 //      that value, see vx_distance.hpp); after the last brick along x the lane stores its row's target word (vxb::distance_row) into LDS:
-//      one lane holds a row, a plain store.
+//      one lane holds a row, a plain store. (Why each box kernel writes this loop out: kernels_shared.hpp.)
 //   3  pass y: thread t owns the columns (x, z) = (t & 31, (t >> 5) + 8 k), k = 0..3, along y. It reads the row words of its z -- the threads
 //      of one z read the same words --, takes its x's distance from each (vxb::distance_row_x), keeps the line of 32 in registers, runs the
 //      pass entry by entry (vxb::distance_pass_at) and writes 16-bit values into the LDS array, which is laid out as the field is: entry
 //      (z * size.y + y) * size.x + x.
 //   4  pass z: thread t owns the columns (x, y) = (t & 31, (t >> 5) + 8 k) along z: its entries into registers, the pass, the final values
 //      back in place -- the column is its own --, and the record's fold (vxb::distance_fold_cell) from the values in registers; then
-//      xor-shuffles within a wave and three LDS words a wave across the four.
-//   5  the field leaves LDS as 16-byte stores, the entries behind the last cell written VX_DISTANCE_NONE in LDS before; thread 0 stores the
-//      16-byte record in one store.
+//      across the workgroup (fold_put, fold_take with vxb::distance_fold: three LDS words a wave).
+//   5  the field leaves LDS as 16-byte stores (store_field), the entries behind the last cell written VX_DISTANCE_NONE in LDS before;
+//      thread 0 stores the 16-byte record in one store (store_record).
 // One build a format: records need `farthest`, so a records-only call runs both passes and needs the same 64 KiB between them; only the
 // stores of step 5 are left out (fields == NULL is a kernel argument).
 // Registers (hipcc -Rpass-analysis=kernel-resource-usage, ESVO / CSVO / ESVO beyond 4 GiB): 245 / 245 / 245 VGPRs, 91 / 106 / 95 SGPRs. No
@@ -27,16 +27,14 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels_blocks.h"
+#include "kernels_shared.hpp"
 #include "vx_device.hpp"
 #include "vx_world_bytes.hpp"
 
 using namespace vxd;
-using vxk::kFormat;
-using vxk::WorldBytes;
+using namespace vxk;
 
 namespace {
-
-__device__ __forceinline__ uint32_t uniform(uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
 
 // A uniform value the compiler may not carry across this point: the 32 comparisons of a line's length with a constant are made where a
 // trip of the loop over the owned columns needs them, not ahead of the loop, where they would fill the scalar registers.
@@ -140,29 +138,12 @@ __global__ __launch_bounds__(256) void distance_boxes_kernel(SceneArgs sa, const
             }
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        vxb::DistanceAcc b;
-        b.targets = uint32_t(__shfl_xor(int(acc.targets), d, 64));
-        b.faces = uint32_t(__shfl_xor(int(acc.faces), d, 64));
-        b.key = uint32_t(__shfl_xor(int(acc.key), d, 64));
-        vxb::distance_fold(acc, b);
-    }
-    if (lane == 0) lds.fold[wave] = acc;
+    fold_put(lds.fold, wave, lane, acc, vxb::distance_fold);
     __syncthreads();
 
     // 5  the record, the field
-    if (info && t == 0) {  // (info: a kernel argument)
-        vxb::DistanceAcc all = lds.fold[0];
-        for (uint32_t v = 1; v < kWaves; ++v) vxb::distance_fold(all, lds.fold[v]);
-        const vx_distance_info r = vxb::distance_record(all, s);
-        *reinterpret_cast<uint4*>(info + n) = make_uint4(r.targets, r.farthest, r.where, r.faces);
-    }
-    if (fields) {
-        uint4* const to = reinterpret_cast<uint4*>(fields + size_t(n) * field_stride);
-        const uint4* const from = reinterpret_cast<const uint4*>(lds.dist);
-        for (uint32_t c = t; c < chunks; c += vxb::kFloodThreads) to[c] = from[c];
-    }
+    if (info && t == 0) store_record(info + n, vxb::distance_record(fold_take(lds.fold, vxb::distance_fold), s));  // (info: a kernel argument)
+    if (fields) store_field(fields + size_t(n) * field_stride, lds.dist, chunks, t, vxb::kFloodThreads);
 }
 
 }  // namespace
@@ -174,20 +155,15 @@ hipError_t launch_distance_boxes(int svo, hipStream_t stream, const SceneArgs& s
     static_assert(sizeof(vx_distance_info) == 16, "one 16-byte store");
     if (count == 0 || count > vxb::kDistanceMaxCount || (!fields && !info) || !lo) return hipErrorInvalidValue;
     // the kernel's own bounds, whatever the caller checked: rows and entries of LDS are indexed by these, and its loops end by them
-    for (int a = 0; a < 3; ++a)
-        if (shape.size[a] == 0 || shape.size[a] > vxb::kFloodSide) return hipErrorInvalidValue;
+    if (!sizes_within(shape.size, vxb::kFloodSide)) return hipErrorInvalidValue;
     if ((shape.flags & ~uint32_t(VX_DISTANCE_TO_AIR)) || (shape.match_value && shape.pass_value)) return hipErrorInvalidValue;
-    if (fields && (field_stride % 16u || field_stride < 2u * vxb::distance_voxels(shape))) return hipErrorInvalidValue;
+    if (!field_stride_ok(fields, field_stride, 2u * vxb::distance_voxels(shape))) return hipErrorInvalidValue;
     const dim3 grid(count, 1, 1), block(vxb::kFloodThreads);
     const uint8_t* p = static_cast<const uint8_t*>(lo);
     uint8_t* const f = reinterpret_cast<uint8_t*>(fields);
-#define VX_LAUNCH_DISTANCE(S) hipLaunchKernelGGL((distance_boxes_kernel<S>), grid, block, 0, stream, sc, p, lo_stride, shape, f, field_stride, info)
-    if (svo == VX_SVO_ESVO_BIG) VX_LAUNCH_DISTANCE(VX_SVO_ESVO_BIG);
-    else if (svo == VX_SVO_ESVO) VX_LAUNCH_DISTANCE(VX_SVO_ESVO);
-    else if (svo == VX_SVO_CSVO) VX_LAUNCH_DISTANCE(VX_SVO_CSVO);
-    else return hipErrorInvalidValue;
-#undef VX_LAUNCH_DISTANCE
-    return hipGetLastError();
+    return for_format(svo, [&](auto fmt) {
+        hipLaunchKernelGGL((distance_boxes_kernel<decltype(fmt)::value>), grid, block, 0, stream, sc, p, lo_stride, shape, f, field_stride, info);
+    });
 }
 
 }  // namespace vxk

@@ -19,19 +19,22 @@
 // Registers (hipcc -Rpass-analysis=kernel-resource-usage, ESVO / CSVO / ESVO beyond 4 GiB): with a field 66 / 87 / 68 VGPRs, 89 / 104 / 91
 // SGPRs; records only 59 / 87 / 68 and 82 / 97 / 84. No spill, no scratch in any of the six. LDS: 45,360 bytes with a field (three
 // workgroups a CU under the 160 KiB), 12,608 bytes for records only; both include what __syncthreads_or keeps for itself.
+// The device code below is deliberately the one from before kernels_shared.hpp (own folds, stores and loading loop; only uniform() and the
+// launcher come from the header): on the header's folds, rows_around and stores 2 of the 96 rows of profiles/flood_bench.py
+// ran 0.3 and 0.9 % slower (profiles/box_kernels/README.md), and the cause was not found in the generated code.
 #include <hip/hip_runtime.h>
 
 #include "kernels_blocks.h"
+#include "kernels_shared.hpp"
 #include "vx_device.hpp"
 #include "vx_world_bytes.hpp"
 
 using namespace vxd;
 using vxk::kFormat;
 using vxk::WorldBytes;
+using vxk::uniform;
 
 namespace {
-
-__device__ __forceinline__ uint32_t uniform(uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
 
 constexpr uint32_t kFieldBytes = vxb::kFloodRows * vxb::kFloodSide;  // 32 KiB: a multiple of 16, so the rounded voxel count fits
 
@@ -174,23 +177,17 @@ hipError_t launch_flood_points(int svo, hipStream_t stream, const SceneArgs& sc,
     static_assert(sizeof(vx_flood_info) == 16, "one 16-byte store");
     if (count == 0 || count > vxb::kMaxCount || (!fields && !info)) return hipErrorInvalidValue;
     // the kernel's own bounds, whatever the caller checked: rows and bytes of LDS are indexed by these
-    for (int a = 0; a < 3; ++a)
-        if (shape.size[a] == 0 || shape.size[a] > vxb::kFloodSide || shape.seed_at[a] >= shape.size[a]) return hipErrorInvalidValue;
+    if (!sizes_within(shape.size, vxb::kFloodSide)) return hipErrorInvalidValue;
+    if (shape.seed_at[0] >= shape.size[0] || shape.seed_at[1] >= shape.size[1] || shape.seed_at[2] >= shape.size[2]) return hipErrorInvalidValue;
     if (shape.max_steps > VX_FLOOD_MAX_STEPS) return hipErrorInvalidValue;
-    if (fields && (field_stride % 16u || field_stride < vxb::flood_voxels(shape))) return hipErrorInvalidValue;
+    if (!field_stride_ok(fields, field_stride, vxb::flood_voxels(shape))) return hipErrorInvalidValue;
     const dim3 grid(count, 1, 1), block(vxb::kFloodThreads);
     const uint8_t* p = static_cast<const uint8_t*>(pos);
-#define VX_LAUNCH_FLOOD(S)                                                                                                                     \
-    do {                                                                                                                                       \
-        if (fields) hipLaunchKernelGGL((flood_points_kernel<S, true>), grid, block, 0, stream, sc, p, pos_stride, shape, fields, field_stride, info); \
-        else hipLaunchKernelGGL((flood_points_kernel<S, false>), grid, block, 0, stream, sc, p, pos_stride, shape, fields, field_stride, info);      \
-    } while (0)
-    if (svo == VX_SVO_ESVO_BIG) VX_LAUNCH_FLOOD(VX_SVO_ESVO_BIG);
-    else if (svo == VX_SVO_ESVO) VX_LAUNCH_FLOOD(VX_SVO_ESVO);
-    else if (svo == VX_SVO_CSVO) VX_LAUNCH_FLOOD(VX_SVO_CSVO);
-    else return hipErrorInvalidValue;
-#undef VX_LAUNCH_FLOOD
-    return hipGetLastError();
+    return for_format(svo, [&](auto f) {
+        constexpr int S = decltype(f)::value;
+        if (fields) hipLaunchKernelGGL((flood_points_kernel<S, true>), grid, block, 0, stream, sc, p, pos_stride, shape, fields, field_stride, info);
+        else hipLaunchKernelGGL((flood_points_kernel<S, false>), grid, block, 0, stream, sc, p, pos_stride, shape, fields, field_stride, info);
+    });
 }
 
 }  // namespace vxk

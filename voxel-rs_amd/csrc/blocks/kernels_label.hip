@@ -27,19 +27,22 @@
 // SGPRs; records only 72 / 85 / 72 and 76 / 90 / 77. No spill, no scratch in any of the six. LDS: 41,392 bytes with a field (three
 // workgroups a CU under the 160 KiB, as kernels_flood.hip), 8,640 bytes for records only; both include what __syncthreads_or keeps for
 // itself.
+// The device code below is deliberately the one from before kernels_shared.hpp (own folds, stores and loading loop; only uniform() and the
+// launcher come from the header): on the header's folds, rows_around and stores 10 of the 36 rows of profiles/label_bench.py
+// ran 0.4 to 1.1 % slower (profiles/box_kernels/README.md), and the cause was not found in the generated code.
 #include <hip/hip_runtime.h>
 
 #include "kernels_blocks.h"
+#include "kernels_shared.hpp"
 #include "vx_device.hpp"
 #include "vx_world_bytes.hpp"
 
 using namespace vxd;
 using vxk::kFormat;
 using vxk::WorldBytes;
+using vxk::uniform;
 
 namespace {
-
-__device__ __forceinline__ uint32_t uniform(uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
 
 constexpr uint32_t kFieldBytes = vxb::kFloodRows * vxb::kFloodSide;  // 32 KiB: a multiple of 16, so the rounded voxel count fits
 constexpr uint32_t kWaves = vxb::kFloodThreads / 64u;
@@ -262,25 +265,18 @@ hipError_t launch_label_boxes(int svo, hipStream_t stream, const SceneArgs& sc, 
     static_assert(sizeof(vx_label_piece) == 16 && sizeof(vx_label_info) == 32, "16-byte stores");
     if (count == 0 || count > vxb::kLabelMaxCount || (!fields && !pieces && !info) || !lo) return hipErrorInvalidValue;
     // the kernel's own bounds, whatever the caller checked: rows and bytes of LDS are indexed by these, and its loops end by them
-    for (int a = 0; a < 3; ++a)
-        if (shape.size[a] == 0 || shape.size[a] > vxb::kFloodSide) return hipErrorInvalidValue;
+    if (!sizes_within(shape.size, vxb::kFloodSide)) return hipErrorInvalidValue;
     if (shape.max_steps > VX_LABEL_MAX_STEPS || shape.max_pieces > VX_LABEL_MAX_PIECES || (shape.anchor_faces & ~uint32_t(VX_LABEL_ALL_FACES)) || shape.flags)
         return hipErrorInvalidValue;
     if (pieces && shape.max_pieces == 0) return hipErrorInvalidValue;
-    if (fields && (field_stride % 16u || field_stride < vxb::label_voxels(shape))) return hipErrorInvalidValue;
+    if (!field_stride_ok(fields, field_stride, vxb::label_voxels(shape))) return hipErrorInvalidValue;
     const dim3 grid(count, 1, 1), block(vxb::kFloodThreads);
     const uint8_t* p = static_cast<const uint8_t*>(lo);
-#define VX_LAUNCH_LABEL(S)                                                                                                                            \
-    do {                                                                                                                                              \
-        if (fields) hipLaunchKernelGGL((label_boxes_kernel<S, true>), grid, block, 0, stream, sc, p, lo_stride, shape, fields, field_stride, pieces, info); \
-        else hipLaunchKernelGGL((label_boxes_kernel<S, false>), grid, block, 0, stream, sc, p, lo_stride, shape, fields, field_stride, pieces, info);      \
-    } while (0)
-    if (svo == VX_SVO_ESVO_BIG) VX_LAUNCH_LABEL(VX_SVO_ESVO_BIG);
-    else if (svo == VX_SVO_ESVO) VX_LAUNCH_LABEL(VX_SVO_ESVO);
-    else if (svo == VX_SVO_CSVO) VX_LAUNCH_LABEL(VX_SVO_CSVO);
-    else return hipErrorInvalidValue;
-#undef VX_LAUNCH_LABEL
-    return hipGetLastError();
+    return for_format(svo, [&](auto f) {
+        constexpr int S = decltype(f)::value;
+        if (fields) hipLaunchKernelGGL((label_boxes_kernel<S, true>), grid, block, 0, stream, sc, p, lo_stride, shape, fields, field_stride, pieces, info);
+        else hipLaunchKernelGGL((label_boxes_kernel<S, false>), grid, block, 0, stream, sc, p, lo_stride, shape, fields, field_stride, pieces, info);
+    });
 }
 
 }  // namespace vxk

@@ -7,7 +7,8 @@
 //      bricks through readfirstlane.
 //   2  loading, as kernels_flood.hip loads: wave v takes the brick rows v, v + 4, ... of the cover (at most 7 x 7), enters each brick along x
 //      once (enter_brick_at) and has lane l read the column along x at (y, z) = (l & 7, l >> 3) (vxb::light_brick_lane); after the last brick
-//      the lane stores its five rows -- passable, four emission planes -- into LDS: one lane holds a row, plain stores.
+//      the lane stores its five rows -- passable, four emission planes -- into LDS: one lane holds a row, plain stores. (Why each box
+//      kernel writes this loop out: kernels_shared.hpp.)
 //   3  exposure above the box (not under VX_LIGHT_NO_SKY): wave v takes z = v, v + 4, ...; lane x runs the column's chain of scan_line
 //      (vxb::column_open); the 64 answers are the word of that z by one ballot.
 //   4  thread t owns rows t + 256 k, k = 0..8: (y, z) = (r % 48, r / 48). It takes its passable row and its emission planes into REGISTERS;
@@ -20,8 +21,9 @@
 //      starting as the emission planes (sources_L: the planes say L); it ends when no frontier and no unreached source is left.
 //   7  the levels of both channels stay in registers as 2 x 4 bit planes a row (144 VGPRs): no read-modify-write of bytes in global memory,
 //      which byte stores from 64 different rows a wave would have made of it. At the end the owners expand their rows to bytes in LDS, in
-//      vx_read_region's layout, at most 92,160 bytes a pass (two passes from 45^3 on), and the workgroup stores them as 16-byte words.
-//   8  the record: folded by xor-shuffles in a wave, across the waves through 16 LDS words.
+//      vx_read_region's layout, at most 92,160 bytes a pass (two passes from 45^3 on), and the workgroup stores them as 16-byte words
+//      (store_field).
+//   8  the record: folded across the workgroup (fold_put, fold_take: 16 LDS words), one 16-byte store (store_record).
 //   FIELD == false (fields == NULL): step 7's expansion and stores are left out; the planes are still what the record is read from.
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage), the same with and without FIELD -- the planes and the loader set them, not the
 // expansion --, ESVO / CSVO / ESVO beyond 4 GiB: 256 VGPRs and 5 AGPRs in each of the six; 79 / 105 / 82 SGPRs; no VGPR spill, no SGPR spill,
@@ -32,17 +34,16 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels_blocks.h"
+#include "kernels_shared.hpp"
 #include "vx_device.hpp"
 #include "vx_world_bytes.hpp"
 
 using namespace vxd;
-using vxk::kFormat;
-using vxk::WorldBytes;
+using namespace vxk;
 
 namespace {
 
-__device__ __forceinline__ uint32_t uniform(uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
-
+constexpr uint32_t kWaves = vxb::kLightThreads / 64u;
 constexpr uint32_t kRowBytes = vxb::kLightRows * 8u;  // one 64-bit row each: 18,432
 constexpr uint32_t kArena = 5u * kRowBytes;           // the loaded rows (passable, four planes) | the two frontiers | the field's staging
 static_assert(kArena % 16u == 0, "a pass of the field ends on a 16-byte word");
@@ -50,9 +51,13 @@ static_assert(kArena % 16u == 0, "a pass of the field ends on a 16-byte word");
 struct LightLds {
     alignas(16) uint8_t arena[kArena];
     uint64_t open[vxb::kLightSide];
-    uint32_t fold[16];
+    vxb::LightAcc fold[kWaves];
     alignas(16) uint8_t props[VX_LIGHT_MAX_PROPS];
 };
+
+__device__ __forceinline__ void light_fold(vxb::LightAcc& a, const vxb::LightAcc& b) {
+    a.lit += b.lit, a.sources += b.sources, a.open_columns += b.open_columns, a.faces |= b.faces;
+}
 
 // One channel's steps (vx_light.hpp: the spread) on the thread's rows; frontier 0 holds the first frontier, `reached` its rows.
 template <bool SOURCES>
@@ -139,7 +144,7 @@ __global__ __launch_bounds__(256) void light_boxes_kernel(SceneArgs sa, const ui
     // 3  exposure above the box
     if (sky_wanted) {
 #pragma nounroll
-        for (uint32_t rz = wave; rz < sz; rz += vxb::kLightThreads / 64u) {  // (wave-uniform)
+        for (uint32_t rz = wave; rz < sz; rz += kWaves) {  // (wave-uniform)
             uint32_t trips = 0u;
             const bool open = lane < sx && vxb::column_open<kFormat<SVO>>(w, lds.props, VX_LIGHT_MAX_PROPS, box.lo[0] + lane, box.lo[2] + rz, box.top, trips);
             const uint64_t word = __ballot(open);
@@ -210,24 +215,15 @@ __global__ __launch_bounds__(256) void light_boxes_kernel(SceneArgs sa, const ui
             const uint32_t r = t + k * vxb::kLightThreads;
             vxb::light_fold_row(acc, size, r % vxb::kLightSide, r / vxb::kLightSide, sky[k], block[k]);
         }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            acc.lit += uint32_t(__shfl_xor(int(acc.lit), d, 64));
-            acc.sources += uint32_t(__shfl_xor(int(acc.sources), d, 64));
-            acc.open_columns += uint32_t(__shfl_xor(int(acc.open_columns), d, 64));
-            acc.faces |= uint32_t(__shfl_xor(int(acc.faces), d, 64));
-        }
-        if (lane == 0) lds.fold[wave] = acc.lit, lds.fold[4u + wave] = acc.sources, lds.fold[8u + wave] = acc.open_columns, lds.fold[12u + wave] = acc.faces;
+        fold_put(lds.fold, wave, lane, acc, light_fold);
     }
     __syncthreads();  // (the fold's words; the last step's reads of the frontiers)
-    if (info && t == 0)
-        *reinterpret_cast<uint4*>(info + n) = make_uint4(lds.fold[0] + lds.fold[1] + lds.fold[2] + lds.fold[3], lds.fold[4] + lds.fold[5] + lds.fold[6] + lds.fold[7],
-                                                         lds.fold[8] + lds.fold[9] + lds.fold[10] + lds.fold[11], lds.fold[12] | lds.fold[13] | lds.fold[14] | lds.fold[15]);
+    if (info && t == 0) store_record(info + n, vxb::light_record(fold_take(lds.fold, light_fold)));
 
     // 7  the field: the owners' rows as bytes into LDS, a pass of kArena bytes at a time, out as 16-byte words
     if (FIELD) {
         const uint32_t voxels = vxb::light_voxels(size), padded = vxb::light_round16(voxels);
-        uint4* const out = reinterpret_cast<uint4*>(fields + size_t(n) * field_stride);
+        uint8_t* const out = fields + size_t(n) * field_stride;
 #pragma nounroll
         for (uint32_t base = 0; base < padded; base += kArena) {  // (uniform)
 #pragma unroll
@@ -248,8 +244,7 @@ __global__ __launch_bounds__(256) void light_boxes_kernel(SceneArgs sa, const ui
             if (t < 16u && voxels + t < padded && voxels + t - base < kArena) lds.arena[voxels + t - base] = 0u;
             __syncthreads();
             const uint32_t chunks = ((padded - base < kArena ? padded - base : kArena)) / 16u;
-            const uint4* const from = reinterpret_cast<const uint4*>(lds.arena);
-            for (uint32_t c = t; c < chunks; c += vxb::kLightThreads) out[base / 16u + c] = from[c];
+            store_field(out + base, lds.arena, chunks, t, vxb::kLightThreads);
             __syncthreads();
         }
     }
@@ -264,27 +259,18 @@ hipError_t launch_light_boxes(int svo, hipStream_t stream, const SceneArgs& sc, 
     static_assert(sizeof(vx_light_info) == 16, "one 16-byte store");
     if (count == 0 || count > vxb::kMaxCount || (!fields && !info) || !lo || !props) return hipErrorInvalidValue;
     // the kernel's own bounds, whatever the caller checked: rows and bytes of LDS are indexed by these
-    for (int a = 0; a < 3; ++a)
-        if (size[a] == 0 || size[a] > vxb::kLightSide) return hipErrorInvalidValue;
+    if (!sizes_within(size, vxb::kLightSide)) return hipErrorInvalidValue;
     if ((flags & ~uint32_t(VX_LIGHT_NO_SKY | VX_LIGHT_NO_BLOCKS)) || flags == uint32_t(VX_LIGHT_NO_SKY | VX_LIGHT_NO_BLOCKS)) return hipErrorInvalidValue;
     if (lo_stride % 4u || lo_stride < 12u) return hipErrorInvalidValue;
-    if (fields && (field_stride % 16u || field_stride < vxb::light_voxels(size))) return hipErrorInvalidValue;
+    if (!field_stride_ok(fields, field_stride, vxb::light_voxels(size))) return hipErrorInvalidValue;
     const dim3 grid(count, 1, 1), block(vxb::kLightThreads);
     const uint8_t* p = static_cast<const uint8_t*>(lo);
     const uint32_t* table = static_cast<const uint32_t*>(props);
-#define VX_LAUNCH_LIGHT(S)                                                                                                                          \
-    do {                                                                                                                                            \
-        if (fields) hipLaunchKernelGGL((light_boxes_kernel<S, true>), grid, block, 0, stream, sc, p, lo_stride, size[0], size[1], size[2], flags, table, fields, \
-                                       field_stride, info);                                                                                         \
-        else hipLaunchKernelGGL((light_boxes_kernel<S, false>), grid, block, 0, stream, sc, p, lo_stride, size[0], size[1], size[2], flags, table, fields,      \
-                                field_stride, info);                                                                                                \
-    } while (0)
-    if (svo == VX_SVO_ESVO_BIG) VX_LAUNCH_LIGHT(VX_SVO_ESVO_BIG);
-    else if (svo == VX_SVO_ESVO) VX_LAUNCH_LIGHT(VX_SVO_ESVO);
-    else if (svo == VX_SVO_CSVO) VX_LAUNCH_LIGHT(VX_SVO_CSVO);
-    else return hipErrorInvalidValue;
-#undef VX_LAUNCH_LIGHT
-    return hipGetLastError();
+    return for_format(svo, [&](auto f) {
+        constexpr int S = decltype(f)::value;
+        if (fields) hipLaunchKernelGGL((light_boxes_kernel<S, true>), grid, block, 0, stream, sc, p, lo_stride, size[0], size[1], size[2], flags, table, fields, field_stride, info);
+        else hipLaunchKernelGGL((light_boxes_kernel<S, false>), grid, block, 0, stream, sc, p, lo_stride, size[0], size[1], size[2], flags, table, fields, field_stride, info);
+    });
 }
 
 }  // namespace vxk

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels_blocks.h"
+#include "kernels_shared.hpp"
 #include "vx_device.hpp"
 #include "vx_world_bytes.hpp"
 
@@ -148,23 +149,21 @@ static hipError_t list_grid(const vxb::Region& r, dim3& grid) {
     return hipSuccess;
 }
 
-#define VX_LAUNCH_LIST(S, WRITE)                                                                                                              \
-    do {                                                                                                                                      \
-        if (faces) hipLaunchKernelGGL((list_region_kernel<S, true, WRITE>), grid, dim3(64), 0, stream, sc, r, flags, counts, out, capacity);  \
-        else hipLaunchKernelGGL((list_region_kernel<S, false, WRITE>), grid, dim3(64), 0, stream, sc, r, flags, counts, out, capacity);       \
-    } while (0)
-
-hipError_t launch_list_count(int svo, hipStream_t stream, const SceneArgs& sc, const vxb::Region& r, uint32_t flags, uint32_t* counts) {
+// count (WRITE false: out null, capacity 0) and write share one launch
+template <bool WRITE>
+static hipError_t launch_list(int svo, hipStream_t stream, const SceneArgs& sc, const vxb::Region& r, uint32_t flags, uint32_t* counts, vx_block_at* out, uint32_t capacity) {
     dim3 grid;
     if (const hipError_t e = list_grid(r, grid); e != hipSuccess) return e;
     const bool faces = vxb::list_wants_faces(flags);
-    vx_block_at* const out = nullptr;
-    const uint32_t capacity = 0;
-    if (svo == VX_SVO_ESVO_BIG) VX_LAUNCH_LIST(VX_SVO_ESVO_BIG, false);
-    else if (svo == VX_SVO_ESVO) VX_LAUNCH_LIST(VX_SVO_ESVO, false);
-    else if (svo == VX_SVO_CSVO) VX_LAUNCH_LIST(VX_SVO_CSVO, false);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return for_format(svo, [&](auto f) {
+        constexpr int S = decltype(f)::value;
+        if (faces) hipLaunchKernelGGL((list_region_kernel<S, true, WRITE>), grid, dim3(64), 0, stream, sc, r, flags, counts, out, capacity);
+        else hipLaunchKernelGGL((list_region_kernel<S, false, WRITE>), grid, dim3(64), 0, stream, sc, r, flags, counts, out, capacity);
+    });
+}
+
+hipError_t launch_list_count(int svo, hipStream_t stream, const SceneArgs& sc, const vxb::Region& r, uint32_t flags, uint32_t* counts) {
+    return launch_list<false>(svo, stream, sc, r, flags, counts, nullptr, 0);
 }
 
 hipError_t launch_list_offsets(hipStream_t stream, uint32_t* counts, uint32_t bricks, uint32_t* total) {
@@ -175,15 +174,7 @@ hipError_t launch_list_offsets(hipStream_t stream, uint32_t* counts, uint32_t br
 hipError_t launch_list_write(int svo, hipStream_t stream, const SceneArgs& sc, const vxb::Region& r, uint32_t flags, uint32_t* counts, vx_block_at* out,
                              uint32_t capacity) {
     static_assert(sizeof(vx_block_at) == 8, "one 8-byte store");
-    dim3 grid;
-    if (const hipError_t e = list_grid(r, grid); e != hipSuccess) return e;
-    const bool faces = vxb::list_wants_faces(flags);
-    if (svo == VX_SVO_ESVO_BIG) VX_LAUNCH_LIST(VX_SVO_ESVO_BIG, true);
-    else if (svo == VX_SVO_ESVO) VX_LAUNCH_LIST(VX_SVO_ESVO, true);
-    else if (svo == VX_SVO_CSVO) VX_LAUNCH_LIST(VX_SVO_CSVO, true);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return launch_list<true>(svo, stream, sc, r, flags, counts, out, capacity);
 }
-#undef VX_LAUNCH_LIST
 
 }  // namespace vxk

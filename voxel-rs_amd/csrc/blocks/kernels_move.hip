@@ -12,26 +12,24 @@
 //   3  the slab's bricks, nearest brick layer first: a brick of air, or one leaf above the brick that only_value refuses, is skipped by a
 //      scalar branch; else lane l takes column (l & 7, l >> 3) with vxb::move_brick_lane (lanes outside the slab load nothing) and keeps
 //      one key with its value. After each brick layer a ballot ends the walk if any lane holds a key.
-//   4  one min-fold of (key, value) by 6 x 2 xor-shuffles a pass, which leaves the smallest in every lane, then the pass's float operations,
-//      the same in every lane. The file is built with -ffp-contract=off like every other: no multiply of the rule is fused into the add
-//      behind it.
-//   5  lane 0 writes the record as three 16-byte stores.
-// Registers (hipcc -Rpass-analysis=kernel-resource-usage, ESVO / CSVO / ESVO beyond 4 GiB): 109 / 120 / 106 VGPRs, 92 / 106 / 96 SGPRs. No
+//   4  one min-fold of (key, value) by 6 x 2 xor-shuffles a pass (fold_wave, kernels_shared.hpp), which leaves the smallest in every lane,
+//      then the pass's float operations, the same in every lane. The file is built with -ffp-contract=off like every other: no multiply of
+//      the rule is fused into the add behind it.
+//   5  lane 0 writes the record as three 16-byte stores (store_record).
+// Registers (hipcc -Rpass-analysis=kernel-resource-usage, ESVO / CSVO / ESVO beyond 4 GiB): 109 / 120 / 106 VGPRs, 90 / 104 / 94 SGPRs. No
 // spill, no scratch, no LDS in any of the three. (With the box's floats and the slab's brick range left to the compiler -- in scalar registers
 // -- the three builds spilled 12 to 27 SGPRs.)
 #include <hip/hip_runtime.h>
 
 #include "kernels_blocks.h"
+#include "kernels_shared.hpp"
 #include "vx_device.hpp"
 #include "vx_world_bytes.hpp"
 
 using namespace vxd;
-using vxk::kFormat;
-using vxk::WorldBytes;
+using namespace vxk;
 
 namespace {
-
-__device__ __forceinline__ uint32_t uniform(uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
 
 // The box's floats live in VGPRs, one copy a lane: loaded at a uniform address they would all be kept in scalar registers, with the
 // descent's cursor, the slab and the loop counters more than there are. (No instruction: the constraint alone places the value.)
@@ -40,16 +38,9 @@ __device__ __forceinline__ float in_vgpr(float v) {
     return v;
 }
 
-__device__ __forceinline__ void load3_at(const uint8_t* base, size_t at, float out[3]) {
-    const float* p = reinterpret_cast<const float*>(base + at);
-    out[0] = in_vgpr(p[0]); out[1] = in_vgpr(p[1]); out[2] = in_vgpr(p[2]);
-}
-
-__device__ __forceinline__ void store_record(vx_move_hit* out, const vx_move_hit& h) {
-    uint4* const o = reinterpret_cast<uint4*>(out);
-    o[0] = make_uint4(__float_as_uint(h.origin[0]), __float_as_uint(h.origin[1]), __float_as_uint(h.origin[2]), __float_as_uint(h.moved[0]));
-    o[1] = make_uint4(__float_as_uint(h.moved[1]), __float_as_uint(h.moved[2]), h.contacts, h.value[0]);
-    o[2] = make_uint4(h.value[1], h.value[2], 0u, 0u);
+__device__ __forceinline__ void load3_in_vgpr(const uint8_t* base, size_t at, float out[3]) {
+    load3_at(base, at, out);
+    out[0] = in_vgpr(out[0]), out[1] = in_vgpr(out[1]), out[2] = in_vgpr(out[2]);
 }
 
 // (each pointer a kernel argument of its own, as in kernels_boxes.hip: the loads address global memory; has_offset, the strides, the order
@@ -62,10 +53,10 @@ __global__ __launch_bounds__(64) void move_boxes_kernel(SceneArgs sa, const uint
     const WorldBytes<SVO> w = {make_scene(sa)};
     const uint32_t n = blockIdx.x, lane = threadIdx.x;
     float o[3], f[3] = {0.0f, 0.0f, 0.0f}, e[3], mot[3];
-    load3_at(origin, size_t(n) * origin_stride, o);
-    if (has_offset) load3_at(offset, size_t(n) * offset_stride, f);
-    load3_at(extents, size_t(n) * extents_stride, e);
-    load3_at(motion, size_t(n) * motion_stride, mot);
+    load3_in_vgpr(origin, size_t(n) * origin_stride, o);
+    if (has_offset) load3_in_vgpr(offset, size_t(n) * offset_stride, f);
+    load3_in_vgpr(extents, size_t(n) * extents_stride, e);
+    load3_in_vgpr(motion, size_t(n) * motion_stride, mot);
     const uint32_t depth = vxb::depth_of(w.head());
     // (the rule's floats stay in VGPRs with the box: what is scalar of a pass is its axis, its direction and its bricks)
     const float world = in_vgpr(float(1u << depth)), skin_v = in_vgpr(skin);
@@ -106,13 +97,7 @@ __global__ __launch_bounds__(64) void move_boxes_kernel(SceneArgs sa, const uint
                     }
                     if (__ballot(best.key != vxb::kBoxNoKey)) break;  // a nearer brick layer cannot be beaten by a farther one
                 }
-#pragma unroll
-                for (int x = 32; x >= 1; x >>= 1) {
-                    vxb::MoveKey other;
-                    other.key = uint32_t(__shfl_xor(int(best.key), x, 64));
-                    other.value = uint32_t(__shfl_xor(int(best.value), x, 64));
-                    vxb::move_fold(best, other);
-                }
+                fold_wave(best, vxb::move_fold);
             }
             st = vxb::move_step(sv, a, d, skin_v, vxb::pick3(m.mn, a), vxb::pick3(m.mx, a), best);  // (every lane the same)
         }
@@ -136,15 +121,10 @@ hipError_t launch_move_boxes(int svo, hipStream_t stream, const SceneArgs& sc, c
     const uint8_t *po = static_cast<const uint8_t*>(origin), *pf = static_cast<const uint8_t*>(offset), *pe = static_cast<const uint8_t*>(extents),
                   *pm = static_cast<const uint8_t*>(motion);
     const uint32_t has_offset = offset ? 1u : 0u;
-#define VX_LAUNCH_MOVE(S)                                                                                                                             \
-    hipLaunchKernelGGL((move_boxes_kernel<S>), grid, block, 0, stream, sc, po, pf, pe, pm, origin_stride, offset_stride, extents_stride, motion_stride, \
-                       has_offset, only_value, shape.scale, shape.skin, shape.order, out)
-    if (svo == VX_SVO_ESVO_BIG) VX_LAUNCH_MOVE(VX_SVO_ESVO_BIG);
-    else if (svo == VX_SVO_ESVO) VX_LAUNCH_MOVE(VX_SVO_ESVO);
-    else if (svo == VX_SVO_CSVO) VX_LAUNCH_MOVE(VX_SVO_CSVO);
-    else return hipErrorInvalidValue;
-#undef VX_LAUNCH_MOVE
-    return hipGetLastError();
+    return for_format(svo, [&](auto f) {
+        hipLaunchKernelGGL((move_boxes_kernel<decltype(f)::value>), grid, block, 0, stream, sc, po, pf, pe, pm, origin_stride, offset_stride, extents_stride, motion_stride,
+                           has_offset, only_value, shape.scale, shape.skin, shape.order, out);
+    });
 }
 
 }  // namespace vxk

@@ -15,19 +15,15 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels_blocks.h"
+#include "kernels_shared.hpp"
 #include "vx_device.hpp"
 #include "vx_ray_batch.hpp"
 #include "vx_world_bytes.hpp"
 
 using namespace vxd;
-using vxk::kFormat;
-using vxk::WorldBytes;
+using namespace vxk;
 
 namespace {
-
-__device__ __forceinline__ void store_hit(vx_scan_hit* out, const vx_scan_hit& h) {
-    *reinterpret_cast<uint4*>(out) = make_uint4(uint32_t(h.coord), h.value, h.cell_log2, 0u);
-}
 
 template <int SVO>
 __global__ __launch_bounds__(64) void scan_points_kernel(SceneArgs sa, const uint8_t* __restrict__ pos, uint32_t pos_stride, uint32_t n,
@@ -38,7 +34,7 @@ __global__ __launch_bounds__(64) void scan_points_kernel(SceneArgs sa, const uin
     float p[3];
     vxk::load3(pos, pos_stride, i, p);
     uint32_t trips = 0;  // (the harness's figure: dead here)
-    store_hit(out + i, vxb::scan_point<kFormat<SVO>>(w, p, direction, reach, trips));
+    store_record(out + i, vxb::scan_point<kFormat<SVO>>(w, p, direction, reach, trips));
 }
 
 template <int SVO>
@@ -60,7 +56,7 @@ __global__ __launch_bounds__(64) void scan_columns_kernel(SceneArgs sa, vxb::Col
         }
     }
     uint32_t index;
-    if (vxb::column_index(p, t, i, j, index)) store_hit(out + index, hit);
+    if (vxb::column_index(p, t, i, j, index)) store_record(out + index, hit);
 }
 
 }  // namespace
@@ -73,26 +69,14 @@ hipError_t launch_scan_points(int svo, hipStream_t stream, const SceneArgs& sc, 
     const dim3 grid((count + 63u) / 64u), block(64);
     const uint8_t* p = static_cast<const uint8_t*>(pos);
     const uint32_t dir = static_cast<uint32_t>(direction);
-#define VX_LAUNCH_SCAN_POINTS(S) hipLaunchKernelGGL((scan_points_kernel<S>), grid, block, 0, stream, sc, p, pos_stride, count, dir, reach, out)
-    if (svo == VX_SVO_ESVO_BIG) VX_LAUNCH_SCAN_POINTS(VX_SVO_ESVO_BIG);
-    else if (svo == VX_SVO_ESVO) VX_LAUNCH_SCAN_POINTS(VX_SVO_ESVO);
-    else if (svo == VX_SVO_CSVO) VX_LAUNCH_SCAN_POINTS(VX_SVO_CSVO);
-    else return hipErrorInvalidValue;
-#undef VX_LAUNCH_SCAN_POINTS
-    return hipGetLastError();
+    return for_format(svo, [&](auto f) { hipLaunchKernelGGL((scan_points_kernel<decltype(f)::value>), grid, block, 0, stream, sc, p, pos_stride, count, dir, reach, out); });
 }
 
 hipError_t launch_scan_columns(int svo, hipStream_t stream, const SceneArgs& sc, const vxb::Columns& p, vx_scan_hit* out) {
     const uint64_t tiles = vxb::column_tiles(p);
     if (tiles == 0 || tiles > 0x7fffffffull) return hipErrorInvalidValue;  // (a footprint of 2^24 columns has fewer than 2^23 tiles)
     const dim3 grid(static_cast<uint32_t>(tiles), 1, 1), block(64);
-#define VX_LAUNCH_SCAN_COLUMNS(S) hipLaunchKernelGGL((scan_columns_kernel<S>), grid, block, 0, stream, sc, p, out)
-    if (svo == VX_SVO_ESVO_BIG) VX_LAUNCH_SCAN_COLUMNS(VX_SVO_ESVO_BIG);
-    else if (svo == VX_SVO_ESVO) VX_LAUNCH_SCAN_COLUMNS(VX_SVO_ESVO);
-    else if (svo == VX_SVO_CSVO) VX_LAUNCH_SCAN_COLUMNS(VX_SVO_CSVO);
-    else return hipErrorInvalidValue;
-#undef VX_LAUNCH_SCAN_COLUMNS
-    return hipGetLastError();
+    return for_format(svo, [&](auto f) { hipLaunchKernelGGL((scan_columns_kernel<decltype(f)::value>), grid, block, 0, stream, sc, p, out); });
 }
 
 }  // namespace vxk

@@ -7,7 +7,7 @@
 //      workgroup alike -- the field goes out as VX_WALK_NO_POSITION, the path as VX_WALK_NONE, thread 0 writes the record.
 //   2  the box of the extended layers (vxb::walk_load_shape) and its bricks through readfirstlane.
 //   3  loading: kernels_flood.hip's, over size.y + height layers: wave v takes the brick rows v, v + 4, ... of the cover, lane l the column
-//      along x at (y, z) = (l & 7, l >> 3); one lane holds a row, a plain store.
+//      along x at (y, z) = (l & 7, l >> 3); one lane holds a row, a plain store. (Why each box kernel writes this loop out: kernels_shared.hpp.)
 //   4  settling: every thread reads the goal (and the position again) at the same addresses; thread 0 walks the seed's column down, thread
 //      64 the goal's (vxb::walk_settle: at most 36 LDS reads); two words of LDS.
 //   5  thread t owns rows t + 256 k, k = 0..3: (layer, z) = (t & 31, (t >> 5) + 8 k). Its rows' standable and reached bits, the up mask and
@@ -18,10 +18,11 @@
 //      other parity; newly reached bits get the step written into the byte field; the owner of the goal's row notes the step that finds it;
 //      one __syncthreads_or a step, which every thread reaches. Under VX_WALK_STOP_AT_GOAL all threads compare that word with the step just
 //      done (a thread already in the next step can only write a LARGER step into it: the comparison cannot tear the workgroup apart).
-//   7  the record: folded by xor-shuffles in a wave, across the waves through 8 LDS words; two 16-byte stores by thread 0.
+//   7  the record: folded across the workgroup (fold_put, fold_take: 8 LDS words); two 16-byte stores by thread 0 (store_record).
 //   8  the path: wave 0 walks back from the goal, lane c the candidate c of vxb::walk_candidate (at most 4 x (2 + drop) = 20 lanes), a ballot
 //      picks the first, a readlane hands it on; at most path_steps <= max_steps trips; entries into LDS, and after a barrier out as 16-byte
-//      stores. The field leaves as 16-byte stores.
+//      stores. The field leaves as 16-byte stores (store_field). The step's reads of the frontier stay vxb::walk_beside's (vx_walk.hpp, which
+//      the host harness shares): its rows beside a row are other layers of the column.
 //   FIELD == false (no fields and no path): the byte field is not declared.
 // Registers (hipcc -Rpass-analysis=kernel-resource-usage, ESVO / CSVO / ESVO beyond 4 GiB): with a field 66 / 88 / 68 VGPRs, 99 / 106 / 101
 // SGPRs; records only 67 / 88 / 70 and 91 / 106 / 93. No scratch in any of the six and no VGPR spill. The target of no spill at all is missed
@@ -32,26 +33,35 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels_blocks.h"
+#include "kernels_shared.hpp"
 #include "vx_device.hpp"
 #include "vx_world_bytes.hpp"
 
 using namespace vxd;
-using vxk::kFormat;
-using vxk::WorldBytes;
+using namespace vxk;
 
 namespace {
 
-__device__ __forceinline__ uint32_t uniform(uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
+constexpr uint32_t kWaves = vxb::kFloodThreads / 64u;
 
 template <bool FIELD>
 struct WalkLds {
     uint32_t passable[vxb::kFloodRows];
     uint32_t frontier[2][vxb::kFloodRows];
     uint32_t up[2][vxb::kFloodRows];
-    uint32_t fold[8];
+    vxb::FloodAcc fold[kWaves];
     uint32_t seed_value, start_e, goal_e, goal_step;
     alignas(16) uint32_t path[FIELD ? vxb::kWalkMaxPath : 4];
     alignas(16) uint8_t field[FIELD ? vxb::kWalkFieldBytes : 16];
+};
+
+__device__ __forceinline__ void walk_fold(vxb::FloodAcc& a, const vxb::FloodAcc& b) { a.reached += b.reached, a.faces |= b.faces; }
+
+// where a query's outputs go
+struct WalkOutputs {
+    uint32_t voxels, chunks, path_chunks;
+    uint8_t* out;
+    uint4* path_out;
 };
 
 template <int SVO, bool FIELD>
@@ -62,27 +72,21 @@ __global__ __launch_bounds__(256) void walk_points_kernel(SceneArgs sa, const ui
     const WorldBytes<SVO> w = {make_scene(sa)};
     const uint32_t n = blockIdx.x, t = threadIdx.x, lane = t & 63u, wave = uniform(t >> 6);
     float p[3];
-    {
-        const float* q = reinterpret_cast<const float*>(pos + size_t(n) * pos_stride);
-        p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
-    }
+    load3_at(pos, size_t(n) * pos_stride, p);
     // (where the outputs go is worked out where they are written, here and at the end: nothing of it is kept across the loading)
-#define VX_WALK_OUTPUTS                                                                                                                    \
-    const uint32_t voxels = vxb::walk_voxels(s), chunks = vxb::flood_round16(voxels) / 16u, path_chunks = s.path_capacity / 4u;            \
-    uint4* const out = FIELD && fields ? reinterpret_cast<uint4*>(fields + size_t(n) * field_stride) : nullptr;                            \
-    uint4* const path_out = FIELD && paths ? reinterpret_cast<uint4*>(paths + size_t(n) * s.path_capacity) : nullptr
+    const auto outputs = [&] {
+        const uint32_t voxels = vxb::walk_voxels(s);
+        return WalkOutputs{voxels, vxb::flood_round16(voxels) / 16u, s.path_capacity / 4u, FIELD && fields ? fields + size_t(n) * field_stride : nullptr,
+                           FIELD && paths ? reinterpret_cast<uint4*>(paths + size_t(n) * s.path_capacity) : nullptr};
+    };
     if (!vxb::flood_has_position(p)) {  // (the same for every thread of the workgroup; no barrier has been met)
-        VX_WALK_OUTPUTS;
-        if (out)
-            for (uint32_t c = t; c < chunks; c += vxb::kFloodThreads)
-                out[c] = make_uint4(vxb::flood_no_position_word(4u * c, voxels), vxb::flood_no_position_word(4u * c + 1u, voxels),
-                                    vxb::flood_no_position_word(4u * c + 2u, voxels), vxb::flood_no_position_word(4u * c + 3u, voxels));
-        if (path_out && t < path_chunks) path_out[t] = make_uint4(VX_WALK_NONE, VX_WALK_NONE, VX_WALK_NONE, VX_WALK_NONE);
-        if (info && t == 0) {
-            uint4* const r = reinterpret_cast<uint4*>(info + n);
-            r[0] = make_uint4(VX_FLOOD_INVALID, 0u, 0u, 0u);
-            r[1] = make_uint4(VX_WALK_NONE, VX_WALK_NONE, VX_WALK_NONE, 0u);
-        }
+        const WalkOutputs o = outputs();
+        if (o.out)
+            for (uint32_t c = t; c < o.chunks; c += vxb::kFloodThreads)
+                reinterpret_cast<uint4*>(o.out)[c] = make_uint4(vxb::flood_no_position_word(4u * c, o.voxels), vxb::flood_no_position_word(4u * c + 1u, o.voxels),
+                                                                vxb::flood_no_position_word(4u * c + 2u, o.voxels), vxb::flood_no_position_word(4u * c + 3u, o.voxels));
+        if (o.path_out && t < o.path_chunks) o.path_out[t] = make_uint4(VX_WALK_NONE, VX_WALK_NONE, VX_WALK_NONE, VX_WALK_NONE);
+        if (info && t == 0) store_record(info + n, vxb::walk_no_position());
         return;
     }
     const vx_flood_shape ls = vxb::walk_load_shape(s);
@@ -105,7 +109,7 @@ __global__ __launch_bounds__(256) void walk_points_kernel(SceneArgs sa, const ui
     __syncthreads();
     const uint32_t i = lane & 7u, j = lane >> 3, brick_rows = box.count[1] * box.count[2];
 #pragma nounroll
-    for (uint32_t m = wave; m < brick_rows; m += vxb::kFloodThreads / 64u) {  // (wave-uniform)
+    for (uint32_t m = wave; m < brick_rows; m += kWaves) {  // (wave-uniform)
         const uint32_t cy = box.first[1] + (m % box.count[1]) * vxb::kBrick, cz = box.first[2] + (m / box.count[1]) * vxb::kBrick;
         uint32_t row = 0u, seed_value = 0u;
 #pragma nounroll
@@ -124,8 +128,9 @@ __global__ __launch_bounds__(256) void walk_points_kernel(SceneArgs sa, const ui
     // 4  settling (the goal is read here, and the position again: nothing of them is kept across the loading)
     vxb::WalkCell goal = {0u, 0u, 0u, false};
     if (goals) {  // (a kernel argument: uniform)
-        const float *q = reinterpret_cast<const float*>(pos + size_t(n) * pos_stride), *gq = reinterpret_cast<const float*>(goals + size_t(n) * goal_stride);
-        const float at[3] = {q[0], q[1], q[2]}, g[3] = {gq[0], gq[1], gq[2]};
+        float at[3], g[3];
+        load3_at(pos, size_t(n) * pos_stride, at);
+        load3_at(goals, size_t(n) * goal_stride, g);
         if (vxb::flood_has_position(g)) goal = vxb::walk_goal_cell(at, g, s);
     }
     goal.rx = uniform(goal.rx), goal.ry = uniform(goal.ry), goal.rz = uniform(goal.rz);
@@ -198,27 +203,15 @@ __global__ __launch_bounds__(256) void walk_points_kernel(SceneArgs sa, const ui
         vxb::FloodAcc acc = {0u, 0u};
 #pragma unroll
         for (uint32_t k = 0; k < vxb::kFloodOwned; ++k) vxb::walk_fold_row(acc, s, e, rz0 + 8u * k, reached[k]);
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            acc.reached += uint32_t(__shfl_xor(int(acc.reached), d, 64));
-            acc.faces |= uint32_t(__shfl_xor(int(acc.faces), d, 64));
-        }
-        if (lane == 0) lds.fold[wave] = acc.reached, lds.fold[4u + wave] = acc.faces;
+        fold_put(lds.fold, wave, lane, acc, walk_fold);
     }
     __syncthreads();  // (the fold's words; the last step's bytes of the field; the goal's step)
     const uint32_t path_steps = lds.goal_step;
-    if (info && t == 0) {
-        vxb::FloodAcc all = {lds.fold[0] + lds.fold[1] + lds.fold[2] + lds.fold[3], lds.fold[4] | lds.fold[5] | lds.fold[6] | lds.fold[7]};
-        const vx_walk_info r = vxb::walk_record(all, farthest, lds.seed_value, start_e, goal_e, path_steps);
-        uint4* const to = reinterpret_cast<uint4*>(info + n);
-        to[0] = make_uint4(r.reached, r.farthest, r.faces, r.seed_value);
-        to[1] = make_uint4(r.start_ry, r.goal_ry, r.path_steps, 0u);
-    }
+    if (info && t == 0) store_record(info + n, vxb::walk_record(fold_take(lds.fold, walk_fold), farthest, lds.seed_value, start_e, goal_e, path_steps));
     if (FIELD) {
-        VX_WALK_OUTPUTS;
-#undef VX_WALK_OUTPUTS
+        const WalkOutputs o = outputs();
         // 8  the path
-        if (path_out) {  // (a kernel argument: uniform)
+        if (o.path_out) {  // (a kernel argument: uniform)
             if (wave == 0 && path_steps != VX_WALK_NONE) {
                 uint32_t x = goal.rx, at_e = goal_e, z = goal.rz, k = path_steps;
 #pragma nounroll
@@ -232,12 +225,9 @@ __global__ __launch_bounds__(256) void walk_points_kernel(SceneArgs sa, const ui
                 }
             }
             __syncthreads();  // (reached by every thread: path_out is uniform)
-            if (t < path_chunks) path_out[t] = reinterpret_cast<const uint4*>(lds.path)[t];
+            if (t < o.path_chunks) o.path_out[t] = reinterpret_cast<const uint4*>(lds.path)[t];
         }
-        if (out) {
-            const uint4* const from = reinterpret_cast<const uint4*>(lds.field);
-            for (uint32_t c = t; c < chunks; c += vxb::kFloodThreads) out[c] = from[c];
-        }
+        if (o.out) store_field(o.out, lds.field, o.chunks, t, vxb::kFloodThreads);
     }
 }
 
@@ -251,27 +241,19 @@ hipError_t launch_walk_points(int svo, hipStream_t stream, const SceneArgs& sc, 
     if (!goal || shape.path_capacity == 0) paths = nullptr;  // no path is written
     if (count == 0 || count > vxb::kMaxCount || (!fields && !info && !paths)) return hipErrorInvalidValue;
     // the kernel's own bounds, whatever the caller checked: rows and bytes of LDS are indexed by these
-    for (int a = 0; a < 3; ++a)
-        if (shape.size[a] == 0 || shape.size[a] > vxb::kFloodSide || shape.seed_at[a] >= shape.size[a]) return hipErrorInvalidValue;
+    if (!sizes_within(shape.size, vxb::kFloodSide)) return hipErrorInvalidValue;
+    if (shape.seed_at[0] >= shape.size[0] || shape.seed_at[1] >= shape.size[1] || shape.seed_at[2] >= shape.size[2]) return hipErrorInvalidValue;
     if (shape.height == 0 || shape.height > vxb::kWalkMaxHeight || shape.size[1] + shape.height > vxb::kFloodSide) return hipErrorInvalidValue;
     if (shape.max_steps > VX_WALK_MAX_STEPS || shape.climb > 1u || shape.drop > vxb::kWalkMaxDrop) return hipErrorInvalidValue;
     if (shape.path_capacity > vxb::kWalkMaxPath || shape.path_capacity % 4u) return hipErrorInvalidValue;
-    if (fields && (field_stride % 16u || field_stride < vxb::walk_voxels(shape))) return hipErrorInvalidValue;
+    if (!field_stride_ok(fields, field_stride, vxb::walk_voxels(shape))) return hipErrorInvalidValue;
     const dim3 grid(count, 1, 1), block(vxb::kFloodThreads);
     const uint8_t *p = static_cast<const uint8_t*>(pos), *g = static_cast<const uint8_t*>(goal);
-#define VX_LAUNCH_WALK(S)                                                                                                                          \
-    do {                                                                                                                                           \
-        if (fields || paths)                                                                                                                       \
-            hipLaunchKernelGGL((walk_points_kernel<S, true>), grid, block, 0, stream, sc, p, pos_stride, g, goal_stride, shape, fields, field_stride, paths, info);  \
-        else                                                                                                                                       \
-            hipLaunchKernelGGL((walk_points_kernel<S, false>), grid, block, 0, stream, sc, p, pos_stride, g, goal_stride, shape, fields, field_stride, paths, info); \
-    } while (0)
-    if (svo == VX_SVO_ESVO_BIG) VX_LAUNCH_WALK(VX_SVO_ESVO_BIG);
-    else if (svo == VX_SVO_ESVO) VX_LAUNCH_WALK(VX_SVO_ESVO);
-    else if (svo == VX_SVO_CSVO) VX_LAUNCH_WALK(VX_SVO_CSVO);
-    else return hipErrorInvalidValue;
-#undef VX_LAUNCH_WALK
-    return hipGetLastError();
+    return for_format(svo, [&](auto f) {
+        constexpr int S = decltype(f)::value;
+        if (fields || paths) hipLaunchKernelGGL((walk_points_kernel<S, true>), grid, block, 0, stream, sc, p, pos_stride, g, goal_stride, shape, fields, field_stride, paths, info);
+        else hipLaunchKernelGGL((walk_points_kernel<S, false>), grid, block, 0, stream, sc, p, pos_stride, g, goal_stride, shape, fields, field_stride, paths, info);
+    });
 }
 
 }  // namespace vxk

@@ -3,14 +3,10 @@ worlds -- `glasshouse`, depth 6, one chunk; `far_chunks`, depth 14, 2 x 2 chunks
 for each, and the ground truth of both: info["blocks"] and info["detail"], the dense copy the worlds were built from, with the LOD chunk's
 voxels of 4 x 4 x 4 blocks worked out by the reference's pick_leaf_for_lod rule (internal.rs:461-485) restated here over the dense array.
 Nothing of the code under test is used. Also the runner of the host harness (tests/cpp/blocks_on_host.cpp), a stand-alone program."""
-import subprocess
-import tempfile
-from pathlib import Path
-
 import numpy as np
 
 from batch_cases import BUILDERS
-from helpers import ROOT
+from host_harness import HostRunner, build_harness
 from voxel_rs_amd import hip, host
 
 OUTSIDE = 0xFFFFFFFF
@@ -18,7 +14,6 @@ POINT_SEED = {"glasshouse": 41, "far_chunks": 42}
 LOD_ORDER = (2, 3, 6, 7, 0, 1, 4, 5)  # pick_leaf_for_lod's visiting order; a child's index is x | y << 1 | z << 2
 REGIONS = {"glasshouse": ((-3, -3, -3), (70, 70, 70)),  # the whole world and a margin of 3 on every side
            "far_chunks": ((12795, 93, 12825), (75, 37, 77))}  # all four chunks (12800..12864, 96..128, 12832..12896) from an odd corner
-BUILD = Path(ROOT) / "tests" / "_build"
 
 
 def pick_octants(a):
@@ -180,37 +175,23 @@ def check_cells(c, cells, pts=None, kinds=None):
 
 
 def harness():
-    """tests/_build/blocks_on_host, built when it is older than its sources."""
-    BUILD.mkdir(exist_ok=True)
-    exe = BUILD / "blocks_on_host"
-    deps = [Path(ROOT) / "tests" / "cpp" / "blocks_on_host.cpp", Path(ROOT) / "voxel-rs_amd" / "csrc" / "blocks" / "vx_blocks.hpp", Path(ROOT) / "include" / "voxel_hip.h"]
-    if not exe.exists() or exe.stat().st_mtime < max(p.stat().st_mtime for p in deps):
-        cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", f"-I{ROOT}/include", f"-I{ROOT}/voxel-rs_amd/csrc/blocks", str(deps[0]), "-o", str(exe)]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout
-    return exe
-
-
-def _run(exe, args):
-    r = subprocess.run([str(exe)] + [str(a) for a in args], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    return r.stdout
+    """tests/_build/blocks_on_host: host_harness.build_harness's."""
+    return build_harness("blocks_on_host")
 
 
 def host_points(exe, c, raw, stride, count):
     """`count` float[3] at `stride` bytes of `raw` (a uint8 array) through the harness: BLOCK_CELL_DTYPE records."""
-    with tempfile.TemporaryDirectory() as d:
-        d = Path(d)
-        c.frame.tofile(d / "world.bin")
-        np.asarray(raw).view(np.uint8).tofile(d / "points.bin")
-        _run(exe, [c.svo_type, d / "world.bin", "points", d / "points.bin", stride, count, d / "out.bin"])
-        return np.fromfile(d / "out.bin", dtype=hip.BLOCK_CELL_DTYPE)
+    h = HostRunner(exe, c)
+    h.run("points", h.put("points.bin", raw), stride, count, h.path("out.bin"))
+    out = h.get("out.bin", hip.BLOCK_CELL_DTYPE)
+    h.close()
+    return out
 
 
 def host_region(exe, c, lo, size):
     """The box through the harness's region routine: uint32 [z][y][x]."""
-    with tempfile.TemporaryDirectory() as d:
-        d = Path(d)
-        c.frame.tofile(d / "world.bin")
-        _run(exe, [c.svo_type, d / "world.bin", "region", *lo, *size, d / "out.bin"])
-        return np.fromfile(d / "out.bin", dtype=np.uint32).reshape(size[2], size[1], size[0])
+    h = HostRunner(exe, c)
+    h.run("region", *lo, *size, h.path("out.bin"))
+    out = h.get("out.bin", np.uint32, shape=(size[2], size[1], size[0]))
+    h.close()
+    return out

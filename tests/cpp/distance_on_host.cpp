@@ -12,54 +12,19 @@
 //                                  call leaves untouched 0x5a; info.bin: `count` vx_distance_info records; "-": that output is null
 //   distance_on_host rules         prints what check_distance refuses
 //   distance_on_host lines         the bit function and the min-plus pass against their definitions, on seeded words and lines
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
-
+#include "on_host.hpp"
 #include "vx_distance.hpp"
 
+using namespace on_host;
+const char* const on_host::program = "distance_on_host";
+
 namespace {
-
-// vx_blocks.hpp's reader over a byte vector: a dword or a byte that does not lie wholly inside it reads 0
-struct HostWorld {
-    const uint8_t* bytes;
-    uint64_t size;
-    uint32_t u32_at(uint64_t off) const {
-        uint32_t v = 0;
-        if (off + 4 <= size) std::memcpy(&v, bytes + off, 4);
-        return v;
-    }
-    uint32_t head() const { return u32_at(0); }
-    uint32_t root_ptr() const { return u32_at(4); }
-    uint32_t word(uint32_t i) const { return u32_at(4ull + 4ull * i); }
-    uint32_t c32(uint32_t p) const { return u32_at(8ull + p); }
-    uint32_t c8(uint32_t p) const { return 8ull + p < size ? bytes[8ull + p] : 0u; }
-};
-
-bool read_file(const char* path, std::vector<uint8_t>& out) {
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) return false;
-    const std::streamsize n = f.tellg();
-    f.seekg(0);
-    out.resize(size_t(n));  // (exactly the file's size: the sanitizer's red zone starts at its end)
-    return n == 0 || bool(f.read(reinterpret_cast<char*>(out.data()), n));
-}
-
-bool write_file(const char* path, const void* data, size_t bytes) {
-    std::ofstream f(path, std::ios::binary);
-    return f && (bytes == 0 || bool(f.write(static_cast<const char*>(data), std::streamsize(bytes))));
-}
 
 int usage() {
     std::fprintf(stderr, "usage: distance_on_host <svo_type> <world.bin> distance <lo.bin> <lo_stride> <count> <size x y z> <pass_value> <match_value> <flags> "
                          "<field_stride> <fields.bin | -> <info.bin | ->\n       distance_on_host rules\n       distance_on_host lines\n");
     return 2;
 }
-
-void say(const std::string& what, const char* refused) { std::printf("%s: %s\n", what.c_str(), refused ? refused : "ok"); }
 
 int rules() {
     alignas(16) static int32_t v[64];
@@ -183,44 +148,25 @@ int main(int argc, char** argv) {
     if (argc == 2 && !std::strcmp(argv[1], "rules")) return rules();
     if (argc == 2 && !std::strcmp(argv[1], "lines")) return lines();
     if (argc != 16 || std::strcmp(argv[3], "distance")) return usage();
-    const int svo_type = std::atoi(argv[1]);
-    if (svo_type != VX_SVO_ESVO && svo_type != VX_SVO_CSVO) return usage();
+    const int svo_type = svo_type_of(argv[1]);
+    if (svo_type < 0) return usage();
     std::vector<uint8_t> world, raw;
-    if (!read_file(argv[2], world)) { std::fprintf(stderr, "distance_on_host: cannot read %s\n", argv[2]); return 1; }
-    if (!read_file(argv[4], raw)) { std::fprintf(stderr, "distance_on_host: cannot read %s\n", argv[4]); return 1; }
+    if (!load(argv[2], world) || !load(argv[4], raw)) return 1;
     const HostWorld w = {world.data(), world.size()};
-    const auto u32 = [argv](int i) { return uint32_t(std::strtoul(argv[i], nullptr, 10)); };
+    const auto u32 = [argv](int i) { return u32_of(argv[i]); };
     const uint32_t lo_stride = u32(5), count = u32(6), field_stride = u32(13);
     const vx_distance_shape s = {{u32(7), u32(8), u32(9)}, u32(10), u32(11), u32(12), {0u, 0u}};
-    const bool want_fields = std::strcmp(argv[14], "-") != 0, want_info = std::strcmp(argv[15], "-") != 0;
     // (the shape's own rules first, on one box and a record that lies apart: the sizes below come from a shape that has passed them; the
     // whole call's rules again below, on the blocks it writes to)
     alignas(16) static uint8_t apart[16];
-    if (const char* refused = vxb::check_distance(raw.data(), 12, (count && raw.size() >= 12) ? 1u : 0u, &s, nullptr, 0, apart)) {
-        std::fprintf(stderr, "distance_on_host: %s\n", refused);
-        return 1;
-    }
-    if (count > vxb::kDistanceMaxCount) { std::fprintf(stderr, "distance_on_host: count exceeds 1048576 (2^20)\n"); return 1; }
-    if (field_stride % 16u) { std::fprintf(stderr, "distance_on_host: field_stride must be 0, or a multiple of 16\n"); return 1; }
-    const size_t packed = vxb::distance_field_bytes(s), stride = field_stride ? field_stride : packed;
-    // exactly up to the last byte the call may write: the last query's rounded field, not its whole stride
-    const size_t field_bytes = want_fields && count ? size_t(count - 1u) * stride + packed : 0u;
-    std::vector<uint8_t> fields(field_bytes, uint8_t(0x5a));
-    std::vector<vx_distance_info> info(want_info ? count : 0u);
-    if (!info.empty()) std::memset(info.data(), 0x5a, info.size() * sizeof(vx_distance_info));
-    if (count && raw.size() < size_t(count - 1u) * lo_stride + 12u) { std::fprintf(stderr, "distance_on_host: lo.bin is too short\n"); return 1; }
-    uint8_t* const f = want_fields ? fields.data() : nullptr;
-    vx_distance_info* const r = want_info ? info.data() : nullptr;
-    if (const char* refused = vxb::check_distance(raw.data(), lo_stride, count, &s, f, field_stride, r)) {
-        std::fprintf(stderr, "distance_on_host: %s\n", refused);
-        return 1;
-    }
-    if (svo_type == VX_SVO_CSVO) vxb::distance_boxes<vxb::kCsvo>(w, raw.data(), lo_stride, count, s, f, field_stride, r);
-    else vxb::distance_boxes<vxb::kEsvo>(w, raw.data(), lo_stride, count, s, f, field_stride, r);
-    if (want_fields) {  // (written out at the whole stride: the tail of the last query as the sentinel)
-        fields.resize(size_t(count) * stride, uint8_t(0x5a));
-        if (!write_file(argv[14], fields.data(), fields.size())) return 1;
-    }
-    if (want_info && !write_file(argv[15], info.data(), info.size() * sizeof(vx_distance_info))) return 1;
-    return 0;
+    if (const char* refused = vxb::check_distance(raw.data(), 12, (count && raw.size() >= 12) ? 1u : 0u, &s, nullptr, 0, apart)) return refuse(refused);
+    if (count > vxb::kDistanceMaxCount) return refuse("count exceeds 1048576 (2^20)");
+    if (field_stride % 16u) return refuse("field_stride must be 0, or a multiple of 16");
+    const size_t packed = vxb::distance_field_bytes(s);
+    Fields fields(given(argv[14]), count, field_stride ? field_stride : packed, packed);
+    Output<vx_distance_info> info(given(argv[15]), count);
+    if (too_short(raw, count, lo_stride, "lo.bin")) return 1;
+    if (const char* refused = vxb::check_distance(raw.data(), lo_stride, count, &s, fields.data(), field_stride, info.data())) return refuse(refused);
+    with_format(svo_type, [&](auto format) { vxb::distance_boxes<decltype(format)::value>(w, raw.data(), lo_stride, count, s, fields.data(), field_stride, info.data()); });
+    return fields.write(argv[14]) && info.write(argv[15]) ? 0 : 1;
 }

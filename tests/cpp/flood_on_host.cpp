@@ -11,54 +11,19 @@
 //                                  -> fields.bin: count * field_stride bytes (field_stride 0: the voxel count rounded up to 16), what the call
 //                                  leaves untouched 0x5a; info.bin: `count` vx_flood_info records; "-": that output is null
 //   flood_on_host rules            prints what check_flood refuses
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
-
+#include "on_host.hpp"
 #include "vx_flood.hpp"
 
+using namespace on_host;
+const char* const on_host::program = "flood_on_host";
+
 namespace {
-
-// vx_blocks.hpp's reader over a byte vector: a dword or a byte that does not lie wholly inside it reads 0
-struct HostWorld {
-    const uint8_t* bytes;
-    uint64_t size;
-    uint32_t u32_at(uint64_t off) const {
-        uint32_t v = 0;
-        if (off + 4 <= size) std::memcpy(&v, bytes + off, 4);
-        return v;
-    }
-    uint32_t head() const { return u32_at(0); }
-    uint32_t root_ptr() const { return u32_at(4); }
-    uint32_t word(uint32_t i) const { return u32_at(4ull + 4ull * i); }
-    uint32_t c32(uint32_t p) const { return u32_at(8ull + p); }
-    uint32_t c8(uint32_t p) const { return 8ull + p < size ? bytes[8ull + p] : 0u; }
-};
-
-bool read_file(const char* path, std::vector<uint8_t>& out) {
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) return false;
-    const std::streamsize n = f.tellg();
-    f.seekg(0);
-    out.resize(size_t(n));  // (exactly the file's size: the sanitizer's red zone starts at its end)
-    return n == 0 || bool(f.read(reinterpret_cast<char*>(out.data()), n));
-}
-
-bool write_file(const char* path, const void* data, size_t bytes) {
-    std::ofstream f(path, std::ios::binary);
-    return f && (bytes == 0 || bool(f.write(static_cast<const char*>(data), std::streamsize(bytes))));
-}
 
 int usage() {
     std::fprintf(stderr, "usage: flood_on_host <svo_type> <world.bin> flood <points.bin> <pos_stride> <count> <size x y z> <seed_at x y z> <max_steps> "
                          "<pass_value> <flags> <field_stride> <fields.bin | -> <info.bin | ->\n       flood_on_host rules\n");
     return 2;
 }
-
-void say(const std::string& what, const char* refused) { std::printf("%s: %s\n", what.c_str(), refused ? refused : "ok"); }
 
 int rules() {
     alignas(16) static float v[64];
@@ -113,37 +78,20 @@ int rules() {
 int main(int argc, char** argv) {
     if (argc == 2 && !std::strcmp(argv[1], "rules")) return rules();
     if (argc != 19 || std::strcmp(argv[3], "flood")) return usage();
-    const int svo_type = std::atoi(argv[1]);
-    if (svo_type != VX_SVO_ESVO && svo_type != VX_SVO_CSVO) return usage();
+    const int svo_type = svo_type_of(argv[1]);
+    if (svo_type < 0) return usage();
     std::vector<uint8_t> world, raw;
-    if (!read_file(argv[2], world)) { std::fprintf(stderr, "flood_on_host: cannot read %s\n", argv[2]); return 1; }
-    if (!read_file(argv[4], raw)) { std::fprintf(stderr, "flood_on_host: cannot read %s\n", argv[4]); return 1; }
+    if (!load(argv[2], world) || !load(argv[4], raw)) return 1;
     const HostWorld w = {world.data(), world.size()};
-    const auto u32 = [argv](int i) { return uint32_t(std::strtoul(argv[i], nullptr, 10)); };
+    const auto u32 = [argv](int i) { return u32_of(argv[i]); };
     const uint32_t pos_stride = u32(5), count = u32(6), field_stride = u32(16);
     const vx_flood_shape s = {{u32(7), u32(8), u32(9)}, {u32(10), u32(11), u32(12)}, u32(13), u32(14), u32(15)};
-    const bool want_fields = std::strcmp(argv[17], "-") != 0, want_info = std::strcmp(argv[18], "-") != 0;
-    std::vector<vx_flood_info> info(want_info ? count : 0u);
-    // (a one-byte block stands in for an output that has no byte to receive: never written, never null by accident)
-    uint8_t none = 0;
-    if (const char* refused = vxb::check_flood(raw.data(), pos_stride, count, &s, want_fields ? &none : nullptr, field_stride, want_info ? &none : nullptr)) {
-        std::fprintf(stderr, "flood_on_host: %s\n", refused);
-        return 1;
-    }
-    const size_t stride = field_stride ? field_stride : vxb::flood_round16(vxb::flood_voxels(s));
-    // exactly up to the last byte the call may write: the last query's rounded voxel count, not its whole stride
-    const size_t field_bytes = want_fields && count ? size_t(count - 1u) * stride + vxb::flood_round16(vxb::flood_voxels(s)) : 0u;
-    std::vector<uint8_t> fields(field_bytes, uint8_t(0x5a));
-    if (want_info && count) std::memset(info.data(), 0x5a, info.size() * sizeof(vx_flood_info));
-    if (count && raw.size() < size_t(count - 1u) * pos_stride + 12u) { std::fprintf(stderr, "flood_on_host: points.bin is too short\n"); return 1; }
-    uint8_t* const f = want_fields ? fields.data() : nullptr;
-    vx_flood_info* const r = want_info ? info.data() : nullptr;
-    if (svo_type == VX_SVO_CSVO) vxb::flood_points<vxb::kCsvo>(w, raw.data(), pos_stride, count, s, f, field_stride, r);
-    else vxb::flood_points<vxb::kEsvo>(w, raw.data(), pos_stride, count, s, f, field_stride, r);
-    if (want_fields) {  // (written out at the whole stride: the tail of the last query as the sentinel)
-        fields.resize(size_t(count) * stride, uint8_t(0x5a));
-        if (!write_file(argv[17], fields.data(), fields.size())) return 1;
-    }
-    if (want_info && !write_file(argv[18], info.data(), info.size() * sizeof(vx_flood_info))) return 1;
-    return 0;
+    const bool want_fields = given(argv[17]), want_info = given(argv[18]);
+    if (const char* refused = vxb::check_flood(raw.data(), pos_stride, count, &s, stand_in(want_fields), field_stride, stand_in(want_info))) return refuse(refused);
+    const size_t packed = vxb::flood_round16(vxb::flood_voxels(s));
+    Fields fields(want_fields, count, field_stride ? field_stride : packed, packed);
+    Output<vx_flood_info> info(want_info, count);
+    if (too_short(raw, count, pos_stride, "points.bin")) return 1;
+    with_format(svo_type, [&](auto format) { vxb::flood_points<decltype(format)::value>(w, raw.data(), pos_stride, count, s, fields.data(), field_stride, info.data()); });
+    return fields.write(argv[17]) && info.write(argv[18]) ? 0 : 1;
 }

@@ -13,42 +13,15 @@
 //                                  -> out.bin: `count` vx_move_hit records
 //   move_on_host rules             prints what check_move refuses
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
 #include <limits>
-#include <string>
-#include <vector>
 
+#include "on_host.hpp"
 #include "vx_move.hpp"
 
+using namespace on_host;
+const char* const on_host::program = "move_on_host";
+
 namespace {
-
-// vx_blocks.hpp's reader over a byte vector: a dword or a byte that does not lie wholly inside it reads 0
-struct HostWorld {
-    const uint8_t* bytes;
-    uint64_t size;
-    uint32_t u32_at(uint64_t off) const {
-        uint32_t v = 0;
-        if (off + 4 <= size) std::memcpy(&v, bytes + off, 4);
-        return v;
-    }
-    uint32_t head() const { return u32_at(0); }
-    uint32_t root_ptr() const { return u32_at(4); }
-    uint32_t word(uint32_t i) const { return u32_at(4ull + 4ull * i); }
-    uint32_t c32(uint32_t p) const { return u32_at(8ull + p); }
-    uint32_t c8(uint32_t p) const { return 8ull + p < size ? bytes[8ull + p] : 0u; }
-};
-
-bool read_file(const char* path, std::vector<uint8_t>& out) {
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) return false;
-    const std::streamsize n = f.tellg();
-    f.seekg(0);
-    out.resize(size_t(n));  // (exactly the file's size: the sanitizer's red zone starts at its end)
-    return n == 0 || bool(f.read(reinterpret_cast<char*>(out.data()), n));
-}
 
 float float_of_bits(const char* hex) {
     const uint32_t bits = uint32_t(std::strtoul(hex, nullptr, 16));
@@ -63,9 +36,6 @@ int usage() {
                          "       move_on_host rules\n");
     return 2;
 }
-
-void say(const char* what, const char* refused) { std::printf("%s: %s\n", what, refused ? refused : "ok"); }
-void say(const std::string& what, const char* refused) { say(what.c_str(), refused); }
 
 int rules() {
     alignas(16) static float v[64];
@@ -124,35 +94,20 @@ int rules() {
 int main(int argc, char** argv) {
     if (argc == 2 && !std::strcmp(argv[1], "rules")) return rules();
     if (argc != 19 || std::strcmp(argv[3], "move")) return usage();
-    const int svo_type = std::atoi(argv[1]);
-    if (svo_type != VX_SVO_ESVO && svo_type != VX_SVO_CSVO) return usage();
+    const int svo_type = svo_type_of(argv[1]);
+    if (svo_type < 0) return usage();
     std::vector<uint8_t> world, raw;
-    if (!read_file(argv[2], world)) { std::fprintf(stderr, "move_on_host: cannot read %s\n", argv[2]); return 1; }
-    if (!read_file(argv[4], raw)) { std::fprintf(stderr, "move_on_host: cannot read %s\n", argv[4]); return 1; }
+    if (!load(argv[2], world) || !load(argv[4], raw)) return 1;
     const HostWorld w = {world.data(), world.size()};
-    const uint32_t count = uint32_t(std::strtoul(argv[5], nullptr, 10));
-    const long long origin_at = std::atoll(argv[6]), offset_at = std::atoll(argv[8]), extents_at = std::atoll(argv[10]), motion_at = std::atoll(argv[12]);
-    vx_box_batch b = {};
-    b.origin = raw.data() + origin_at;
-    b.offset = offset_at < 0 ? nullptr : raw.data() + offset_at;
-    b.extents = raw.data() + extents_at;
-    b.origin_stride = uint32_t(std::strtoul(argv[7], nullptr, 10));
-    b.offset_stride = uint32_t(std::strtoul(argv[9], nullptr, 10));
-    b.extents_stride = uint32_t(std::strtoul(argv[11], nullptr, 10));
-    const void* motion = raw.data() + motion_at;
-    const uint32_t motion_stride = uint32_t(std::strtoul(argv[13], nullptr, 10));
-    b.only_value = uint32_t(std::strtoul(argv[14], nullptr, 10));
+    const uint32_t count = u32_of(argv[5]), motion_stride = u32_of(argv[13]);
+    const vx_box_batch b = box_batch_of(argv, raw, u32_of(argv[14]));
+    const void* motion = raw.data() + std::atoll(argv[12]);
     vx_move_shape shape = {};
     shape.scale = float_of_bits(argv[15]);
     shape.skin = float_of_bits(argv[16]);
-    shape.order = uint32_t(std::strtoul(argv[17], nullptr, 10));
-    std::vector<vx_move_hit> out(count);  // (exactly `count` records: a record written beyond them is a heap overflow)
-    if (const char* refused = vxb::check_move(&b, motion, motion_stride, count, &shape, out.data())) { std::fprintf(stderr, "move_on_host: %s\n", refused); return 1; }
-    if (count) std::memset(static_cast<void*>(out.data()), 0x5a, out.size() * sizeof(vx_move_hit));
-    if (svo_type == VX_SVO_CSVO) vxb::move_boxes<vxb::kCsvo>(w, b, motion, motion_stride, count, shape, out.data());
-    else vxb::move_boxes<vxb::kEsvo>(w, b, motion, motion_stride, count, shape, out.data());
-    std::ofstream f(argv[18], std::ios::binary);
-    if (!f) return 1;
-    if (count && !f.write(reinterpret_cast<const char*>(out.data()), std::streamsize(out.size() * sizeof(vx_move_hit)))) return 1;
-    return 0;
+    shape.order = u32_of(argv[17]);
+    Output<vx_move_hit> out(true, count);  // (exactly `count` records)
+    if (const char* refused = vxb::check_move(&b, motion, motion_stride, count, &shape, out.data())) return refuse(refused);
+    with_format(svo_type, [&](auto format) { vxb::move_boxes<decltype(format)::value>(w, b, motion, motion_stride, count, shape, out.data()); });
+    return out.write(argv[18]) ? 0 : 1;
 }

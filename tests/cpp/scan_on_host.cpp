@@ -9,46 +9,13 @@
 //   scan_on_host <svo_type> <world.bin> columns <lox> <loy> <loz> <sx> <sy> <sz> <direction> <out.bin> <trips.bin>
 //                                                  -> size[u] * size[v] vx_scan_hit records, u fastest; uint32 loop trips a tile
 //   scan_on_host rules                             prints what check_scan_points / check_scan_columns refuse
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
-
+#include "on_host.hpp"
 #include "vx_scan.hpp"
 
+using namespace on_host;
+const char* const on_host::program = "scan_on_host";
+
 namespace {
-
-// vx_blocks.hpp's reader over a byte vector: a dword or a byte that does not lie wholly inside it reads 0
-struct HostWorld {
-    const uint8_t* bytes;
-    uint64_t size;
-    uint32_t u32_at(uint64_t off) const {
-        uint32_t v = 0;
-        if (off + 4 <= size) std::memcpy(&v, bytes + off, 4);
-        return v;
-    }
-    uint32_t head() const { return u32_at(0); }
-    uint32_t root_ptr() const { return u32_at(4); }
-    uint32_t word(uint32_t i) const { return u32_at(4ull + 4ull * i); }
-    uint32_t c32(uint32_t p) const { return u32_at(8ull + p); }
-    uint32_t c8(uint32_t p) const { return 8ull + p < size ? bytes[8ull + p] : 0u; }
-};
-
-bool read_file(const char* path, std::vector<uint8_t>& out) {
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) return false;
-    const std::streamsize n = f.tellg();
-    f.seekg(0);
-    out.resize(size_t(n));  // (exactly the file's size: the sanitizer's red zone starts at its end)
-    return n == 0 || bool(f.read(reinterpret_cast<char*>(out.data()), n));
-}
-
-bool write_file(const char* path, const void* data, size_t bytes) {
-    std::ofstream f(path, std::ios::binary);
-    return f && (bytes == 0 || f.write(static_cast<const char*>(data), std::streamsize(bytes)));
-}
 
 int usage() {
     std::fprintf(stderr, "usage: scan_on_host <svo_type> <world.bin> points <points.bin> <stride> <count> <direction> <reach> <out.bin> <trips.bin>\n"
@@ -56,8 +23,6 @@ int usage() {
                          "       scan_on_host rules\n");
     return 2;
 }
-
-void say(const char* what, const char* refused) { std::printf("%s: %s\n", what, refused ? refused : "ok"); }
 
 int rules() {
     alignas(8) static float p[8];
@@ -95,44 +60,36 @@ int rules() {
 int main(int argc, char** argv) {
     if (argc == 2 && !std::strcmp(argv[1], "rules")) return rules();
     if (argc < 4) return usage();
-    const int svo_type = std::atoi(argv[1]);
-    if (svo_type != VX_SVO_ESVO && svo_type != VX_SVO_CSVO) return usage();
+    const int svo_type = svo_type_of(argv[1]);
+    if (svo_type < 0) return usage();
     std::vector<uint8_t> world;
-    if (!read_file(argv[2], world)) { std::fprintf(stderr, "scan_on_host: cannot read %s\n", argv[2]); return 1; }
+    if (!load(argv[2], world)) return 1;
     const HostWorld w = {world.data(), world.size()};
 
     if (!std::strcmp(argv[3], "points") && argc == 11) {
         std::vector<uint8_t> points;
-        if (!read_file(argv[4], points)) { std::fprintf(stderr, "scan_on_host: cannot read %s\n", argv[4]); return 1; }
-        const uint32_t stride = uint32_t(std::strtoul(argv[5], nullptr, 10)), count = uint32_t(std::strtoul(argv[6], nullptr, 10));
+        if (!load(argv[4], points)) return 1;
+        const uint32_t stride = u32_of(argv[5]), count = u32_of(argv[6]), reach = u32_of(argv[8]);
         const int direction = std::atoi(argv[7]);
-        const uint32_t reach = uint32_t(std::strtoul(argv[8], nullptr, 10));
-        std::vector<vx_scan_hit> out(count);
+        Output<vx_scan_hit> out(true, count);  // (every record has to be written, its padding too)
         std::vector<uint32_t> trips(count);
-        std::memset(out.data(), 0x5a, out.size() * sizeof(vx_scan_hit));  // (every record has to be written, its padding too)
-        if (const char* refused = vxb::check_scan_points(points.data(), stride, count, direction, reach, out.data())) { std::fprintf(stderr, "scan_on_host: %s\n", refused); return 1; }
-        if (count && points.size() < size_t(count - 1) * stride + 12) { std::fprintf(stderr, "scan_on_host: %s is too short\n", argv[4]); return 1; }
-        if (svo_type == VX_SVO_CSVO) vxb::scan_points<vxb::kCsvo>(w, points.data(), stride, count, direction, reach, out.data(), trips.data());
-        else vxb::scan_points<vxb::kEsvo>(w, points.data(), stride, count, direction, reach, out.data(), trips.data());
-        return write_file(argv[9], out.data(), out.size() * sizeof(vx_scan_hit)) && write_file(argv[10], trips.data(), trips.size() * 4) ? 0 : 1;
+        if (const char* refused = vxb::check_scan_points(points.data(), stride, count, direction, reach, out.data())) return refuse(refused);
+        if (too_short(points, count, stride, argv[4])) return 1;
+        with_format(svo_type, [&](auto format) { vxb::scan_points<decltype(format)::value>(w, points.data(), stride, count, direction, reach, out.data(), trips.data()); });
+        return out.write(argv[9]) && write_file(argv[10], trips.data(), trips.size() * 4) ? 0 : 1;
     }
     if (!std::strcmp(argv[3], "columns") && argc == 13) {
         int32_t lo[3];
         uint32_t size[3];
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = int32_t(std::strtol(argv[4 + a], nullptr, 10));
-            size[a] = uint32_t(std::strtoul(argv[7 + a], nullptr, 10));
-        }
+        for (int a = 0; a < 3; ++a) lo[a] = i32_of(argv[4 + a]), size[a] = u32_of(argv[7 + a]);
         const int direction = std::atoi(argv[10]);
-        if (const char* refused = vxb::check_scan_columns(lo, size, direction)) { std::fprintf(stderr, "scan_on_host: %s\n", refused); return 1; }
+        if (const char* refused = vxb::check_scan_columns(lo, size, direction)) return refuse(refused);
         const vxb::Columns p = vxb::plan_columns(lo, size, direction);
         const uint64_t tiles = vxb::column_tiles(p);
-        std::vector<vx_scan_hit> out(tiles ? size_t(p.size_u) * p.size_v : 0);
+        Output<vx_scan_hit> out(true, tiles ? size_t(p.size_u) * p.size_v : 0);  // (every column of the footprint has to be written)
         std::vector<uint32_t> trips(size_t(tiles), 0u);
-        std::memset(out.data(), 0x5a, out.size() * sizeof(vx_scan_hit));  // (every column of the footprint has to be written)
-        if (svo_type == VX_SVO_CSVO) vxb::scan_columns<vxb::kCsvo>(w, lo, size, direction, out.data(), trips.data());
-        else vxb::scan_columns<vxb::kEsvo>(w, lo, size, direction, out.data(), trips.data());
-        return write_file(argv[11], out.data(), out.size() * sizeof(vx_scan_hit)) && write_file(argv[12], trips.data(), trips.size() * 4) ? 0 : 1;
+        with_format(svo_type, [&](auto format) { vxb::scan_columns<decltype(format)::value>(w, lo, size, direction, out.data(), trips.data()); });
+        return out.write(argv[11]) && write_file(argv[12], trips.data(), trips.size() * 4) ? 0 : 1;
     }
     return usage();
 }

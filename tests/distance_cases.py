@@ -7,14 +7,9 @@ a broadcast minimum over the 32 x 32 matrix of (i - j)^2 (distance_truth), and f
 cells of the squared distance itself (brute_force). `where` and `farthest` come from argmax over the field in its own order. Nothing of the
 code under test is used.
 Also the runner of the host harness (tests/cpp/distance_on_host.cpp), a stand-alone program, plain and built with sanitizers."""
-import subprocess
-import tempfile
-from pathlib import Path
-
 import numpy as np
 
-from blocks_cases import BUILD
-from helpers import ROOT
+from host_harness import HostRunner, build_harness, outputs_differing
 from label_cases import LABEL_CASES, SEEDED, _faces_of, make_label_case, pass_id, regions_of
 from light_cases import in_form, torch_boxes  # noqa: F401  (the forms of lo are vx_light_boxes')
 from voxel_rs_amd import hip
@@ -193,43 +188,22 @@ def unpack(word):
 
 
 def harness(sanitize=False):
-    """tests/_build/distance_on_host (or distance_on_host_san: the same program under AddressSanitizer and UndefinedBehaviorSanitizer, every
-    finding fatal), built when it is older than its sources."""
-    BUILD.mkdir(exist_ok=True)
-    exe = BUILD / ("distance_on_host_san" if sanitize else "distance_on_host")
-    blocks = Path(ROOT) / "voxel-rs_amd" / "csrc" / "blocks"
-    deps = [Path(ROOT) / "tests" / "cpp" / "distance_on_host.cpp", blocks / "vx_distance.hpp", blocks / "vx_flood.hpp", blocks / "vx_scan.hpp", blocks / "vx_blocks.hpp",
-            Path(ROOT) / "include" / "voxel_hip.h"]
-    if not exe.exists() or exe.stat().st_mtime < max(p.stat().st_mtime for p in deps):
-        flags = ["-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else []
-        cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", *flags, f"-I{ROOT}/include", f"-I{ROOT}/tests/cpp/shims", f"-I{blocks}", str(deps[0]), "-o", str(exe)]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout
-    return exe
+    """tests/_build/distance_on_host, or distance_on_host_san: host_harness.build_harness's."""
+    return build_harness("distance_on_host", sanitize)
 
 
-class HostDistance:
+class HostDistance(HostRunner):
     """The harness on one world: the frame is written once, every call is a run of the program."""
-
-    def __init__(self, exe, c):
-        self.exe, self.c = exe, c
-        self.dir = tempfile.TemporaryDirectory()
-        self.world = Path(self.dir.name) / "world.bin"
-        c.frame.tofile(self.world)
 
     def distance(self, boxes, size, pass_value=0, match_value=0, flags=0, lo_stride=12, field_stride=0, fields=True, info=True):
         """(fields uint16 [count, (field_stride or a field's bytes) / 2] or None, DISTANCE_INFO_DTYPE records or None); what the call left
         untouched reads 0x5a5a."""
-        d = Path(self.dir.name)
         count = len(boxes)
         voxels = size[0] * size[1] * size[2]
-        in_form(np.asarray(boxes, dtype=np.int32).reshape(-1, 3), lo_stride)[0].tofile(d / "lo.bin")
-        args = [self.exe, self.c.svo_type, self.world, "distance", d / "lo.bin", lo_stride, count, *size, pass_value, match_value, flags, field_stride,
-                d / "fields.bin" if fields else "-", d / "info.bin" if info else "-"]
-        r = subprocess.run([str(a) for a in args], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout
-        f = np.fromfile(d / "fields.bin", dtype=np.uint16).reshape(count, (field_stride or (2 * voxels + 15) // 16 * 16) // 2) if fields else None
-        i = np.fromfile(d / "info.bin", dtype=hip.DISTANCE_INFO_DTYPE) if info else None
+        lo = self.put("lo.bin", in_form(np.asarray(boxes, dtype=np.int32).reshape(-1, 3), lo_stride)[0])
+        self.run("distance", lo, lo_stride, count, *size, pass_value, match_value, flags, field_stride, self.path("fields.bin", fields), self.path("info.bin", info))
+        f = self.get("fields.bin", np.uint16, fields, (count, (field_stride or (2 * voxels + 15) // 16 * 16) // 2))
+        i = self.get("info.bin", hip.DISTANCE_INFO_DTYPE, info)
         assert i is None or len(i) == count
         return f, i
 
@@ -241,22 +215,7 @@ class HostDistance:
         assert (f[:, shape.entries:] == 0x5A5A).all(), "entries beyond the field were written"
         return f[:, :shape.entries], i
 
-    def close(self):
-        self.dir.cleanup()
-
 
 def differing(got, expected):
     """A message naming the first box whose field or record differ between two (fields, info), or None."""
-    (gf, gi), (ef, ei) = got, expected
-    if gf.shape != ef.shape or gi.shape != ei.shape:
-        return f"shapes differ: {gf.shape}, {gi.shape} vs {ef.shape}, {ei.shape}"
-    n = len(gf)
-    if n == 0:
-        return None
-    bad = np.flatnonzero((gf != ef).any(axis=1) | (gi.view(np.uint32).reshape(n, -1) != ei.view(np.uint32).reshape(n, -1)).any(axis=1))
-    if not len(bad):
-        return None
-    i = int(bad[0])
-    at = np.flatnonzero(gf[i] != ef[i])
-    return (f"{len(bad)} boxes differ, first {i}: record {gi[i]} expected {ei[i]}; {len(at)} entries differ"
-            + (f", first at {int(at[0])}: {int(gf[i][at[0]])} expected {int(ef[i][at[0]])}" if len(at) else ""))
+    return outputs_differing(got, expected)

@@ -7,15 +7,13 @@ plain numpy over blocks_cases.dense_region of the query's box, a breadth-first f
 VX_FLOOD_MAX_STEPS; a smaller step limit's field is that field with the larger step counts turned into VX_FLOOD_UNREACHED -- what a
 breadth-first search cut short gives. Nothing of the code under test is used. Also the runner of the host harness
 (tests/cpp/flood_on_host.cpp), a stand-alone program, plain and built with sanitizers."""
-import subprocess
-import tempfile
-from pathlib import Path
 
 import numpy as np
 
 from batch_cases import _chunk_of
-from blocks_cases import BUILD, dense_region
-from helpers import ROOT, vra
+from blocks_cases import dense_region
+from host_harness import HostRunner, build_harness, outputs_differing
+from helpers import vra
 from scan_cases import SCAN_CASES, ScanCase, make_scan_case, start_of
 from voxel_rs_amd import hip, host
 
@@ -355,28 +353,12 @@ def pass_id(c):
 
 
 def harness(sanitize=False):
-    """tests/_build/flood_on_host (or flood_on_host_san: the same program under AddressSanitizer and UndefinedBehaviorSanitizer, every finding
-    fatal), built when it is older than its sources."""
-    BUILD.mkdir(exist_ok=True)
-    exe = BUILD / ("flood_on_host_san" if sanitize else "flood_on_host")
-    blocks = Path(ROOT) / "voxel-rs_amd" / "csrc" / "blocks"
-    deps = [Path(ROOT) / "tests" / "cpp" / "flood_on_host.cpp", blocks / "vx_flood.hpp", blocks / "vx_scan.hpp", blocks / "vx_blocks.hpp", Path(ROOT) / "include" / "voxel_hip.h"]
-    if not exe.exists() or exe.stat().st_mtime < max(p.stat().st_mtime for p in deps):
-        flags = ["-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else []
-        cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", *flags, f"-I{ROOT}/include", f"-I{ROOT}/tests/cpp/shims", f"-I{blocks}", str(deps[0]), "-o", str(exe)]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout
-    return exe
+    """tests/_build/flood_on_host, or flood_on_host_san: host_harness.build_harness's."""
+    return build_harness("flood_on_host", sanitize)
 
 
-class HostFlood:
+class HostFlood(HostRunner):
     """The harness on one world: the frame is written once, every call is a run of the program."""
-
-    def __init__(self, exe, c):
-        self.exe, self.c = exe, c
-        self.dir = tempfile.TemporaryDirectory()
-        self.world = Path(self.dir.name) / "world.bin"
-        c.frame.tofile(self.world)
 
     def flood(self, raw, stride, count, shape, max_steps, pass_value=0, flags=0, field_stride=0, fields=True, info=True):
         """(fields [count, field_stride or padded] or None, FLOOD_INFO_DTYPE records or None); more queries than one call may write fields
@@ -385,14 +367,10 @@ class HostFlood:
         if len(parts) > 1:
             got = [self.flood(raw[a * stride:], stride, b - a, shape, max_steps, pass_value, flags, field_stride, fields, info) for a, b in parts]
             return np.concatenate([f for f, _ in got]), (np.concatenate([i for _, i in got]) if info else None)
-        d = Path(self.dir.name)
-        np.asarray(raw).view(np.uint8).tofile(d / "points.bin")
-        args = [self.exe, self.c.svo_type, self.world, "flood", d / "points.bin", stride, count, *shape.size, *shape.seed_at, max_steps, pass_value, flags, field_stride,
-                d / "fields.bin" if fields else "-", d / "info.bin" if info else "-"]
-        r = subprocess.run([str(a) for a in args], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout
-        f = np.fromfile(d / "fields.bin", dtype=np.uint8).reshape(count, field_stride or shape.padded) if fields else None
-        i = np.fromfile(d / "info.bin", dtype=hip.FLOOD_INFO_DTYPE) if info else None
+        self.run("flood", self.put("points.bin", raw), stride, count, *shape.size, *shape.seed_at, max_steps, pass_value, flags, field_stride,
+                 self.path("fields.bin", fields), self.path("info.bin", info))
+        f = self.get("fields.bin", np.uint8, fields, (count, field_stride or shape.padded))
+        i = self.get("info.bin", hip.FLOOD_INFO_DTYPE, info)
         assert i is None or len(i) == count
         return f, i
 
@@ -404,18 +382,7 @@ class HostFlood:
         raw, stride, _ = in_form(pts, form)
         return self.flood(raw, stride, len(pts), shape, max_steps, pass_value, flags)
 
-    def close(self):
-        self.dir.cleanup()
-
 
 def differing(got_fields, got_info, exp_fields, exp_info):
     """A message naming the first query whose field or record differs, or None."""
-    if got_fields.shape != exp_fields.shape or got_info.shape != exp_info.shape:
-        return f"shapes differ: {got_fields.shape}, {got_info.shape} vs {exp_fields.shape}, {exp_info.shape}"
-    bad = np.flatnonzero((got_fields != exp_fields).any(axis=1) | (got_info.view(np.uint32).reshape(-1, 4) != exp_info.view(np.uint32).reshape(-1, 4)).any(axis=1))
-    if not len(bad):
-        return None
-    i = int(bad[0])
-    cells = np.flatnonzero(got_fields[i] != exp_fields[i])
-    return (f"{len(bad)} queries differ, first {i}: record {got_info[i]} expected {exp_info[i]}; {len(cells)} cells differ"
-            + (f", first at {int(cells[0])}: {int(got_fields[i][cells[0]])} expected {int(exp_fields[i][cells[0]])}" if len(cells) else ""))
+    return outputs_differing((got_fields, got_info), (exp_fields, exp_info))

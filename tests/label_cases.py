@@ -9,16 +9,14 @@ solid cell in the field's order, again and again until none is left --, recordin
 once per shape, anchor_faces and pass_value with no budget at all; the answer under max_pieces and max_steps is derived from the recorded
 depths by the rule of include/voxel_hip.h (a flood is complete when used + depth <= max_steps). Nothing of the code under test is used.
 Also the runner of the host harness (tests/cpp/label_on_host.cpp), a stand-alone program, plain and built with sanitizers."""
-import subprocess
-import tempfile
-from pathlib import Path
 
 import numpy as np
 
 from batch_cases import _chunk_of
-from blocks_cases import BUILD, dense_region
+from blocks_cases import dense_region
+from host_harness import HostRunner, build_harness, outputs_differing
 from flood_cases import FLOOD_CASES, make_flood_case
-from helpers import ROOT, vra
+from helpers import vra
 from light_cases import in_form, torch_boxes  # noqa: F401  (the forms of lo are vx_light_boxes')
 from scan_cases import ScanCase
 from voxel_rs_amd import hip, host
@@ -417,46 +415,26 @@ def cells(fields, shape):
 
 
 def harness(sanitize=False):
-    """tests/_build/label_on_host (or label_on_host_san: the same program under AddressSanitizer and UndefinedBehaviorSanitizer, every finding
-    fatal), built when it is older than its sources."""
-    BUILD.mkdir(exist_ok=True)
-    exe = BUILD / ("label_on_host_san" if sanitize else "label_on_host")
-    blocks = Path(ROOT) / "voxel-rs_amd" / "csrc" / "blocks"
-    deps = [Path(ROOT) / "tests" / "cpp" / "label_on_host.cpp", blocks / "vx_label.hpp", blocks / "vx_flood.hpp", blocks / "vx_scan.hpp", blocks / "vx_blocks.hpp",
-            Path(ROOT) / "include" / "voxel_hip.h"]
-    if not exe.exists() or exe.stat().st_mtime < max(p.stat().st_mtime for p in deps):
-        flags = ["-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else []
-        cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", *flags, f"-I{ROOT}/include", f"-I{ROOT}/tests/cpp/shims", f"-I{blocks}", str(deps[0]), "-o", str(exe)]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout
-    return exe
+    """tests/_build/label_on_host, or label_on_host_san: host_harness.build_harness's."""
+    return build_harness("label_on_host", sanitize)
 
 
-class HostLabel:
+class HostLabel(HostRunner):
     """The harness on one world: the frame is written once, every call is a run of the program."""
-
-    def __init__(self, exe, c):
-        self.exe, self.c = exe, c
-        self.dir = tempfile.TemporaryDirectory()
-        self.world = Path(self.dir.name) / "world.bin"
-        c.frame.tofile(self.world)
 
     def label(self, boxes, size, anchor_faces=ALL_FACES, max_pieces=MAX_PIECES, max_steps=MAX_STEPS, pass_value=0, lo_stride=12, field_stride=0, fields=True, pieces=None,
               info=True):
         """(fields [count, field_stride or padded] or None, LABEL_PIECE_DTYPE [count, max_pieces] or None, LABEL_INFO_DTYPE records or None);
         pieces None: asked for when max_pieces > 0."""
-        d = Path(self.dir.name)
         count = len(boxes)
         voxels = size[0] * size[1] * size[2]
         pieces = max_pieces > 0 if pieces is None else pieces
-        in_form(np.asarray(boxes, dtype=np.int32).reshape(-1, 3), lo_stride)[0].tofile(d / "lo.bin")
-        args = [self.exe, self.c.svo_type, self.world, "label", d / "lo.bin", lo_stride, count, *size, anchor_faces, max_pieces, max_steps, pass_value, field_stride,
-                d / "fields.bin" if fields else "-", d / "pieces.bin" if pieces else "-", d / "info.bin" if info else "-"]
-        r = subprocess.run([str(a) for a in args], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout
-        f = np.fromfile(d / "fields.bin", dtype=np.uint8).reshape(count, field_stride or (voxels + 15) // 16 * 16) if fields else None
-        p = np.fromfile(d / "pieces.bin", dtype=hip.LABEL_PIECE_DTYPE).reshape(count, max_pieces) if pieces else None
-        i = np.fromfile(d / "info.bin", dtype=hip.LABEL_INFO_DTYPE) if info else None
+        lo = self.put("lo.bin", in_form(np.asarray(boxes, dtype=np.int32).reshape(-1, 3), lo_stride)[0])
+        self.run("label", lo, lo_stride, count, *size, anchor_faces, max_pieces, max_steps, pass_value, field_stride, self.path("fields.bin", fields),
+                 self.path("pieces.bin", pieces), self.path("info.bin", info))
+        f = self.get("fields.bin", np.uint8, fields, (count, field_stride or (voxels + 15) // 16 * 16))
+        p = self.get("pieces.bin", hip.LABEL_PIECE_DTYPE, pieces, (count, max_pieces))
+        i = self.get("info.bin", hip.LABEL_INFO_DTYPE, info)
         assert i is None or len(i) == count
         return f, p, i
 
@@ -467,25 +445,7 @@ class HostLabel:
         f, p, i = self.label(boxes if pick is None else boxes[pick], shape.size, faces, most, steps, pass_value, stride)
         return f, (np.zeros((len(f), 0), dtype=hip.LABEL_PIECE_DTYPE) if p is None else p), i
 
-    def close(self):
-        self.dir.cleanup()
-
 
 def differing(got, expected):
     """A message naming the first box whose field, piece records or record differ between two (fields, pieces, info), or None."""
-    (gf, gp, gi), (ef, ep, ei) = got, expected
-    if gf.shape != ef.shape or gp.shape != ep.shape or gi.shape != ei.shape:
-        return f"shapes differ: {gf.shape}, {gp.shape}, {gi.shape} vs {ef.shape}, {ep.shape}, {ei.shape}"
-    n = len(gf)
-    if n == 0:
-        return None
-    bad = np.flatnonzero((gf != ef).any(axis=1) | (gp.view(np.uint32).reshape(n, -1) != ep.view(np.uint32).reshape(n, -1)).any(axis=1)
-                         | (gi.view(np.uint32).reshape(n, -1) != ei.view(np.uint32).reshape(n, -1)).any(axis=1))
-    if not len(bad):
-        return None
-    i = int(bad[0])
-    at = np.flatnonzero(gf[i] != ef[i])
-    wrong = np.flatnonzero(gp[i] != ep[i])
-    return (f"{len(bad)} boxes differ, first {i}: record {gi[i]} expected {ei[i]}; {len(at)} cells differ"
-            + (f", first at {int(at[0])}: {int(gf[i][at[0]]):#x} expected {int(ef[i][at[0]]):#x}" if len(at) else "")
-            + (f"; {len(wrong)} piece records differ, first {int(wrong[0])}: {gp[i][wrong[0]]} expected {ep[i][wrong[0]]}" if len(wrong) else ""))
+    return outputs_differing(got, expected)

@@ -15,16 +15,14 @@ lies in a corridor sealed in rock, so none of its seeded boxes has both channels
 the two other conditions on the seeded boxes: test_light_on_host.py prints the figures). `lantern` carries all of that: a walled hall under a roof with a one-cell hole and a
 patch of panes, lamps of 15, an ember of 4, lava (transparent, 12), a lamp sealed in rock and a wall between a lamp and the cells behind it.
 Also the runner of the host harness (tests/cpp/light_on_host.cpp), a stand-alone program, plain and built with sanitizers."""
-import subprocess
-import tempfile
-from pathlib import Path
 
 import numpy as np
 
 from batch_cases import _chunk_of
-from blocks_cases import BUILD, dense_region
+from blocks_cases import dense_region
+from host_harness import HostRunner, build_harness, outputs_differing
 from flood_cases import FLOOD_CASES, make_flood_case
-from helpers import ROOT, vra
+from helpers import vra
 from scan_cases import ScanCase
 from voxel_rs_amd import hip, host
 
@@ -322,42 +320,22 @@ def cells(fields, shape):
 
 
 def harness(sanitize=False):
-    """tests/_build/light_on_host (or light_on_host_san: the same program under AddressSanitizer and UndefinedBehaviorSanitizer, every finding
-    fatal), built when it is older than its sources."""
-    BUILD.mkdir(exist_ok=True)
-    exe = BUILD / ("light_on_host_san" if sanitize else "light_on_host")
-    blocks = Path(ROOT) / "voxel-rs_amd" / "csrc" / "blocks"
-    deps = [Path(ROOT) / "tests" / "cpp" / "light_on_host.cpp", blocks / "vx_light.hpp", blocks / "vx_scan.hpp", blocks / "vx_blocks.hpp", Path(ROOT) / "include" / "voxel_hip.h"]
-    if not exe.exists() or exe.stat().st_mtime < max(p.stat().st_mtime for p in deps):
-        flags = ["-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else []
-        cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", *flags, f"-I{ROOT}/include", f"-I{ROOT}/tests/cpp/shims", f"-I{blocks}", str(deps[0]), "-o", str(exe)]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout
-    return exe
+    """tests/_build/light_on_host, or light_on_host_san: host_harness.build_harness's."""
+    return build_harness("light_on_host", sanitize)
 
 
-class HostLight:
+class HostLight(HostRunner):
     """The harness on one world: the frame is written once, every call is a run of the program."""
-
-    def __init__(self, exe, c):
-        self.exe, self.c = exe, c
-        self.dir = tempfile.TemporaryDirectory()
-        self.world = Path(self.dir.name) / "world.bin"
-        c.frame.tofile(self.world)
 
     def light(self, boxes, size, props, flags=0, lo_stride=12, field_stride=0, fields=True, info=True):
         """(fields [count, field_stride or padded] or None, LIGHT_INFO_DTYPE records or None)."""
-        d = Path(self.dir.name)
         count = len(boxes)
         voxels = size[0] * size[1] * size[2]
-        in_form(np.asarray(boxes, dtype=np.int32).reshape(-1, 3), lo_stride)[0].tofile(d / "lo.bin")
-        np.asarray(props, dtype=np.uint8).tofile(d / "props.bin")
-        args = [self.exe, self.c.svo_type, self.world, "light", d / "lo.bin", lo_stride, count, *size, flags, d / "props.bin" if len(props) else "-", field_stride,
-                d / "fields.bin" if fields else "-", d / "info.bin" if info else "-"]
-        r = subprocess.run([str(a) for a in args], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout
-        f = np.fromfile(d / "fields.bin", dtype=np.uint8).reshape(count, field_stride or (voxels + 15) // 16 * 16) if fields else None
-        i = np.fromfile(d / "info.bin", dtype=hip.LIGHT_INFO_DTYPE) if info else None
+        lo = self.put("lo.bin", in_form(np.asarray(boxes, dtype=np.int32).reshape(-1, 3), lo_stride)[0])
+        self.put("props.bin", np.asarray(props, dtype=np.uint8))
+        self.run("light", lo, lo_stride, count, *size, flags, self.path("props.bin", len(props)), field_stride, self.path("fields.bin", fields), self.path("info.bin", info))
+        f = self.get("fields.bin", np.uint8, fields, (count, field_stride or (voxels + 15) // 16 * 16))
+        i = self.get("info.bin", hip.LIGHT_INFO_DTYPE, info)
         assert i is None or len(i) == count
         return f, i
 
@@ -367,18 +345,7 @@ class HostLight:
         boxes = boxes_for(c, shape)
         return self.light(boxes if pick is None else boxes[pick], shape.size, props, flags, stride)
 
-    def close(self):
-        self.dir.cleanup()
-
 
 def differing(got_fields, got_info, exp_fields, exp_info):
     """A message naming the first box whose field or record differs, or None."""
-    if got_fields.shape != exp_fields.shape or got_info.shape != exp_info.shape:
-        return f"shapes differ: {got_fields.shape}, {got_info.shape} vs {exp_fields.shape}, {exp_info.shape}"
-    bad = np.flatnonzero((got_fields != exp_fields).any(axis=1) | (got_info.view(np.uint32).reshape(-1, 4) != exp_info.view(np.uint32).reshape(-1, 4)).any(axis=1))
-    if not len(bad):
-        return None
-    i = int(bad[0])
-    at = np.flatnonzero(got_fields[i] != exp_fields[i])
-    return (f"{len(bad)} boxes differ, first {i}: record {got_info[i]} expected {exp_info[i]}; {len(at)} cells differ"
-            + (f", first at {int(at[0])}: {int(got_fields[i][at[0]]):#x} expected {int(exp_fields[i][at[0]]):#x}" if len(at) else ""))
+    return outputs_differing((got_fields, got_info), (exp_fields, exp_info))

@@ -2,14 +2,11 @@
 the boxes, and the expected list of each box -- plain numpy over the dense truth: blocks_cases.dense_region of the box padded by one voxel,
 the face bits from its six shifted views, the records sorted by (z >> 3, y >> 3, x >> 3, z, y, x). Nothing of the code under test is used.
 Also the runner of the host harness (tests/cpp/list_on_host.cpp), a stand-alone program."""
-import subprocess
-import tempfile
-from pathlib import Path
 
 import numpy as np
 
-from blocks_cases import BUILD, REGIONS, dense_region
-from helpers import ROOT
+from blocks_cases import REGIONS, dense_region
+from host_harness import HostRunner, build_harness
 from scan_cases import SCAN_CASES, make_scan_case  # noqa: F401  (the tests' parameters)
 from voxel_rs_amd import hip
 
@@ -114,34 +111,17 @@ def split_at(lo, size, axis, cut):
 
 
 def harness():
-    """tests/_build/list_on_host, built when it is older than its sources."""
-    BUILD.mkdir(exist_ok=True)
-    exe = BUILD / "list_on_host"
-    blocks = Path(ROOT) / "voxel-rs_amd" / "csrc" / "blocks"
-    deps = [Path(ROOT) / "tests" / "cpp" / "list_on_host.cpp", blocks / "vx_list.hpp", blocks / "vx_blocks.hpp", Path(ROOT) / "include" / "voxel_hip.h"]
-    if not exe.exists() or exe.stat().st_mtime < max(p.stat().st_mtime for p in deps):
-        cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", f"-I{ROOT}/include", f"-I{blocks}", str(deps[0]), "-o", str(exe)]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout
-    return exe
+    """tests/_build/list_on_host: host_harness.build_harness's."""
+    return build_harness("list_on_host")
 
 
-class HostLists:
+class HostLists(HostRunner):
     """The harness on one world: the frame is written once, every call is a run of the program."""
-
-    def __init__(self, exe, c):
-        self.exe, self.c = exe, c
-        self.dir = tempfile.TemporaryDirectory()
-        self.world = Path(self.dir.name) / "world.bin"
-        c.frame.tofile(self.world)
 
     def buffer(self, lo, size, flags, capacity):
         """(the `capacity` records of a buffer that held 0x5a bytes before the call, total, bricks)"""
-        out = Path(self.dir.name) / "out.bin"
-        args = [self.exe, self.c.svo_type, self.world, "list", *lo, *size, flags, capacity, out]
-        r = subprocess.run([str(a) for a in args], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout
-        raw = np.fromfile(out, dtype=np.uint32)
+        self.run("list", *lo, *size, flags, capacity, self.path("out.bin"))
+        raw = self.get("out.bin", np.uint32)
         assert len(raw) == 2 + 2 * capacity
         return raw[2:].view(hip.BLOCK_AT_DTYPE), int(raw[0]), int(raw[1])
 
@@ -151,9 +131,6 @@ class HostLists:
         records, again, _ = self.buffer(lo, size, flags, total)
         assert again == total
         return records, total
-
-    def close(self):
-        self.dir.cleanup()
 
 
 def differing(got, exp):

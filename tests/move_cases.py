@@ -6,15 +6,12 @@ in float64 of those float32 values, the clamps in Python integers, blocks_cases.
 and its first voxel in [z][y][x] order. Nothing of the code under test is used. Also the runner of the host harness
 (tests/cpp/move_on_host.cpp), a stand-alone program, plain and built with sanitizers."""
 import math
-import subprocess
-import tempfile
-from pathlib import Path
 
 import numpy as np
 
-from blocks_cases import BUILD, dense_region
+from blocks_cases import dense_region
+from host_harness import HostRunner, build_harness, outputs_differing
 from boxes_cases import FORMS, ONE_EXTENTS, Boxes, absent_id, box_truth, commonest_id, cover_of, invalid_boxes, resting_voxel
-from helpers import ROOT
 from list_cases import ANCHOR
 from scan_cases import SCAN_CASES, make_scan_case  # noqa: F401  (the tests' parameters)
 from voxel_rs_amd import hip
@@ -345,56 +342,26 @@ def overlaps_at(c, mv, origin):
 
 
 def harness(sanitize=False):
-    """tests/_build/move_on_host (or move_on_host_san: the same program under AddressSanitizer and UndefinedBehaviorSanitizer with the
-    float-to-integer conversion check, every finding fatal), built when it is older than its sources."""
-    BUILD.mkdir(exist_ok=True)
-    exe = BUILD / ("move_on_host_san" if sanitize else "move_on_host")
-    blocks = Path(ROOT) / "voxel-rs_amd" / "csrc" / "blocks"
-    deps = [Path(ROOT) / "tests" / "cpp" / "move_on_host.cpp", blocks / "vx_move.hpp", blocks / "vx_boxes.hpp", blocks / "vx_list.hpp", blocks / "vx_blocks.hpp",
-            Path(ROOT) / "include" / "voxel_hip.h"]
-    if not exe.exists() or exe.stat().st_mtime < max(p.stat().st_mtime for p in deps):
-        flags = ["-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fsanitize=float-cast-overflow", "-fno-sanitize-recover=all"] if sanitize else []
-        cmd = ["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", *flags, f"-I{ROOT}/include", f"-I{blocks}", str(deps[0]), "-o", str(exe)]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout
-    return exe
+    """tests/_build/move_on_host, or move_on_host_san: host_harness.build_harness's."""
+    return build_harness("move_on_host", sanitize, float_cast=True)
 
 
 def float_bits(v):
     return f"{int(np.array(v, dtype=np.float32).view(np.uint32)):08x}"
 
 
-class HostMoves:
+class HostMoves(HostRunner):
     """The harness on one world: the frame is written once, every call is a run of the program."""
 
-    def __init__(self, exe, c):
-        self.exe, self.c = exe, c
-        self.dir = tempfile.TemporaryDirectory()
-        self.world = Path(self.dir.name) / "world.bin"
-        c.frame.tofile(self.world)
-
     def records(self, mv, scale=1.0, skin=SKIN, order=YXZ, only_value=0):
-        d = Path(self.dir.name)
-        mv.raw.tofile(d / "raw.bin")
         at = mv.at
-        args = [self.exe, self.c.svo_type, self.world, "move", d / "raw.bin", len(mv), *at["origin"], *at.get("offset", (-1, 0)), *at["extents"], *at["motion"],
-                only_value, float_bits(scale), float_bits(skin), order, d / "out.bin"]
-        r = subprocess.run([str(a) for a in args], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout
-        out = np.fromfile(d / "out.bin", dtype=hip.MOVE_HIT_DTYPE)
+        self.run("move", self.put("raw.bin", mv.raw), len(mv), *at["origin"], *at.get("offset", (-1, 0)), *at["extents"], *at["motion"], only_value, float_bits(scale),
+                 float_bits(skin), order, self.path("out.bin"))
+        out = self.get("out.bin", hip.MOVE_HIT_DTYPE)
         assert len(out) == len(mv)
         return out
-
-    def close(self):
-        self.dir.cleanup()
 
 
 def differing(got, exp):
     """A message naming the first differing record of two MOVE_HIT_DTYPE arrays, or None. (Equal bytes: -0.0 is not 0.0, the padding counts.)"""
-    if got.shape != exp.shape:
-        return f"lengths differ: {got.shape} vs {exp.shape}"
-    if got.tobytes() == exp.tobytes():
-        return None
-    bad = np.flatnonzero((got.view(np.uint32).reshape(-1, 12) != exp.view(np.uint32).reshape(-1, 12)).any(axis=1))
-    i = int(bad[0])
-    return f"{len(bad)} records differ, first at {i}: got {got[i]}, expected {exp[i]}"
+    return outputs_differing((got,), (exp,))

@@ -10,15 +10,12 @@ which still end the descent above the brick) --, a seeded point set and a list o
 along the axis within the range, and the cell size from the chunk's LOD. Plain numpy over the dense arrays the worlds were built from
 (blocks_cases.lod_voxels for the LOD chunks); nothing of the code under test is used. Also the runner of the host harness
 (tests/cpp/scan_on_host.cpp), a stand-alone program."""
-import subprocess
-import tempfile
-from pathlib import Path
-
 import numpy as np
 
 from batch_cases import _chunk_of
-from blocks_cases import BUILD, dense_region, lod_voxels, make_block_case
-from helpers import ROOT, vra
+from blocks_cases import dense_region, lod_voxels, make_block_case
+from helpers import vra
+from host_harness import HostRunner, build_harness
 from voxel_rs_amd import hip, host
 
 NONE, OUTSIDE, TO_EDGE = hip.VX_SCAN_NONE, hip.VX_CELL_OUTSIDE, hip.VX_SCAN_TO_EDGE
@@ -320,69 +317,40 @@ def skipping_box(c):
 
 
 def harness():
-    """tests/_build/scan_on_host, built when it is older than its sources."""
-    BUILD.mkdir(exist_ok=True)
-    exe = BUILD / "scan_on_host"
-    blocks = Path(ROOT) / "voxel-rs_amd" / "csrc" / "blocks"
-    deps = [Path(ROOT) / "tests" / "cpp" / "scan_on_host.cpp", blocks / "vx_scan.hpp", blocks / "vx_blocks.hpp", Path(ROOT) / "include" / "voxel_hip.h"]
-    if not exe.exists() or exe.stat().st_mtime < max(p.stat().st_mtime for p in deps):
-        cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", f"-I{ROOT}/include", f"-I{blocks}", str(deps[0]), "-o", str(exe)]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout
-    return exe
-
-
-def _run(exe, args):
-    r = subprocess.run([str(exe)] + [str(a) for a in args], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    return r.stdout
+    """tests/_build/scan_on_host: host_harness.build_harness's."""
+    return build_harness("scan_on_host")
 
 
 def host_scan_points(exe, c, raw, stride, count, direction, reach):
     """`count` float[3] at `stride` bytes of `raw` through the harness: (SCAN_HIT_DTYPE records, loop trips a point)."""
-    with tempfile.TemporaryDirectory() as d:
-        d = Path(d)
-        c.frame.tofile(d / "world.bin")
-        np.asarray(raw).view(np.uint8).tofile(d / "points.bin")
-        _run(exe, [c.svo_type, d / "world.bin", "points", d / "points.bin", stride, count, direction, reach, d / "out.bin", d / "trips.bin"])
-        return np.fromfile(d / "out.bin", dtype=hip.SCAN_HIT_DTYPE), np.fromfile(d / "trips.bin", dtype=np.uint32)
+    h = HostScans(exe, c)
+    h.run("points", h.put("points.bin", raw), stride, count, direction, reach, h.path("out.bin"), h.path("trips.bin"))
+    out = h.get("out.bin", hip.SCAN_HIT_DTYPE), h.get("trips.bin", np.uint32)
+    h.close()
+    return out
 
 
 def host_scan_columns(exe, c, lo, size, direction):
     """The box through the harness's columns routine: (SCAN_HIT_DTYPE records [v][u], loop trips a tile)."""
-    _, u, v, _ = axes_of(direction)
-    with tempfile.TemporaryDirectory() as d:
-        d = Path(d)
-        c.frame.tofile(d / "world.bin")
-        _run(exe, [c.svo_type, d / "world.bin", "columns", *lo, *size, direction, d / "out.bin", d / "trips.bin"])
-        return np.fromfile(d / "out.bin", dtype=hip.SCAN_HIT_DTYPE).reshape(size[v], size[u]), np.fromfile(d / "trips.bin", dtype=np.uint32)
+    h = HostScans(exe, c)
+    out = h.columns(lo, size, direction), h.get("trips.bin", np.uint32)
+    h.close()
+    return out
 
 
-class HostScans:
+class HostScans(HostRunner):
     """The harness on one world for many calls (a streamed frame of several MB): the frame is written once, every call is a run of the program.
     The records of host_scan_points and host_scan_columns, without the trips."""
 
-    def __init__(self, exe, c):
-        self.exe, self.c = exe, c
-        self.dir = tempfile.TemporaryDirectory()
-        self.world = Path(self.dir.name) / "world.bin"
-        c.frame.tofile(self.world)
-
     def points(self, pts, direction, reach):
-        d = Path(self.dir.name)
         pts = np.ascontiguousarray(pts, dtype=np.float32)
-        pts.view(np.uint8).tofile(d / "points.bin")
-        _run(self.exe, [self.c.svo_type, self.world, "points", d / "points.bin", 12, len(pts), direction, reach, d / "out.bin", d / "trips.bin"])
-        return np.fromfile(d / "out.bin", dtype=hip.SCAN_HIT_DTYPE)
+        self.run("points", self.put("points.bin", pts), 12, len(pts), direction, reach, self.path("out.bin"), self.path("trips.bin"))
+        return self.get("out.bin", hip.SCAN_HIT_DTYPE)
 
     def columns(self, lo, size, direction):
         _, u, v, _ = axes_of(direction)
-        d = Path(self.dir.name)
-        _run(self.exe, [self.c.svo_type, self.world, "columns", *lo, *size, direction, d / "out.bin", d / "trips.bin"])
-        return np.fromfile(d / "out.bin", dtype=hip.SCAN_HIT_DTYPE).reshape(size[v], size[u])
-
-    def close(self):
-        self.dir.cleanup()
+        self.run("columns", *lo, *size, direction, self.path("out.bin"), self.path("trips.bin"))
+        return self.get("out.bin", hip.SCAN_HIT_DTYPE, shape=(size[v], size[u]))
 
 
 def differing(got, exp):

@@ -2,29 +2,15 @@
 probe compiled from include/voxel_hip.h with gcc, the way the C-ABI client is compiled), and the entry points' argument checks, which come
 before any HIP call, name the field they refuse."""
 import ctypes as C
-import subprocess
-from pathlib import Path
 
 import numpy as np
 
+from abi_checks import probe, refusing
 from helpers import vra  # noqa: F401
 from voxel_rs_amd import hip
 
-ROOT = Path(__file__).resolve().parent.parent
 _vp = C.c_void_p
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "voxel_hip.h"
-#define F(S, M) printf(#S "." #M " %zu %zu\n", offsetof(S, M), sizeof(((S*)0)->M))
-int main(void) {
-    printf("vx_block_cell %zu\nVX_CELL_OUTSIDE %lu\n", sizeof(vx_block_cell), (unsigned long)VX_CELL_OUTSIDE);
-    F(vx_block_cell, value);
-    F(vx_block_cell, cell_log2);
-    return 0;
-}
-"""
 
 
 def test_the_library_exports_them():
@@ -35,19 +21,13 @@ def test_the_library_exports_them():
 
 
 def test_the_record_has_the_headers_layout(tmp_path):
-    (tmp_path / "probe.c").write_text(PROBE)
-    exe = tmp_path / "probe"
-    r = subprocess.run(["gcc", "-std=c11", "-O1", "-Wall", "-Wextra", "-Werror", f"-I{ROOT}/include", str(tmp_path / "probe.c"), "-o", str(exe)],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    out = subprocess.run([str(exe)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    probe = {ln.split()[0]: tuple(int(v) for v in ln.split()[1:]) for ln in out.splitlines()}
-    assert probe["vx_block_cell"] == (8,) == (hip.BLOCK_CELL_DTYPE.itemsize,)
-    assert probe["VX_CELL_OUTSIDE"] == (hip.VX_CELL_OUTSIDE,) == (0xFFFFFFFF,)
+    said = probe(tmp_path, {"vx_block_cell": ["value", "cell_log2"]}, ["VX_CELL_OUTSIDE"])
+    assert said["vx_block_cell"] == (8,) == (hip.BLOCK_CELL_DTYPE.itemsize,)
+    assert said["VX_CELL_OUTSIDE"] == (hip.VX_CELL_OUTSIDE,) == (0xFFFFFFFF,)
     assert list(hip.BLOCK_CELL_DTYPE.names) == ["value", "cell_log2"]
     for f, at in (("value", 0), ("cell_log2", 4)):
         dt, offset = hip.BLOCK_CELL_DTYPE.fields[f][:2]
-        assert probe[f"vx_block_cell.{f}"] == (offset, dt.itemsize) == (at, 4) and dt.str == "<u4", f
+        assert said[f"vx_block_cell.{f}"] == (offset, dt.itemsize) == (at, 4) and dt.str == "<u4", f
 
 
 def test_block_points_argument_checks_need_no_device():
@@ -56,12 +36,11 @@ def test_block_points_argument_checks_need_no_device():
     L = hip.lib()
     pos = np.zeros((4, 4), dtype=np.float32)
     out = np.full(4 * 8 + 8, 0x5a, dtype=np.uint8)
-    sentinel = out.tobytes()
 
-    def refused(word, p=pos.ctypes.data, stride=12, count=4, memory=hip.VX_MEM_HOST, o=out.ctypes.data):
-        assert L.vx_block_points(None, _vp(p), stride, count, memory, _vp(o)) == 1
-        assert word in L.vx_last_error(), (word, L.vx_last_error())
-        assert out.tobytes() == sentinel
+    def call(p=pos.ctypes.data, stride=12, count=4, memory=hip.VX_MEM_HOST, o=out.ctypes.data):
+        return L.vx_block_points(None, _vp(p), stride, count, memory, _vp(o))
+
+    refused = refusing(L, call, (out,))
 
     refused(b"null context")
     for stride in (0, 4, 8, 13, 14, 18, 2):
@@ -90,13 +69,12 @@ def test_block_points_argument_checks_need_no_device():
 def test_read_region_argument_checks_need_no_device():
     L = hip.lib()
     out = np.full(64 + 8, 0x5a, dtype=np.uint8)
-    sentinel = out.tobytes()
     i3, u3 = C.c_int32 * 3, C.c_uint32 * 3
 
-    def refused(word, lo=(-3, 0, 5), size=(4, 2, 2), memory=hip.VX_MEM_HOST, o=out.ctypes.data):
-        rc = L.vx_read_region(None, C.byref(i3(*lo)) if lo is not None else None, C.byref(u3(*size)) if size is not None else None, memory, _vp(o))
-        assert rc == 1 and word in L.vx_last_error(), (word, rc, L.vx_last_error())
-        assert out.tobytes() == sentinel
+    def call(lo=(-3, 0, 5), size=(4, 2, 2), memory=hip.VX_MEM_HOST, o=out.ctypes.data):
+        return L.vx_read_region(None, C.byref(i3(*lo)) if lo is not None else None, C.byref(u3(*size)) if size is not None else None, memory, _vp(o))
+
+    refused = refusing(L, call, (out,))
 
     refused(b"null context")
     refused(b"null lo", lo=None)

@@ -2,43 +2,17 @@
 with gcc, the way the C-ABI client is compiled) and the Python binding and the Rust declarations agree with them, check_boxes' messages as
 the host harness prints them, and the entry point's argument checks, which come before any HIP call, name the field they refuse."""
 import ctypes as C
-import re
 import subprocess
-from pathlib import Path
 
 import numpy as np
 
 from boxes_cases import harness
+from abi_checks import Rust, probe, refusing
 from helpers import vra  # noqa: F401
 from voxel_rs_amd import hip
 
-ROOT = Path(__file__).resolve().parent.parent
 _vp = C.c_void_p
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "voxel_hip.h"
-#define F(S, M) printf(#S "." #M " %zu %zu\n", offsetof(S, M), sizeof(((S*)0)->M))
-int main(void) {
-    printf("vx_box_batch %zu\nvx_box_hit %zu\nVX_BOX_INVALID %lu\n", sizeof(vx_box_batch), sizeof(vx_box_hit), (unsigned long)VX_BOX_INVALID);
-    F(vx_box_batch, origin);
-    F(vx_box_batch, offset);
-    F(vx_box_batch, extents);
-    F(vx_box_batch, origin_stride);
-    F(vx_box_batch, offset_stride);
-    F(vx_box_batch, extents_stride);
-    F(vx_box_batch, only_value);
-    F(vx_box_hit, blocks);
-    F(vx_box_hit, value);
-    F(vx_box_hit, lo);
-    F(vx_box_hit, hi);
-    F(vx_entity, position);
-    F(vx_entity, aabb_offset);
-    F(vx_entity, aabb_extents);
-    return 0;
-}
-"""
 
 
 def test_the_library_exports_it():
@@ -49,42 +23,34 @@ def test_the_library_exports_it():
 
 
 def test_the_structs_have_the_headers_layout(tmp_path):
-    (tmp_path / "probe.c").write_text(PROBE)
-    exe = tmp_path / "probe"
-    r = subprocess.run(["gcc", "-std=c11", "-O1", "-Wall", "-Wextra", "-Werror", f"-I{ROOT}/include", str(tmp_path / "probe.c"), "-o", str(exe)],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    out = subprocess.run([str(exe)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    probe = {ln.split()[0]: tuple(int(v) for v in ln.split()[1:]) for ln in out.splitlines()}
-    assert probe["vx_box_hit"] == (32,) == (hip.BOX_HIT_DTYPE.itemsize,)
-    assert probe["vx_box_batch"] == (40,) == (C.sizeof(hip.BoxBatch),)
-    assert probe["VX_BOX_INVALID"] == (0xFFFFFFFF,) == (hip.VX_BOX_INVALID,)
+    said = probe(tmp_path, {"vx_box_batch": ["origin", "offset", "extents", "origin_stride", "offset_stride", "extents_stride", "only_value"], "vx_box_hit": ["blocks", "value", "lo", "hi"],
+                             "vx_entity": ["position", "aabb_offset", "aabb_extents"]}, ["VX_BOX_INVALID"])
+    assert said["vx_box_hit"] == (32,) == (hip.BOX_HIT_DTYPE.itemsize,)
+    assert said["vx_box_batch"] == (40,) == (C.sizeof(hip.BoxBatch),)
+    assert said["VX_BOX_INVALID"] == (0xFFFFFFFF,) == (hip.VX_BOX_INVALID,)
     assert [n for n, _ in hip.BoxBatch._fields_] == ["origin", "offset", "extents", "origin_stride", "offset_stride", "extents_stride", "only_value"]
     for name, _ in hip.BoxBatch._fields_:
         field = getattr(hip.BoxBatch, name)
-        assert probe[f"vx_box_batch.{name}"] == (field.offset, field.size), name
+        assert said[f"vx_box_batch.{name}"] == (field.offset, field.size), name
     assert list(hip.BOX_HIT_DTYPE.names) == ["blocks", "value", "lo", "hi"]
     for f, at, size, kind in (("blocks", 0, 4, "<u4"), ("value", 4, 4, "<u4"), ("lo", 8, 12, "<i4"), ("hi", 20, 12, "<i4")):
         dt, offset = hip.BOX_HIT_DTYPE.fields[f][:2]
-        assert probe[f"vx_box_hit.{f}"] == (offset, dt.itemsize) == (at, size) and dt.base.str == kind, f
+        assert said[f"vx_box_hit.{f}"] == (offset, dt.itemsize) == (at, size) and dt.base.str == kind, f
     # a vx_entity is read in place: entity_boxes' views lie where the header's fields do
     e = np.zeros(3, dtype=hip.ENTITY_DTYPE)
     origin, extents, offset = hip.entity_boxes(e)
     for view, field in ((origin, "position"), (offset, "aabb_offset"), (extents, "aabb_extents")):
-        assert view.ctypes.data - e.ctypes.data == probe[f"vx_entity.{field}"][0] and view.strides == (64, 4) and view.shape == (3, 3), field
+        assert view.ctypes.data - e.ctypes.data == said[f"vx_entity.{field}"][0] and view.strides == (64, 4) and view.shape == (3, 3), field
 
 
 def test_the_rust_declarations_agree():
     """What tests/test_rust_shim.py's parser cannot see of this call: the constant (the header writes it in hexadecimal with a `u` suffix)."""
-    text = (ROOT / "integration" / "rust" / "voxel_hip_sys.rs").read_text()
-    assert re.search(r"pub const VX_BOX_INVALID\s*:\s*u32\s*=\s*u32::MAX\s*;", text)
-    body = re.search(r"pub struct vx_box_hit\s*\{(.*?)\}", text, flags=re.S).group(1)
-    assert re.findall(r"pub\s+(\w+)\s*:\s*([^,\n]+),", body) == [("blocks", "u32"), ("value", "u32"), ("lo", "[i32; 3]"), ("hi", "[i32; 3]")]
-    body = re.search(r"pub struct vx_box_batch\s*\{(.*?)\}", text, flags=re.S).group(1)
-    assert [n for n, _ in re.findall(r"pub\s+(\w+)\s*:\s*([^,\n]+),", body)] == [n for n, _ in hip.BoxBatch._fields_]
-    assert "size_of::<vx_box_hit>() == 32" in text and "size_of::<vx_box_batch>() == 40" in text
-    decl = re.search(r"pub fn vx_overlap_boxes\((.*?)\)\s*->\s*c_int;", text, flags=re.S).group(1)
-    assert [a.split(":")[0].strip() for a in decl.split(",")] == ["ctx", "boxes", "count", "memory", "out"]
+    rust = Rust()
+    assert rust.const("VX_BOX_INVALID") == ("u32", "u32::MAX")
+    assert rust.struct("vx_box_hit") == [("blocks", "u32"), ("value", "u32"), ("lo", "[i32; 3]"), ("hi", "[i32; 3]")]
+    assert [n for n, _ in rust.struct("vx_box_batch")] == [n for n, _ in hip.BoxBatch._fields_]
+    assert rust.asserts_size("vx_box_hit", 32) and rust.asserts_size("vx_box_batch", 40)
+    assert rust.args("vx_overlap_boxes") == ["ctx", "boxes", "count", "memory", "out"]
 
 
 def test_check_boxes_messages_through_the_harness():
@@ -103,18 +69,17 @@ def test_argument_checks_need_no_device():
     sentinel-filled records stay as they are."""
     L = hip.lib()
     out = np.full(32 * 4 + 16, 0x5a, dtype=np.uint8)
-    sentinel = out.tobytes()
     v = np.arange(64, dtype=np.float32)
     base = v.ctypes.data
     assert base % 4 == 0
 
-    def refused(word, count=2, memory=hip.VX_MEM_HOST, o=out.ctypes.data, boxes=True, **fields):
+    def call(count=2, memory=hip.VX_MEM_HOST, o=out.ctypes.data, boxes=True, **fields):
         b = hip.BoxBatch(base, base + 12 * 4, base + 24 * 4, 12, 12, 12, 0)
         for k, val in fields.items():
             setattr(b, k, val)
-        rc = L.vx_overlap_boxes(None, C.byref(b) if boxes else None, count, memory, _vp(o))
-        assert rc == 1 and word in L.vx_last_error(), (word, rc, L.vx_last_error())
-        assert out.tobytes() == sentinel
+        return L.vx_overlap_boxes(None, C.byref(b) if boxes else None, count, memory, _vp(o))
+
+    refused = refusing(L, call, (out,))
 
     refused(b"null context")
     refused(b"null boxes", boxes=False)

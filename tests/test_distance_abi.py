@@ -3,32 +3,17 @@ include/voxel_hip.h with gcc, the way the C-ABI client is compiled) and the Pyth
 check_distance's messages as the host harness prints them, and the entry point's argument checks, which come before any HIP call, name the
 field they refuse."""
 import ctypes as C
-import re
 import subprocess
-from pathlib import Path
 
 import numpy as np
 
+from abi_checks import ROOT, Rust, probe, refusing
 from distance_cases import harness
 from helpers import vra  # noqa: F401
 from voxel_rs_amd import hip
 
-ROOT = Path(__file__).resolve().parent.parent
-
 SHAPE_FIELDS = ["size", "pass_value", "match_value", "flags", "_pad"]
 INFO_FIELDS = ["targets", "farthest", "where", "faces"]
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "voxel_hip.h"
-#define F(S, M) printf(#S "." #M " %zu %zu\n", offsetof(S, M), sizeof(((S*)0)->M))
-#define K(N) printf(#N " %lu\n", (unsigned long)N)
-int main(void) {
-    printf("vx_distance_shape %zu\nvx_distance_info %zu\n", sizeof(vx_distance_shape), sizeof(vx_distance_info));
-    K(VX_DISTANCE_NONE); K(VX_DISTANCE_TO_AIR);
-""" + "".join(f"    F(vx_distance_shape, {f});\n" for f in SHAPE_FIELDS) + "".join(f"    F(vx_distance_info, {f});\n" for f in INFO_FIELDS) + """    return 0;
-}
-"""
 CONSTANTS = {"VX_DISTANCE_NONE": 0xFFFF, "VX_DISTANCE_TO_AIR": 1}
 
 
@@ -40,25 +25,19 @@ def test_the_library_exports_it():
 
 
 def test_the_structs_have_the_headers_layout(tmp_path):
-    (tmp_path / "probe.c").write_text(PROBE)
-    exe = tmp_path / "probe"
-    r = subprocess.run(["gcc", "-std=c11", "-O1", "-Wall", "-Wextra", "-Werror", f"-I{ROOT}/include", str(tmp_path / "probe.c"), "-o", str(exe)],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    out = subprocess.run([str(exe)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    probe = {ln.split()[0]: tuple(int(v) for v in ln.split()[1:]) for ln in out.splitlines()}
-    assert probe["vx_distance_info"] == (16,) == (hip.DISTANCE_INFO_DTYPE.itemsize,)
-    assert probe["vx_distance_shape"] == (32,) == (C.sizeof(hip.DistanceShape),)
+    said = probe(tmp_path, {"vx_distance_shape": SHAPE_FIELDS, "vx_distance_info": INFO_FIELDS}, CONSTANTS)
+    assert said["vx_distance_info"] == (16,) == (hip.DISTANCE_INFO_DTYPE.itemsize,)
+    assert said["vx_distance_shape"] == (32,) == (C.sizeof(hip.DistanceShape),)
     for name, value in CONSTANTS.items():
-        assert probe[name] == (value,) == (getattr(hip, name),), name
+        assert said[name] == (value,) == (getattr(hip, name),), name
     assert [n for n, _ in hip.DistanceShape._fields_] == SHAPE_FIELDS
     for name, _ in hip.DistanceShape._fields_:
         field = getattr(hip.DistanceShape, name)
-        assert probe[f"vx_distance_shape.{name}"] == (field.offset, field.size), name
+        assert said[f"vx_distance_shape.{name}"] == (field.offset, field.size), name
     assert list(hip.DISTANCE_INFO_DTYPE.names) == INFO_FIELDS
     for k, f in enumerate(INFO_FIELDS):
         dt, offset = hip.DISTANCE_INFO_DTYPE.fields[f][:2]
-        assert probe[f"vx_distance_info.{f}"] == (offset, dt.itemsize) == (4 * k, 4) and dt.str == "<u4", f
+        assert said[f"vx_distance_info.{f}"] == (offset, dt.itemsize) == (4 * k, 4) and dt.str == "<u4", f
     s = hip.distance_shape((31, 3, 17), 9, 0, 1)
     assert (list(s.size), s.pass_value, s.match_value, s.flags, list(s._pad)) == ([31, 3, 17], 9, 0, 1, [0, 0])
     s = hip.distance_shape((1, 1, 1))
@@ -67,18 +46,14 @@ def test_the_structs_have_the_headers_layout(tmp_path):
 
 def test_the_rust_declarations_agree():
     """What tests/test_rust_shim.py's parser cannot see of this call: the constants (the header writes them with a `u` suffix)."""
-    text = (ROOT / "integration" / "rust" / "voxel_hip_sys.rs").read_text()
+    rust = Rust()
     for name, value in CONSTANTS.items():
-        m = re.search(rf"pub const {name}\s*:\s*(u16|u32)\s*=\s*([^;]+);", text)
-        assert m, name
-        assert int(m.group(2).strip().replace("_", ""), 0) == value, name
-    body = re.search(r"pub struct vx_distance_info\s*\{(.*?)\}", text, flags=re.S).group(1)
-    assert re.findall(r"pub\s+(?:r#)?(\w+)\s*:\s*([^,\n]+),", body) == [(n, "u32") for n in INFO_FIELDS]
-    body = re.search(r"pub struct vx_distance_shape\s*\{(.*?)\}", text, flags=re.S).group(1)
-    assert re.findall(r"pub\s+(\w+)\s*:\s*([^,\n]+),", body) == [("size", "[u32; 3]")] + [(n, "u32") for n in SHAPE_FIELDS[1:-1]] + [("_pad", "[u32; 2]")]
-    assert "size_of::<vx_distance_info>() == 16" in text and "size_of::<vx_distance_shape>() == 32" in text
-    decl = re.search(r"pub fn vx_distance_boxes\((.*?)\)\s*->\s*c_int;", text, flags=re.S).group(1)
-    assert [a.split(":")[0].strip() for a in decl.split(",")] == ["ctx", "lo", "lo_stride", "count", "shape", "memory", "fields", "field_stride", "info"]
+        kind, got = rust.const_int(name)
+        assert kind in ("u16", "u32") and got == value, name
+    assert rust.struct("vx_distance_info") == [(n, "u32") for n in INFO_FIELDS]
+    assert rust.struct("vx_distance_shape") == [("size", "[u32; 3]")] + [(n, "u32") for n in SHAPE_FIELDS[1:-1]] + [("_pad", "[u32; 2]")]
+    assert rust.asserts_size("vx_distance_info", 16) and rust.asserts_size("vx_distance_shape", 32)
+    assert rust.args("vx_distance_boxes") == ["ctx", "lo", "lo_stride", "count", "shape", "memory", "fields", "field_stride", "info"]
     header = (ROOT / "include" / "voxel_hip.h").read_text()
     assert header.index("int vx_label_boxes(") < header.index("int vx_distance_boxes(") < header.index("int vx_physics_step(")
 
@@ -104,20 +79,18 @@ def test_argument_checks_need_no_device():
     L = hip.lib()
     fields = np.full(2 * 8192 + 32, 0x5a, dtype=np.uint8)
     info = np.full(3 * 16, 0x5a, dtype=np.uint8)
-    sentinel = fields.tobytes() + info.tobytes()
     v = np.arange(64, dtype=np.int32)
     base = v.ctypes.data
     u3 = C.c_uint32 * 3
     assert base % 4 == 0
 
-    def refused(word, count=2, memory=hip.VX_MEM_HOST, lo=base, lo_stride=12, f=fields.ctypes.data, field_stride=0, i=info.ctypes.data, shape=True, **shape_fields):
+    def call(count=2, memory=hip.VX_MEM_HOST, lo=base, lo_stride=12, f=fields.ctypes.data, field_stride=0, i=info.ctypes.data, shape=True, **shape_fields):
         s = hip.distance_shape((16, 16, 16))
         for k, val in shape_fields.items():
             setattr(s, k, val)
-        rc = L.vx_distance_boxes(None, lo, lo_stride, count, C.byref(s) if shape else None, memory, f, field_stride, i)
-        assert rc == 1 and word in L.vx_last_error(), (word, rc, L.vx_last_error())
-        assert fields.tobytes() + info.tobytes() == sentinel
+        return L.vx_distance_boxes(None, lo, lo_stride, count, C.byref(s) if shape else None, memory, f, field_stride, i)
 
+    refused = refusing(L, call, (fields, info))
     refused(b"null context")
     refused(b"distance_boxes", f=None, i=None)  # (the call is named in front of what it refuses)
     refused(b"VX_MEM", memory=5)

@@ -2,40 +2,17 @@
 gcc, the way the C-ABI client is compiled) and the Python binding and the Rust declarations agree with them, check_flood's messages as the
 host harness prints them, and the entry point's argument checks, which come before any HIP call, name the field they refuse."""
 import ctypes as C
-import re
 import subprocess
-from pathlib import Path
 
 import numpy as np
 
 from flood_cases import harness
+from abi_checks import ROOT, Rust, probe, refusing
 from helpers import vra  # noqa: F401
 from voxel_rs_amd import hip
 
-ROOT = Path(__file__).resolve().parent.parent
 _vp = C.c_void_p
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "voxel_hip.h"
-#define F(S, M) printf(#S "." #M " %zu %zu\n", offsetof(S, M), sizeof(((S*)0)->M))
-#define K(N) printf(#N " %lu\n", (unsigned long)N)
-int main(void) {
-    printf("vx_flood_shape %zu\nvx_flood_info %zu\n", sizeof(vx_flood_shape), sizeof(vx_flood_info));
-    K(VX_FLOOD_MAX_STEPS); K(VX_FLOOD_NO_POSITION); K(VX_FLOOD_UNREACHED); K(VX_FLOOD_BLOCKED); K(VX_FLOOD_SEED_ALWAYS); K(VX_FLOOD_INVALID);
-    F(vx_flood_shape, size);
-    F(vx_flood_shape, seed_at);
-    F(vx_flood_shape, max_steps);
-    F(vx_flood_shape, pass_value);
-    F(vx_flood_shape, flags);
-    F(vx_flood_info, reached);
-    F(vx_flood_info, farthest);
-    F(vx_flood_info, faces);
-    F(vx_flood_info, seed_value);
-    return 0;
-}
-"""
 CONSTANTS = {"VX_FLOOD_MAX_STEPS": 250, "VX_FLOOD_NO_POSITION": 0xFD, "VX_FLOOD_UNREACHED": 0xFE, "VX_FLOOD_BLOCKED": 0xFF, "VX_FLOOD_SEED_ALWAYS": 1,
              "VX_FLOOD_INVALID": 0xFFFFFFFF}
 
@@ -48,45 +25,33 @@ def test_the_library_exports_it():
 
 
 def test_the_structs_have_the_headers_layout(tmp_path):
-    (tmp_path / "probe.c").write_text(PROBE)
-    exe = tmp_path / "probe"
-    r = subprocess.run(["gcc", "-std=c11", "-O1", "-Wall", "-Wextra", "-Werror", f"-I{ROOT}/include", str(tmp_path / "probe.c"), "-o", str(exe)],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    out = subprocess.run([str(exe)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    probe = {ln.split()[0]: tuple(int(v) for v in ln.split()[1:]) for ln in out.splitlines()}
-    assert probe["vx_flood_info"] == (16,) == (hip.FLOOD_INFO_DTYPE.itemsize,)
-    assert probe["vx_flood_shape"] == (36,) == (C.sizeof(hip.FloodShape),)
+    said = probe(tmp_path, {"vx_flood_shape": ["size", "seed_at", "max_steps", "pass_value", "flags"], "vx_flood_info": ["reached", "farthest", "faces", "seed_value"]}, CONSTANTS)
+    assert said["vx_flood_info"] == (16,) == (hip.FLOOD_INFO_DTYPE.itemsize,)
+    assert said["vx_flood_shape"] == (36,) == (C.sizeof(hip.FloodShape),)
     for name, value in CONSTANTS.items():
-        assert probe[name] == (value,) == (getattr(hip, name),), name
+        assert said[name] == (value,) == (getattr(hip, name),), name
     assert [n for n, _ in hip.FloodShape._fields_] == ["size", "seed_at", "max_steps", "pass_value", "flags"]
     for name, _ in hip.FloodShape._fields_:
         field = getattr(hip.FloodShape, name)
-        assert probe[f"vx_flood_shape.{name}"] == (field.offset, field.size), name
+        assert said[f"vx_flood_shape.{name}"] == (field.offset, field.size), name
     assert list(hip.FLOOD_INFO_DTYPE.names) == ["reached", "farthest", "faces", "seed_value"]
     for k, f in enumerate(hip.FLOOD_INFO_DTYPE.names):
         dt, offset = hip.FLOOD_INFO_DTYPE.fields[f][:2]
-        assert probe[f"vx_flood_info.{f}"] == (offset, dt.itemsize) == (4 * k, 4) and dt.str == "<u4", f
+        assert said[f"vx_flood_info.{f}"] == (offset, dt.itemsize) == (4 * k, 4) and dt.str == "<u4", f
     s = hip.flood_shape((31, 3, 17), max_steps=24, pass_value=9, flags=1)
     assert (list(s.size), list(s.seed_at), s.max_steps, s.pass_value, s.flags) == ([31, 3, 17], [15, 1, 8], 24, 9, 1)
 
 
 def test_the_rust_declarations_agree():
     """What tests/test_rust_shim.py's parser cannot see of this call: the constants (the header writes them in hexadecimal with a `u` suffix)."""
-    text = (ROOT / "integration" / "rust" / "voxel_hip_sys.rs").read_text()
+    rust = Rust()
     for name, value in CONSTANTS.items():
         kind = "u8" if name in ("VX_FLOOD_NO_POSITION", "VX_FLOOD_UNREACHED", "VX_FLOOD_BLOCKED") else "u32"
-        m = re.search(rf"pub const {name}\s*:\s*{kind}\s*=\s*([^;]+);", text)
-        assert m, name
-        said = m.group(1).strip()
-        assert (said == "u32::MAX" and value == 0xFFFFFFFF) or int(said.replace("_", ""), 0) == value, name
-    body = re.search(r"pub struct vx_flood_info\s*\{(.*?)\}", text, flags=re.S).group(1)
-    assert re.findall(r"pub\s+(\w+)\s*:\s*([^,\n]+),", body) == [("reached", "u32"), ("farthest", "u32"), ("faces", "u32"), ("seed_value", "u32")]
-    body = re.search(r"pub struct vx_flood_shape\s*\{(.*?)\}", text, flags=re.S).group(1)
-    assert re.findall(r"pub\s+(\w+)\s*:\s*([^,\n]+),", body) == [("size", "[u32; 3]"), ("seed_at", "[u32; 3]"), ("max_steps", "u32"), ("pass_value", "u32"), ("flags", "u32")]
-    assert "size_of::<vx_flood_info>() == 16" in text and "size_of::<vx_flood_shape>() == 36" in text
-    decl = re.search(r"pub fn vx_flood_points\((.*?)\)\s*->\s*c_int;", text, flags=re.S).group(1)
-    assert [a.split(":")[0].strip() for a in decl.split(",")] == ["ctx", "pos", "pos_stride", "count", "shape", "memory", "fields", "field_stride", "info"]
+        assert rust.const_int(name) == (kind, value), name
+    assert rust.struct("vx_flood_info") == [("reached", "u32"), ("farthest", "u32"), ("faces", "u32"), ("seed_value", "u32")]
+    assert rust.struct("vx_flood_shape") == [("size", "[u32; 3]"), ("seed_at", "[u32; 3]"), ("max_steps", "u32"), ("pass_value", "u32"), ("flags", "u32")]
+    assert rust.asserts_size("vx_flood_info", 16) and rust.asserts_size("vx_flood_shape", 36)
+    assert rust.args("vx_flood_points") == ["ctx", "pos", "pos_stride", "count", "shape", "memory", "fields", "field_stride", "info"]
 
 
 def test_check_flood_messages_through_the_harness():
@@ -109,20 +74,18 @@ def test_argument_checks_need_no_device():
     L = hip.lib()
     fields = np.full(2 * 4928 + 32, 0x5a, dtype=np.uint8)
     info = np.full(3 * 16, 0x5a, dtype=np.uint8)
-    sentinel = fields.tobytes() + info.tobytes()
     v = np.arange(64, dtype=np.float32)
     base = v.ctypes.data
     u3 = C.c_uint32 * 3
     assert base % 4 == 0
 
-    def refused(word, count=2, memory=hip.VX_MEM_HOST, pos=base, pos_stride=12, f=fields.ctypes.data, field_stride=0, i=info.ctypes.data, shape=True, **shape_fields):
+    def call(count=2, memory=hip.VX_MEM_HOST, pos=base, pos_stride=12, f=fields.ctypes.data, field_stride=0, i=info.ctypes.data, shape=True, **shape_fields):
         s = hip.flood_shape((17, 17, 17), (8, 8, 8), 250)
         for k, val in shape_fields.items():
             setattr(s, k, val)
-        rc = L.vx_flood_points(None, pos, pos_stride, count, C.byref(s) if shape else None, memory, f, field_stride, i)
-        assert rc == 1 and word in L.vx_last_error(), (word, rc, L.vx_last_error())
-        assert fields.tobytes() + info.tobytes() == sentinel
+        return L.vx_flood_points(None, pos, pos_stride, count, C.byref(s) if shape else None, memory, f, field_stride, i)
 
+    refused = refusing(L, call, (fields, info))
     refused(b"null context")
     refused(b"VX_MEM", memory=5)
     refused(b"VX_MEM", memory=-1)

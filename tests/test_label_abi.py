@@ -2,35 +2,20 @@
 with gcc, the way the C-ABI client is compiled) and the Python binding and the Rust declarations agree with them, check_label's messages as
 the host harness prints them, and the entry point's argument checks, which come before any HIP call, name the field they refuse."""
 import ctypes as C
-import re
 import subprocess
-from pathlib import Path
 
 import numpy as np
 
+from abi_checks import ROOT, Rust, probe, refusing
 from helpers import vra  # noqa: F401
 from label_cases import harness
 from voxel_rs_amd import hip
 
-ROOT = Path(__file__).resolve().parent.parent
 _vp = C.c_void_p
 
 SHAPE_FIELDS = ["size", "anchor_faces", "max_pieces", "max_steps", "pass_value", "flags"]
 PIECE_FIELDS = ["cells", "lo", "hi", "where"]
 INFO_FIELDS = ["solid", "held", "pieces", "loose", "more", "steps", "faces", "flags"]
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "voxel_hip.h"
-#define F(S, M) printf(#S "." #M " %zu %zu\n", offsetof(S, M), sizeof(((S*)0)->M))
-#define K(N) printf(#N " %lu\n", (unsigned long)N)
-int main(void) {
-    printf("vx_label_shape %zu\nvx_label_piece %zu\nvx_label_info %zu\n", sizeof(vx_label_shape), sizeof(vx_label_piece), sizeof(vx_label_info));
-    K(VX_LABEL_MAX_PIECES); K(VX_LABEL_MAX_STEPS); K(VX_LABEL_AIR); K(VX_LABEL_MORE); K(VX_LABEL_HELD); K(VX_LABEL_ALL_FACES); K(VX_LABEL_CUT);
-""" + "".join(f"    F(vx_label_shape, {f});\n" for f in SHAPE_FIELDS) + "".join(f"    F(vx_label_piece, {f});\n" for f in PIECE_FIELDS) + "".join(
-    f"    F(vx_label_info, {f});\n" for f in INFO_FIELDS) + """    return 0;
-}
-"""
 CONSTANTS = {"VX_LABEL_MAX_PIECES": 250, "VX_LABEL_MAX_STEPS": 4096, "VX_LABEL_AIR": 0, "VX_LABEL_MORE": 0xFE, "VX_LABEL_HELD": 0xFF, "VX_LABEL_ALL_FACES": 0x3F,
              "VX_LABEL_CUT": 1}
 
@@ -43,27 +28,21 @@ def test_the_library_exports_it():
 
 
 def test_the_structs_have_the_headers_layout(tmp_path):
-    (tmp_path / "probe.c").write_text(PROBE)
-    exe = tmp_path / "probe"
-    r = subprocess.run(["gcc", "-std=c11", "-O1", "-Wall", "-Wextra", "-Werror", f"-I{ROOT}/include", str(tmp_path / "probe.c"), "-o", str(exe)],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    out = subprocess.run([str(exe)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    probe = {ln.split()[0]: tuple(int(v) for v in ln.split()[1:]) for ln in out.splitlines()}
-    assert probe["vx_label_info"] == (32,) == (hip.LABEL_INFO_DTYPE.itemsize,)
-    assert probe["vx_label_piece"] == (16,) == (hip.LABEL_PIECE_DTYPE.itemsize,)
-    assert probe["vx_label_shape"] == (32,) == (C.sizeof(hip.LabelShape),)
+    said = probe(tmp_path, {"vx_label_shape": SHAPE_FIELDS, "vx_label_piece": PIECE_FIELDS, "vx_label_info": INFO_FIELDS}, CONSTANTS)
+    assert said["vx_label_info"] == (32,) == (hip.LABEL_INFO_DTYPE.itemsize,)
+    assert said["vx_label_piece"] == (16,) == (hip.LABEL_PIECE_DTYPE.itemsize,)
+    assert said["vx_label_shape"] == (32,) == (C.sizeof(hip.LabelShape),)
     for name, value in CONSTANTS.items():
-        assert probe[name] == (value,) == (getattr(hip, name),), name
+        assert said[name] == (value,) == (getattr(hip, name),), name
     assert [n for n, _ in hip.LabelShape._fields_] == SHAPE_FIELDS
     for name, _ in hip.LabelShape._fields_:
         field = getattr(hip.LabelShape, name)
-        assert probe[f"vx_label_shape.{name}"] == (field.offset, field.size), name
+        assert said[f"vx_label_shape.{name}"] == (field.offset, field.size), name
     for struct, dtype, names in (("vx_label_piece", hip.LABEL_PIECE_DTYPE, PIECE_FIELDS), ("vx_label_info", hip.LABEL_INFO_DTYPE, INFO_FIELDS)):
         assert list(dtype.names) == names
         for k, f in enumerate(names):
             dt, offset = dtype.fields[f][:2]
-            assert probe[f"{struct}.{f}"] == (offset, dt.itemsize) == (4 * k, 4) and dt.str == "<u4", f
+            assert said[f"{struct}.{f}"] == (offset, dt.itemsize) == (4 * k, 4) and dt.str == "<u4", f
     s = hip.label_shape((31, 3, 17), 0x04, 4, 24, 9)
     assert (list(s.size), s.anchor_faces, s.max_pieces, s.max_steps, s.pass_value, s.flags) == ([31, 3, 17], 4, 4, 24, 9, 0)
     s = hip.label_shape((1, 1, 1))
@@ -72,19 +51,15 @@ def test_the_structs_have_the_headers_layout(tmp_path):
 
 def test_the_rust_declarations_agree():
     """What tests/test_rust_shim.py's parser cannot see of this call: the constants (the header writes them with a `u` suffix)."""
-    text = (ROOT / "integration" / "rust" / "voxel_hip_sys.rs").read_text()
+    rust = Rust()
     for name, value in CONSTANTS.items():
-        m = re.search(rf"pub const {name}\s*:\s*(u8|u32)\s*=\s*([^;]+);", text)
-        assert m, name
-        assert int(m.group(2).strip().replace("_", ""), 0) == value, name
+        kind, got = rust.const_int(name)
+        assert kind in ("u8", "u32") and got == value, name
     for struct, names in (("vx_label_piece", PIECE_FIELDS), ("vx_label_info", INFO_FIELDS)):
-        body = re.search(rf"pub struct {struct}\s*\{{(.*?)\}}", text, flags=re.S).group(1)
-        assert re.findall(r"pub\s+(?:r#)?(\w+)\s*:\s*([^,\n]+),", body) == [(n, "u32") for n in names], struct
-    body = re.search(r"pub struct vx_label_shape\s*\{(.*?)\}", text, flags=re.S).group(1)
-    assert re.findall(r"pub\s+(\w+)\s*:\s*([^,\n]+),", body) == [("size", "[u32; 3]")] + [(n, "u32") for n in SHAPE_FIELDS[1:]]
-    assert "size_of::<vx_label_info>() == 32" in text and "size_of::<vx_label_piece>() == 16" in text and "size_of::<vx_label_shape>() == 32" in text
-    decl = re.search(r"pub fn vx_label_boxes\((.*?)\)\s*->\s*c_int;", text, flags=re.S).group(1)
-    assert [a.split(":")[0].strip() for a in decl.split(",")] == ["ctx", "lo", "lo_stride", "count", "shape", "memory", "fields", "field_stride", "pieces", "info"]
+        assert rust.struct(struct) == [(n, "u32") for n in names], struct
+    assert rust.struct("vx_label_shape") == [("size", "[u32; 3]")] + [(n, "u32") for n in SHAPE_FIELDS[1:]]
+    assert rust.asserts_size("vx_label_info", 32) and rust.asserts_size("vx_label_piece", 16) and rust.asserts_size("vx_label_shape", 32)
+    assert rust.args("vx_label_boxes") == ["ctx", "lo", "lo_stride", "count", "shape", "memory", "fields", "field_stride", "pieces", "info"]
 
 
 def test_check_label_messages_through_the_harness():
@@ -113,21 +88,19 @@ def test_argument_checks_need_no_device():
     fields = np.full(2 * 4096 + 32, 0x5a, dtype=np.uint8)
     pieces = np.full(2 * 250 * 16 + 16, 0x5a, dtype=np.uint8)
     info = np.full(3 * 32, 0x5a, dtype=np.uint8)
-    sentinel = fields.tobytes() + pieces.tobytes() + info.tobytes()
     v = np.arange(64, dtype=np.int32)
     base = v.ctypes.data
     u3 = C.c_uint32 * 3
     assert base % 4 == 0
 
-    def refused(word, count=2, memory=hip.VX_MEM_HOST, lo=base, lo_stride=12, f=fields.ctypes.data, field_stride=0, p=pieces.ctypes.data, i=info.ctypes.data, shape=True,
+    def call(count=2, memory=hip.VX_MEM_HOST, lo=base, lo_stride=12, f=fields.ctypes.data, field_stride=0, p=pieces.ctypes.data, i=info.ctypes.data, shape=True,
                 **shape_fields):
         s = hip.label_shape((16, 16, 16))
         for k, val in shape_fields.items():
             setattr(s, k, val)
-        rc = L.vx_label_boxes(None, lo, lo_stride, count, C.byref(s) if shape else None, memory, f, field_stride, p, i)
-        assert rc == 1 and word in L.vx_last_error(), (word, rc, L.vx_last_error())
-        assert fields.tobytes() + pieces.tobytes() + info.tobytes() == sentinel
+        return L.vx_label_boxes(None, lo, lo_stride, count, C.byref(s) if shape else None, memory, f, field_stride, p, i)
 
+    refused = refusing(L, call, (fields, pieces, info))
     refused(b"null context")
     refused(b"VX_MEM", memory=5)
     refused(b"VX_MEM", memory=-1)

@@ -2,39 +2,17 @@
 gcc, the way the C-ABI client is compiled) and the Python binding and the Rust declarations agree with them, check_light's messages as the
 host harness prints them, and the entry point's argument checks, which come before any HIP call, name the field they refuse."""
 import ctypes as C
-import re
 import subprocess
-from pathlib import Path
 
 import numpy as np
 
+from abi_checks import ROOT, Rust, probe, refusing
 from helpers import vra  # noqa: F401
 from light_cases import harness
 from voxel_rs_amd import hip
 
-ROOT = Path(__file__).resolve().parent.parent
 _vp = C.c_void_p
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "voxel_hip.h"
-#define F(S, M) printf(#S "." #M " %zu %zu\n", offsetof(S, M), sizeof(((S*)0)->M))
-#define K(N) printf(#N " %lu\n", (unsigned long)N)
-int main(void) {
-    printf("vx_light_shape %zu\nvx_light_info %zu\n", sizeof(vx_light_shape), sizeof(vx_light_info));
-    K(VX_LIGHT_MAX_SIDE); K(VX_LIGHT_MAX_PROPS); K(VX_LIGHT_TRANSPARENT); K(VX_LIGHT_NO_SKY); K(VX_LIGHT_NO_BLOCKS); K(VX_LIGHT_INVALID);
-    F(vx_light_shape, size);
-    F(vx_light_shape, flags);
-    F(vx_light_shape, props);
-    F(vx_light_shape, props_count);
-    F(vx_light_info, lit);
-    F(vx_light_info, sources);
-    F(vx_light_info, open_columns);
-    F(vx_light_info, faces);
-    return 0;
-}
-"""
 CONSTANTS = {"VX_LIGHT_MAX_SIDE": 48, "VX_LIGHT_MAX_PROPS": 4096, "VX_LIGHT_TRANSPARENT": 0x10, "VX_LIGHT_NO_SKY": 1, "VX_LIGHT_NO_BLOCKS": 2,
              "VX_LIGHT_INVALID": 0xFFFFFFFF}
 
@@ -47,25 +25,19 @@ def test_the_library_exports_it():
 
 
 def test_the_structs_have_the_headers_layout(tmp_path):
-    (tmp_path / "probe.c").write_text(PROBE)
-    exe = tmp_path / "probe"
-    r = subprocess.run(["gcc", "-std=c11", "-O1", "-Wall", "-Wextra", "-Werror", f"-I{ROOT}/include", str(tmp_path / "probe.c"), "-o", str(exe)],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    out = subprocess.run([str(exe)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    probe = {ln.split()[0]: tuple(int(v) for v in ln.split()[1:]) for ln in out.splitlines()}
-    assert probe["vx_light_info"] == (16,) == (hip.LIGHT_INFO_DTYPE.itemsize,)
-    assert probe["vx_light_shape"] == (32,) == (C.sizeof(hip.LightShape),)
+    said = probe(tmp_path, {"vx_light_shape": ["size", "flags", "props", "props_count"], "vx_light_info": ["lit", "sources", "open_columns", "faces"]}, CONSTANTS)
+    assert said["vx_light_info"] == (16,) == (hip.LIGHT_INFO_DTYPE.itemsize,)
+    assert said["vx_light_shape"] == (32,) == (C.sizeof(hip.LightShape),)
     for name, value in CONSTANTS.items():
-        assert probe[name] == (value,) == (getattr(hip, name),), name
+        assert said[name] == (value,) == (getattr(hip, name),), name
     assert [n for n, _ in hip.LightShape._fields_] == ["size", "flags", "props", "props_count"]
     for name, _ in hip.LightShape._fields_:
         field = getattr(hip.LightShape, name)
-        assert probe[f"vx_light_shape.{name}"] == (field.offset, field.size), name
+        assert said[f"vx_light_shape.{name}"] == (field.offset, field.size), name
     assert list(hip.LIGHT_INFO_DTYPE.names) == ["lit", "sources", "open_columns", "faces"]
     for k, f in enumerate(hip.LIGHT_INFO_DTYPE.names):
         dt, offset = hip.LIGHT_INFO_DTYPE.fields[f][:2]
-        assert probe[f"vx_light_info.{f}"] == (offset, dt.itemsize) == (4 * k, 4) and dt.str == "<u4", f
+        assert said[f"vx_light_info.{f}"] == (offset, dt.itemsize) == (4 * k, 4) and dt.str == "<u4", f
     s, table = hip.light_shape((33, 9, 17), [0, 15, 0x14], flags=2)
     assert (list(s.size), s.flags, s.props, s.props_count) == ([33, 9, 17], 2, table.ctypes.data, 3) and table.tolist() == [0, 15, 0x14]
     s, table = hip.light_shape((1, 1, 1), [])
@@ -74,19 +46,14 @@ def test_the_structs_have_the_headers_layout(tmp_path):
 
 def test_the_rust_declarations_agree():
     """What tests/test_rust_shim.py's parser cannot see of this call: the constants (the header writes them with a `u` suffix)."""
-    text = (ROOT / "integration" / "rust" / "voxel_hip_sys.rs").read_text()
+    rust = Rust()
     for name, value in CONSTANTS.items():
-        m = re.search(rf"pub const {name}\s*:\s*(u8|u32)\s*=\s*([^;]+);", text)
-        assert m, name
-        said = m.group(2).strip()
-        assert (said == "u32::MAX" and value == 0xFFFFFFFF) or int(said.replace("_", ""), 0) == value, name
-    body = re.search(r"pub struct vx_light_info\s*\{(.*?)\}", text, flags=re.S).group(1)
-    assert re.findall(r"pub\s+(\w+)\s*:\s*([^,\n]+),", body) == [("lit", "u32"), ("sources", "u32"), ("open_columns", "u32"), ("faces", "u32")]
-    body = re.search(r"pub struct vx_light_shape\s*\{(.*?)\}", text, flags=re.S).group(1)
-    assert re.findall(r"pub\s+(\w+)\s*:\s*([^,\n]+),", body) == [("size", "[u32; 3]"), ("flags", "u32"), ("props", "*const u8"), ("props_count", "u32")]
-    assert "size_of::<vx_light_info>() == 16" in text and "size_of::<vx_light_shape>() == 32" in text
-    decl = re.search(r"pub fn vx_light_boxes\((.*?)\)\s*->\s*c_int;", text, flags=re.S).group(1)
-    assert [a.split(":")[0].strip() for a in decl.split(",")] == ["ctx", "lo", "lo_stride", "count", "shape", "memory", "fields", "field_stride", "info"]
+        kind, got = rust.const_int(name)
+        assert kind in ("u8", "u32") and got == value, name
+    assert rust.struct("vx_light_info") == [("lit", "u32"), ("sources", "u32"), ("open_columns", "u32"), ("faces", "u32")]
+    assert rust.struct("vx_light_shape") == [("size", "[u32; 3]"), ("flags", "u32"), ("props", "*const u8"), ("props_count", "u32")]
+    assert rust.asserts_size("vx_light_info", 16) and rust.asserts_size("vx_light_shape", 32)
+    assert rust.args("vx_light_boxes") == ["ctx", "lo", "lo_stride", "count", "shape", "memory", "fields", "field_stride", "info"]
 
 
 def test_check_light_messages_through_the_harness():
@@ -112,22 +79,21 @@ def test_argument_checks_need_no_device():
     L = hip.lib()
     fields = np.full(2 * 4096 + 32, 0x5a, dtype=np.uint8)
     info = np.full(3 * 16, 0x5a, dtype=np.uint8)
-    sentinel = fields.tobytes() + info.tobytes()
     v = np.arange(64, dtype=np.int32)
     base = v.ctypes.data
     u3 = C.c_uint32 * 3
     good = np.array([0, 15, 4, 0x10, 0x19], dtype=np.uint8)
     assert base % 4 == 0
 
-    def refused(word, count=2, memory=hip.VX_MEM_HOST, lo=base, lo_stride=12, f=fields.ctypes.data, field_stride=0, i=info.ctypes.data, shape=True, table=good, **shape_fields):
+    def call(count=2, memory=hip.VX_MEM_HOST, lo=base, lo_stride=12, f=fields.ctypes.data, field_stride=0, i=info.ctypes.data, shape=True, table=good, **shape_fields):
         s, keep = hip.light_shape((16, 16, 16), table)
         for k, val in shape_fields.items():
             setattr(s, k, val)
         rc = L.vx_light_boxes(None, lo, lo_stride, count, C.byref(s) if shape else None, memory, f, field_stride, i)
-        assert rc == 1 and word in L.vx_last_error(), (word, rc, L.vx_last_error())
-        assert fields.tobytes() + info.tobytes() == sentinel
         del keep
+        return rc
 
+    refused = refusing(L, call, (fields, info))
     refused(b"null context")
     refused(b"VX_MEM", memory=5)
     refused(b"VX_MEM", memory=-1)

@@ -3,30 +3,17 @@ include/voxel_hip.h with gcc, the way the C-ABI client is compiled) and the Pyth
 entry point's argument checks, which come before any HIP call, name the field they refuse."""
 import ctypes as C
 import re
-import subprocess
-from pathlib import Path
 
 import numpy as np
 
+from abi_checks import Rust, probe, refusing
 from helpers import vra  # noqa: F401
 from voxel_rs_amd import hip
 
-ROOT = Path(__file__).resolve().parent.parent
 _vp = C.c_void_p
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "voxel_hip.h"
-#define F(S, M) printf(#S "." #M " %zu %zu\n", offsetof(S, M), sizeof(((S*)0)->M))
-int main(void) {
-    printf("vx_block_at %zu\nVX_LIST_FACES %lu\nVX_LIST_EXPOSED %lu\n", sizeof(vx_block_at), (unsigned long)VX_LIST_FACES, (unsigned long)VX_LIST_EXPOSED);
-    F(vx_block_at, where);
-    F(vx_block_at, value);
-    printf("index %lu\nfaces %lu\nabove %lu\n", (unsigned long)VX_AT_INDEX(0xEAFEDCBAu), (unsigned long)VX_AT_FACES(0xEAFEDCBAu), (unsigned long)VX_AT_FACES(0xC0000000u));
-    return 0;
-}
-"""
+# VX_AT_INDEX and VX_AT_FACES on words of the test's own
+MACROS = r'''    printf("index %lu\nfaces %lu\nabove %lu\n", (unsigned long)VX_AT_INDEX(0xEAFEDCBAu), (unsigned long)VX_AT_FACES(0xEAFEDCBAu), (unsigned long)VX_AT_FACES(0xC0000000u));'''
 
 
 def test_the_library_exports_it():
@@ -37,21 +24,15 @@ def test_the_library_exports_it():
 
 
 def test_the_record_and_the_macros_have_the_headers_layout(tmp_path):
-    (tmp_path / "probe.c").write_text(PROBE)
-    exe = tmp_path / "probe"
-    r = subprocess.run(["gcc", "-std=c11", "-O1", "-Wall", "-Wextra", "-Werror", f"-I{ROOT}/include", str(tmp_path / "probe.c"), "-o", str(exe)],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    out = subprocess.run([str(exe)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    probe = {ln.split()[0]: tuple(int(v) for v in ln.split()[1:]) for ln in out.splitlines()}
-    assert probe["vx_block_at"] == (8,) == (hip.BLOCK_AT_DTYPE.itemsize,)
-    assert probe["VX_LIST_FACES"] == (1,) == (hip.VX_LIST_FACES,) and probe["VX_LIST_EXPOSED"] == (2,) == (hip.VX_LIST_EXPOSED,)
+    said = probe(tmp_path, {"vx_block_at": ["where", "value"]}, ["VX_LIST_FACES", "VX_LIST_EXPOSED"], more=MACROS)
+    assert said["vx_block_at"] == (8,) == (hip.BLOCK_AT_DTYPE.itemsize,)
+    assert said["VX_LIST_FACES"] == (1,) == (hip.VX_LIST_FACES,) and said["VX_LIST_EXPOSED"] == (2,) == (hip.VX_LIST_EXPOSED,)
     assert list(hip.BLOCK_AT_DTYPE.names) == ["where", "value"]
     for f, at in (("where", 0), ("value", 4)):
         dt, offset = hip.BLOCK_AT_DTYPE.fields[f][:2]
-        assert probe[f"vx_block_at.{f}"] == (offset, dt.itemsize) == (at, 4) and dt.str == "<u4", f
+        assert said[f"vx_block_at.{f}"] == (offset, dt.itemsize) == (at, 4) and dt.str == "<u4", f
     # VX_AT_INDEX: the low 24 bits; VX_AT_FACES: the six above them, and nothing of bits 30..31
-    assert probe["index"] == (0xFEDCBA,) and probe["faces"] == (0x2A,) and probe["above"] == (0,)
+    assert said["index"] == (0xFEDCBA,) and said["faces"] == (0x2A,) and said["above"] == (0,)
     assert hip.split_where(0xEAFEDCBA) == (0xFEDCBA, 0x2A) and hip.split_where(0xC0000000) == (0, 0)
     index, faces = hip.split_where(np.array([0xEAFEDCBA, 0x3F000001], dtype=np.uint32))
     assert index.tolist() == [0xFEDCBA, 1] and faces.tolist() == [0x2A, 0x3F]
@@ -60,15 +41,13 @@ def test_the_record_and_the_macros_have_the_headers_layout(tmp_path):
 def test_the_rust_declarations_agree():
     """What tests/test_rust_shim.py's parser cannot see of this call: the flag constants (the header writes them with a `u` suffix) and the
     helpers that stand for the two macros."""
-    text = (ROOT / "integration" / "rust" / "voxel_hip_sys.rs").read_text()
-    consts = {k: int(v, 0) for k, v in re.findall(r"pub const (VX_LIST_\w+)\s*:\s*u32\s*=\s*(\w+)\s*;", text)}
+    rust = Rust()
+    consts = {k: int(v, 0) for k, v in re.findall(r"pub const (VX_LIST_\w+)\s*:\s*u32\s*=\s*(\w+)\s*;", rust.text)}
     assert consts == {"VX_LIST_FACES": hip.VX_LIST_FACES, "VX_LIST_EXPOSED": hip.VX_LIST_EXPOSED}
-    body = re.search(r"pub struct vx_block_at\s*\{(.*?)\}", text, flags=re.S).group(1)
-    assert re.findall(r"pub\s+(?:r#)?(\w+)\s*:\s*(\w+)", body) == [("where", "u32"), ("value", "u32")]
-    assert "size_of::<vx_block_at>() == 8" in text
-    assert re.search(r"fn vx_at_index\(at: u32\) -> u32 \{ at & 0xFF_FFFF \}", text) and re.search(r"fn vx_at_faces\(at: u32\) -> u32 \{ \(at >> 24\) & 0x3F \}", text)
-    decl = re.search(r"pub fn vx_list_region\((.*?)\)\s*->\s*c_int;", text, flags=re.S).group(1)
-    assert [a.split(":")[0].strip() for a in decl.split(",")] == ["ctx", "lo", "size", "flags", "memory", "out", "capacity", "total"]
+    assert rust.struct("vx_block_at") == [("where", "u32"), ("value", "u32")]
+    assert rust.asserts_size("vx_block_at", 8)
+    assert re.search(r"fn vx_at_index\(at: u32\) -> u32 \{ at & 0xFF_FFFF \}", rust.text) and re.search(r"fn vx_at_faces\(at: u32\) -> u32 \{ \(at >> 24\) & 0x3F \}", rust.text)
+    assert rust.args("vx_list_region") == ["ctx", "lo", "size", "flags", "memory", "out", "capacity", "total"]
 
 
 def test_argument_checks_need_no_device():
@@ -77,14 +56,13 @@ def test_argument_checks_need_no_device():
     L = hip.lib()
     out = np.full(64 + 8, 0x5a, dtype=np.uint8)
     total = np.full(8, 0x5a, dtype=np.uint8)
-    sentinel = out.tobytes(), total.tobytes()
     i3, u3 = C.c_int32 * 3, C.c_uint32 * 3
 
-    def refused(word, lo=(-3, 0, 5), size=(4, 2, 2), flags=0, memory=hip.VX_MEM_HOST, o=out.ctypes.data, capacity=8, t=total.ctypes.data):
-        rc = L.vx_list_region(None, C.byref(i3(*lo)) if lo is not None else None, C.byref(u3(*size)) if size is not None else None, flags, memory, _vp(o),
+    def call(lo=(-3, 0, 5), size=(4, 2, 2), flags=0, memory=hip.VX_MEM_HOST, o=out.ctypes.data, capacity=8, t=total.ctypes.data):
+        return L.vx_list_region(None, C.byref(i3(*lo)) if lo is not None else None, C.byref(u3(*size)) if size is not None else None, flags, memory, _vp(o),
                               capacity, _vp(t))
-        assert rc == 1 and word in L.vx_last_error(), (word, rc, L.vx_last_error())
-        assert (out.tobytes(), total.tobytes()) == sentinel
+
+    refused = refusing(L, call, (out, total))
 
     refused(b"null context")
     refused(b"null lo", lo=None)

@@ -2,40 +2,15 @@
 with gcc, the way the C-ABI client is compiled) and the Python binding and the Rust declarations agree with them, and the entry point's
 argument checks, which come before any HIP call, name the field they refuse."""
 import ctypes as C
-import re
-import subprocess
-from pathlib import Path
 
 import numpy as np
 
+from abi_checks import Rust, probe, refusing
 from helpers import vra  # noqa: F401
 from voxel_rs_amd import hip
 
-ROOT = Path(__file__).resolve().parent.parent
 _vp = C.c_void_p
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "voxel_hip.h"
-#define F(S, M) printf(#S "." #M " %zu %zu\n", offsetof(S, M), sizeof(((S*)0)->M))
-int main(void) {
-    printf("vx_move_shape %zu\nvx_move_hit %zu\nVX_MOVE_INVALID %lu\nVX_MOVE_ORDER_YXZ %lu\n", sizeof(vx_move_shape), sizeof(vx_move_hit),
-           (unsigned long)VX_MOVE_INVALID, (unsigned long)VX_MOVE_ORDER_YXZ);
-    printf("VX_MOVE_MAX_TRAVEL %d\n", (int)VX_MOVE_MAX_TRAVEL);
-    F(vx_move_shape, scale);
-    F(vx_move_shape, skin);
-    F(vx_move_shape, order);
-    F(vx_move_shape, flags);
-    F(vx_move_hit, origin);
-    F(vx_move_hit, moved);
-    F(vx_move_hit, contacts);
-    F(vx_move_hit, value);
-    F(vx_move_hit, _pad);
-    F(vx_entity, velocity);
-    return 0;
-}
-"""
 
 
 def test_the_library_exports_it():
@@ -46,31 +21,26 @@ def test_the_library_exports_it():
 
 
 def test_the_structs_have_the_headers_layout(tmp_path):
-    (tmp_path / "probe.c").write_text(PROBE)
-    exe = tmp_path / "probe"
-    r = subprocess.run(["gcc", "-std=c11", "-O1", "-Wall", "-Wextra", "-Werror", f"-I{ROOT}/include", str(tmp_path / "probe.c"), "-o", str(exe)],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    out = subprocess.run([str(exe)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    probe = {ln.split()[0]: tuple(int(v) for v in ln.split()[1:]) for ln in out.splitlines()}
-    assert probe["vx_move_hit"] == (48,) == (hip.MOVE_HIT_DTYPE.itemsize,)
-    assert probe["vx_move_shape"] == (16,) == (C.sizeof(hip.MoveShape),)
-    assert probe["VX_MOVE_INVALID"] == (0xFFFFFFFF,) == (hip.VX_MOVE_INVALID,)
-    assert probe["VX_MOVE_ORDER_YXZ"] == (hip.VX_MOVE_ORDER_YXZ,) == (1 | 0 << 2 | 2 << 4,)
-    assert probe["VX_MOVE_MAX_TRAVEL"] == (64,) == (hip.VX_MOVE_MAX_TRAVEL,)
+    said = probe(tmp_path, {"vx_move_shape": ["scale", "skin", "order", "flags"], "vx_move_hit": ["origin", "moved", "contacts", "value", "_pad"], "vx_entity": ["velocity"]},
+                 ["VX_MOVE_INVALID", "VX_MOVE_ORDER_YXZ", "VX_MOVE_MAX_TRAVEL"])
+    assert said["vx_move_hit"] == (48,) == (hip.MOVE_HIT_DTYPE.itemsize,)
+    assert said["vx_move_shape"] == (16,) == (C.sizeof(hip.MoveShape),)
+    assert said["VX_MOVE_INVALID"] == (0xFFFFFFFF,) == (hip.VX_MOVE_INVALID,)
+    assert said["VX_MOVE_ORDER_YXZ"] == (hip.VX_MOVE_ORDER_YXZ,) == (1 | 0 << 2 | 2 << 4,)
+    assert said["VX_MOVE_MAX_TRAVEL"] == (64,) == (hip.VX_MOVE_MAX_TRAVEL,)
     assert (hip.VX_MOVE_ORDER_XYZ, hip.VX_MOVE_ORDER_ZYX) == (0 | 1 << 2 | 2 << 4, 2 | 1 << 2 | 0 << 4)
     assert [n for n, _ in hip.MoveShape._fields_] == ["scale", "skin", "order", "flags"]
     for name, _ in hip.MoveShape._fields_:
         field = getattr(hip.MoveShape, name)
-        assert probe[f"vx_move_shape.{name}"] == (field.offset, field.size), name
+        assert said[f"vx_move_shape.{name}"] == (field.offset, field.size), name
     assert list(hip.MOVE_HIT_DTYPE.names) == ["origin", "moved", "contacts", "value", "_pad"]
     for f, at, size, kind in (("origin", 0, 12, "<f4"), ("moved", 12, 12, "<f4"), ("contacts", 24, 4, "<u4"), ("value", 28, 12, "<u4"), ("_pad", 40, 8, "<u4")):
         dt, offset = hip.MOVE_HIT_DTYPE.fields[f][:2]
-        assert probe[f"vx_move_hit.{f}"] == (offset, dt.itemsize) == (at, size) and dt.base.str == kind, f
+        assert said[f"vx_move_hit.{f}"] == (offset, dt.itemsize) == (at, size) and dt.base.str == kind, f
     # a vx_entity's velocity is read in place: entity_velocities' view lies where the header's field does
     e = np.zeros(3, dtype=hip.ENTITY_DTYPE)
     v = hip.entity_velocities(e)
-    assert v.ctypes.data - e.ctypes.data == probe["vx_entity.velocity"][0] and v.strides == (64, 4) and v.shape == (3, 3)
+    assert v.ctypes.data - e.ctypes.data == said["vx_entity.velocity"][0] and v.strides == (64, 4) and v.shape == (3, 3)
     s = hip.MOVE_SHAPE()
     assert (s.scale, s.skin, s.order, s.flags) == (1.0, 2.0 ** -10, hip.VX_MOVE_ORDER_YXZ, 0)
 
@@ -78,18 +48,14 @@ def test_the_structs_have_the_headers_layout(tmp_path):
 def test_the_rust_declarations_agree():
     """What tests/test_rust_shim.py's parser cannot see of this call: the constants (the header writes them in hexadecimal with a `u` suffix,
     and as a float)."""
-    text = (ROOT / "integration" / "rust" / "voxel_hip_sys.rs").read_text()
-    assert re.search(r"pub const VX_MOVE_INVALID\s*:\s*u32\s*=\s*u32::MAX\s*;", text)
-    assert re.search(r"pub const VX_MOVE_MAX_TRAVEL\s*:\s*f32\s*=\s*64\.0\s*;", text)
-    assert re.search(r"pub const VX_MOVE_ORDER_YXZ\s*:\s*u32\s*=\s*0x21\s*;", text)
-    body = re.search(r"pub struct vx_move_hit\s*\{(.*?)\}", text, flags=re.S).group(1)
-    assert re.findall(r"pub\s+(\w+)\s*:\s*([^,\n]+),", body) == [("origin", "[f32; 3]"), ("moved", "[f32; 3]"), ("contacts", "u32"), ("value", "[u32; 3]"),
-                                                                 ("_pad", "[u32; 2]")]
-    body = re.search(r"pub struct vx_move_shape\s*\{(.*?)\}", text, flags=re.S).group(1)
-    assert re.findall(r"pub\s+(\w+)\s*:\s*([^,\n]+),", body) == [("scale", "f32"), ("skin", "f32"), ("order", "u32"), ("flags", "u32")]
-    assert "size_of::<vx_move_hit>() == 48" in text and "size_of::<vx_move_shape>() == 16" in text
-    decl = re.search(r"pub fn vx_move_boxes\((.*?)\)\s*->\s*c_int;", text, flags=re.S).group(1)
-    assert [a.split(":")[0].strip() for a in decl.split(",")] == ["ctx", "boxes", "motion", "motion_stride", "count", "shape", "memory", "out"]
+    rust = Rust()
+    assert rust.const("VX_MOVE_INVALID") == ("u32", "u32::MAX")
+    assert rust.const("VX_MOVE_MAX_TRAVEL") == ("f32", "64.0")
+    assert rust.const("VX_MOVE_ORDER_YXZ") == ("u32", "0x21")
+    assert rust.struct("vx_move_hit") == [("origin", "[f32; 3]"), ("moved", "[f32; 3]"), ("contacts", "u32"), ("value", "[u32; 3]"), ("_pad", "[u32; 2]")]
+    assert rust.struct("vx_move_shape") == [("scale", "f32"), ("skin", "f32"), ("order", "u32"), ("flags", "u32")]
+    assert rust.asserts_size("vx_move_hit", 48) and rust.asserts_size("vx_move_shape", 16)
+    assert rust.args("vx_move_boxes") == ["ctx", "boxes", "motion", "motion_stride", "count", "shape", "memory", "out"]
 
 
 def test_argument_checks_need_no_device():
@@ -97,19 +63,18 @@ def test_argument_checks_need_no_device():
     sentinel-filled records stay as they are."""
     L = hip.lib()
     out = np.full(48 * 4 + 16, 0x5a, dtype=np.uint8)
-    sentinel = out.tobytes()
     v = np.arange(64, dtype=np.float32)
     base = v.ctypes.data
     assert base % 4 == 0
 
-    def refused(word, count=2, memory=hip.VX_MEM_HOST, o=out.ctypes.data, boxes=True, motion=base + 144, motion_stride=12, shape=True, **fields):
+    def call(count=2, memory=hip.VX_MEM_HOST, o=out.ctypes.data, boxes=True, motion=base + 144, motion_stride=12, shape=True, **fields):
         b = hip.BoxBatch(base, base + 12 * 4, base + 24 * 4, 12, 12, 12, 0)
         s = hip.MOVE_SHAPE()
         for k, val in fields.items():
             setattr(s if hasattr(s, k) else b, k, val)
-        rc = L.vx_move_boxes(None, C.byref(b) if boxes else None, _vp(motion), motion_stride, count, C.byref(s) if shape else None, memory, _vp(o))
-        assert rc == 1 and word in L.vx_last_error(), (word, rc, L.vx_last_error())
-        assert out.tobytes() == sentinel
+        return L.vx_move_boxes(None, C.byref(b) if boxes else None, _vp(motion), motion_stride, count, C.byref(s) if shape else None, memory, _vp(o))
+
+    refused = refusing(L, call, (out,))
 
     refused(b"null context")
     refused(b"null shape", shape=False)

@@ -2,32 +2,17 @@
 compiled from include/voxel_hip.h with gcc, the way the C-ABI client is compiled), and the entry point's argument checks, which come
 before any HIP call, name the field they refuse."""
 import ctypes as C
-import subprocess
-from pathlib import Path
 
 import numpy as np
 
+from abi_checks import probe, refusing
 from helpers import vra  # noqa: F401
 from voxel_rs_amd import hip
 
-ROOT = Path(__file__).resolve().parent.parent
 _vp = C.c_void_p
 
 BATCH_FIELDS = ["origin", "dir", "max_dst", "origin_stride", "dir_stride", "max_dst_stride", "max_dst_all", "flags"]
 HIT_FIELDS = ["dst", "value", "face_id", "inside_voxel", "pos", "_pad"]
-
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "voxel_hip.h"
-#define F(S, M) printf(#S "." #M " %zu %zu\n", offsetof(S, M), sizeof(((S*)0)->M))
-int main(void) {
-    printf("vx_ray_batch %zu\nvx_ray_hit %zu\nVX_RAYS_TRANSLUCENT %d\n", sizeof(vx_ray_batch), sizeof(vx_ray_hit), VX_RAYS_TRANSLUCENT);
-    BATCH
-    HITS
-    return 0;
-}
-"""
 
 
 def test_the_library_exports_it():
@@ -37,23 +22,16 @@ def test_the_library_exports_it():
 
 
 def test_records_have_the_headers_layout(tmp_path):
-    src = PROBE.replace("BATCH", " ".join(f"F(vx_ray_batch, {f});" for f in BATCH_FIELDS)).replace("HITS", " ".join(f"F(vx_ray_hit, {f});" for f in HIT_FIELDS))
-    (tmp_path / "probe.c").write_text(src)
-    exe = tmp_path / "probe"
-    r = subprocess.run(["gcc", "-std=c11", "-O1", "-Wall", "-Wextra", "-Werror", f"-I{ROOT}/include", str(tmp_path / "probe.c"), "-o", str(exe)],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    out = subprocess.run([str(exe)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    probe = {ln.split()[0]: tuple(int(v) for v in ln.split()[1:]) for ln in out.splitlines()}
-    assert probe["vx_ray_batch"] == (48,) and probe["vx_ray_hit"] == (32,) and probe["VX_RAYS_TRANSLUCENT"] == (hip.VX_RAYS_TRANSLUCENT,)
+    said = probe(tmp_path, {"vx_ray_batch": BATCH_FIELDS, "vx_ray_hit": HIT_FIELDS}, ["VX_RAYS_TRANSLUCENT"])
+    assert said["vx_ray_batch"] == (48,) and said["vx_ray_hit"] == (32,) and said["VX_RAYS_TRANSLUCENT"] == (hip.VX_RAYS_TRANSLUCENT,)
     assert C.sizeof(hip.RayBatch) == 48 and [n for n, _ in hip.RayBatch._fields_] == BATCH_FIELDS
     for f in BATCH_FIELDS:
         d = getattr(hip.RayBatch, f)
-        assert probe[f"vx_ray_batch.{f}"] == (d.offset, d.size), f
+        assert said[f"vx_ray_batch.{f}"] == (d.offset, d.size), f
     assert hip.RAY_HIT_DTYPE.itemsize == 32 and list(hip.RAY_HIT_DTYPE.names) == HIT_FIELDS
     for f in HIT_FIELDS:
         dt, offset = hip.RAY_HIT_DTYPE.fields[f][:2]
-        assert probe[f"vx_ray_hit.{f}"] == (offset, dt.itemsize), f
+        assert said[f"vx_ray_hit.{f}"] == (offset, dt.itemsize), f
     assert [hip.RAY_HIT_DTYPE.fields[f][1] for f in HIT_FIELDS] == [0, 4, 8, 12, 16, 28]
     kinds = {f: hip.RAY_HIT_DTYPE.fields[f][0].base.str for f in HIT_FIELDS}
     assert kinds == {"dst": "<f4", "value": "<u4", "face_id": "<i4", "inside_voxel": "<u4", "pos": "<f4", "_pad": "<u4"}
@@ -65,15 +43,14 @@ def test_argument_checks_need_no_device():
     L = hip.lib()
     o, d, m = np.zeros((4, 3), dtype=np.float32), np.ones((4, 3), dtype=np.float32), np.full(4, 9.0, dtype=np.float32)
     hits = np.full(4 * 32, 0x5a, dtype=np.uint8)
-    sentinel = hits.tobytes()
 
-    def refused(word, memory=hip.VX_MEM_HOST, **kw):
+    def call(memory=hip.VX_MEM_HOST, **kw):
         b = hip.RayBatch(o.ctypes.data, d.ctypes.data, m.ctypes.data, 12, 12, 4, -1.0, 0)
         for k, v in kw.items():
             setattr(b, k, v)
-        assert L.vx_raycast_batch(None, C.byref(b), 4, memory, hits.ctypes.data_as(_vp)) == 1
-        assert word in L.vx_last_error(), (word, L.vx_last_error())
-        assert hits.tobytes() == sentinel
+        return L.vx_raycast_batch(None, C.byref(b), 4, memory, hits.ctypes.data_as(_vp))
+
+    refused = refusing(L, call, (hits,))
 
     refused(b"null context")
     for stride in (0, 4, 8, 13, 14):

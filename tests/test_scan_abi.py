@@ -2,35 +2,15 @@
 constant probe compiled from include/voxel_hip.h with gcc, the way the C-ABI client is compiled), and the entry points' argument checks,
 which come before any HIP call, name the field they refuse."""
 import ctypes as C
-import subprocess
-from pathlib import Path
 
 import numpy as np
 
+from abi_checks import probe, refusing
 from helpers import vra  # noqa: F401
 from voxel_rs_amd import hip
 
-ROOT = Path(__file__).resolve().parent.parent
 _vp = C.c_void_p
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "voxel_hip.h"
-#define F(S, M) printf(#S "." #M " %zu %zu\n", offsetof(S, M), sizeof(((S*)0)->M))
-#define K(N) printf(#N " %lld\n", (long long)(N))
-int main(void) {
-    printf("vx_scan_hit %zu\n", sizeof(vx_scan_hit));
-    F(vx_scan_hit, coord);
-    F(vx_scan_hit, value);
-    F(vx_scan_hit, cell_log2);
-    F(vx_scan_hit, _pad);
-    K(VX_DIR_NEG_X); K(VX_DIR_POS_X); K(VX_DIR_NEG_Y); K(VX_DIR_POS_Y); K(VX_DIR_NEG_Z); K(VX_DIR_POS_Z);
-    K(VX_SCAN_NONE); K(VX_SCAN_TO_EDGE); K(VX_CELL_OUTSIDE);
-    printf("none_is_int32 %d\n", (int)(sizeof(VX_SCAN_NONE) == 4 && VX_SCAN_NONE < 0));
-    return 0;
-}
-"""
 
 
 def test_the_library_exports_them():
@@ -41,23 +21,19 @@ def test_the_library_exports_them():
 
 
 def test_the_record_has_the_headers_layout(tmp_path):
-    (tmp_path / "probe.c").write_text(PROBE)
-    exe = tmp_path / "probe"
-    r = subprocess.run(["gcc", "-std=c11", "-O1", "-Wall", "-Wextra", "-Werror", f"-I{ROOT}/include", str(tmp_path / "probe.c"), "-o", str(exe)],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    out = subprocess.run([str(exe)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    probe = {ln.split()[0]: tuple(int(v) for v in ln.split()[1:]) for ln in out.splitlines()}
-    assert probe["vx_scan_hit"] == (16,) == (hip.SCAN_HIT_DTYPE.itemsize,)
+    constants = ["VX_DIR_NEG_X", "VX_DIR_POS_X", "VX_DIR_NEG_Y", "VX_DIR_POS_Y", "VX_DIR_NEG_Z", "VX_DIR_POS_Z", "VX_SCAN_NONE", "VX_SCAN_TO_EDGE", "VX_CELL_OUTSIDE"]
+    said = probe(tmp_path, {"vx_scan_hit": ["coord", "value", "cell_log2", "_pad"]}, constants,
+                 more=r'    printf("none_is_int32 %d\n", (int)(sizeof(VX_SCAN_NONE) == 4 && VX_SCAN_NONE < 0));')
+    assert said["vx_scan_hit"] == (16,) == (hip.SCAN_HIT_DTYPE.itemsize,)
     assert list(hip.SCAN_HIT_DTYPE.names) == ["coord", "value", "cell_log2", "_pad"]
     for f, at, kind in (("coord", 0, "<i4"), ("value", 4, "<u4"), ("cell_log2", 8, "<u4"), ("_pad", 12, "<u4")):
         dt, offset = hip.SCAN_HIT_DTYPE.fields[f][:2]
-        assert probe[f"vx_scan_hit.{f}"] == (offset, dt.itemsize) == (at, 4) and dt.str == kind, f
+        assert said[f"vx_scan_hit.{f}"] == (offset, dt.itemsize) == (at, 4) and dt.str == kind, f
     for k, name in enumerate(("VX_DIR_NEG_X", "VX_DIR_POS_X", "VX_DIR_NEG_Y", "VX_DIR_POS_Y", "VX_DIR_NEG_Z", "VX_DIR_POS_Z")):
-        assert probe[name] == (getattr(hip, name),) == (k,)
-    assert probe["VX_SCAN_NONE"] == (hip.VX_SCAN_NONE,) == (-(1 << 31),) and probe["none_is_int32"] == (1,)
-    assert probe["VX_SCAN_TO_EDGE"] == (hip.VX_SCAN_TO_EDGE,) == (0xFFFFFFFF,)
-    assert probe["VX_CELL_OUTSIDE"] == (hip.VX_CELL_OUTSIDE,)
+        assert said[name] == (getattr(hip, name),) == (k,)
+    assert said["VX_SCAN_NONE"] == (hip.VX_SCAN_NONE,) == (-(1 << 31),) and said["none_is_int32"] == (1,)
+    assert said["VX_SCAN_TO_EDGE"] == (hip.VX_SCAN_TO_EDGE,) == (0xFFFFFFFF,)
+    assert said["VX_CELL_OUTSIDE"] == (hip.VX_CELL_OUTSIDE,)
     assert np.array([hip.VX_SCAN_NONE], dtype=hip.SCAN_HIT_DTYPE["coord"])[0] == hip.VX_SCAN_NONE
 
 
@@ -67,13 +43,12 @@ def test_scan_points_argument_checks_need_no_device():
     L = hip.lib()
     pos = np.zeros((4, 4), dtype=np.float32)
     out = np.full(4 * 16 + 16, 0x5a, dtype=np.uint8)
-    sentinel = out.tobytes()
     base = out.ctypes.data + (-out.ctypes.data) % 16
 
-    def refused(word, p=pos.ctypes.data, stride=12, count=4, direction=hip.VX_DIR_NEG_Y, reach=hip.VX_SCAN_TO_EDGE, memory=hip.VX_MEM_HOST, o=base):
-        assert L.vx_scan_points(None, _vp(p), stride, count, direction, reach, memory, _vp(o)) == 1
-        assert word in L.vx_last_error(), (word, L.vx_last_error())
-        assert out.tobytes() == sentinel
+    def call(p=pos.ctypes.data, stride=12, count=4, direction=hip.VX_DIR_NEG_Y, reach=hip.VX_SCAN_TO_EDGE, memory=hip.VX_MEM_HOST, o=base):
+        return L.vx_scan_points(None, _vp(p), stride, count, direction, reach, memory, _vp(o))
+
+    refused = refusing(L, call, (out,))
 
     refused(b"null context")
     for stride in (0, 4, 8, 13, 14, 18, 2):
@@ -108,14 +83,13 @@ def test_scan_points_argument_checks_need_no_device():
 def test_scan_columns_argument_checks_need_no_device():
     L = hip.lib()
     out = np.full(8 * 16 + 16, 0x5a, dtype=np.uint8)
-    sentinel = out.tobytes()
     base = out.ctypes.data + (-out.ctypes.data) % 16
     i3, u3 = C.c_int32 * 3, C.c_uint32 * 3
 
-    def refused(word, lo=(-3, 0, 5), size=(4, 2, 2), direction=hip.VX_DIR_NEG_Y, memory=hip.VX_MEM_HOST, o=base):
-        rc = L.vx_scan_columns(None, C.byref(i3(*lo)) if lo is not None else None, C.byref(u3(*size)) if size is not None else None, direction, memory, _vp(o))
-        assert rc == 1 and word in L.vx_last_error(), (word, rc, L.vx_last_error())
-        assert out.tobytes() == sentinel
+    def call(lo=(-3, 0, 5), size=(4, 2, 2), direction=hip.VX_DIR_NEG_Y, memory=hip.VX_MEM_HOST, o=base):
+        return L.vx_scan_columns(None, C.byref(i3(*lo)) if lo is not None else None, C.byref(u3(*size)) if size is not None else None, direction, memory, _vp(o))
+
+    refused = refusing(L, call, (out,))
 
     refused(b"null context")
     refused(b"null lo", lo=None)

@@ -1,30 +1,20 @@
 """vx_trace_rays without a GPU: the library exports it, the records it takes and gives have the header's sizes, and the entry point's argument
 checks, which come before any HIP call, name the field they refuse and come in the documented order."""
 import ctypes as C
-import subprocess
-from pathlib import Path
 
 import numpy as np
 
+from abi_checks import probe
 from helpers import vra  # noqa: F401
 from voxel_rs_amd import hip
 
-ROOT = Path(__file__).resolve().parent.parent
 _vp = C.c_void_p
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "voxel_hip.h"
-int main(void) {
-    printf("vx_hit %zu\nvx_ray_batch %zu\nvx_uniforms %zu\n", sizeof(vx_hit), sizeof(vx_ray_batch), sizeof(vx_uniforms));
-    printf("shadow_t %zu\nsteps %zu\nuv %zu\npos %zu\n", offsetof(vx_hit, shadow_t), offsetof(vx_hit, steps), offsetof(vx_hit, uv), offsetof(vx_hit, pos));
-    printf("formats %d %d\nmemory %d %d\n", VX_FORMAT_RGBA32F, VX_FORMAT_RGBA8, VX_MEM_HOST, VX_MEM_DEVICE);
-    return 0;
-}
-typedef int (*trace_rays_fn)(vx_context*, const vx_uniforms*, const vx_ray_batch*, uint32_t, int, void*, int, vx_hit*);
-_Static_assert(__builtin_types_compatible_p(__typeof__(&vx_trace_rays), trace_rays_fn), "the documented signature");
-"""
+# what the probe prints beside the sizes, and what the compiler checks behind it: the declaration has the documented signature
+PRINTS = r"""    printf("shadow_t %zu\nsteps %zu\nuv %zu\npos %zu\n", offsetof(vx_hit, shadow_t), offsetof(vx_hit, steps), offsetof(vx_hit, uv), offsetof(vx_hit, pos));
+    printf("formats %d %d\nmemory %d %d\n", VX_FORMAT_RGBA32F, VX_FORMAT_RGBA8, VX_MEM_HOST, VX_MEM_DEVICE);"""
+SIGNATURE = r"""typedef int (*trace_rays_fn)(vx_context*, const vx_uniforms*, const vx_ray_batch*, uint32_t, int, void*, int, vx_hit*);
+_Static_assert(__builtin_types_compatible_p(__typeof__(&vx_trace_rays), trace_rays_fn), "the documented signature");"""
 
 
 def test_the_library_exports_it():
@@ -35,18 +25,12 @@ def test_the_library_exports_it():
 
 
 def test_record_and_descriptor_sizes(tmp_path):
-    (tmp_path / "probe.c").write_text(PROBE)
-    exe = tmp_path / "probe"
-    r = subprocess.run(["gcc", "-std=gnu11", "-O1", "-Wall", "-Wextra", "-Werror", f"-I{ROOT}/include", str(tmp_path / "probe.c"), "-o", str(exe)],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout  # (the static assertion: the declaration has the documented signature)
-    out = subprocess.run([str(exe)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    probe = {ln.split()[0]: tuple(int(v) for v in ln.split()[1:]) for ln in out.splitlines()}
-    assert probe["vx_hit"] == (48,) == (hip.HIT_DTYPE.itemsize,) and probe["vx_ray_batch"] == (48,) == (C.sizeof(hip.RayBatch),)
-    assert probe["vx_uniforms"] == (C.sizeof(hip.Uniforms),)
+    said = probe(tmp_path, ["vx_hit", "vx_ray_batch", "vx_uniforms"], more=PRINTS, after=SIGNATURE, std="gnu11")
+    assert said["vx_hit"] == (48,) == (hip.HIT_DTYPE.itemsize,) and said["vx_ray_batch"] == (48,) == (C.sizeof(hip.RayBatch),)
+    assert said["vx_uniforms"] == (C.sizeof(hip.Uniforms),)
     for f in ("pos", "uv", "shadow_t", "steps"):
-        assert probe[f] == (hip.HIT_DTYPE.fields[f][1],), f
-    assert probe["formats"] == (hip.VX_FORMAT_RGBA32F, hip.VX_FORMAT_RGBA8) and probe["memory"] == (hip.VX_MEM_HOST, hip.VX_MEM_DEVICE)
+        assert said[f] == (hip.HIT_DTYPE.fields[f][1],), f
+    assert said["formats"] == (hip.VX_FORMAT_RGBA32F, hip.VX_FORMAT_RGBA8) and said["memory"] == (hip.VX_MEM_HOST, hip.VX_MEM_DEVICE)
     # three 16-byte stores a record: {t, value, face_id, flags} {pos, lod} {uv, shadow_t, steps}
     assert [hip.HIT_DTYPE.fields[f][1] for f in hip.HIT_DTYPE.names] == [0, 4, 8, 12, 16, 28, 32, 40, 44]
 

@@ -1,32 +1,22 @@
 """vx_trace_views without a GPU: the library exports it, the records it takes and gives keep the header's sizes, and the entry point's argument
 checks, all of which come before the context is looked at and before any HIP call, name the field they refuse and write nothing."""
 import ctypes as C
-import subprocess
-from pathlib import Path
 
 import numpy as np
 
+from abi_checks import probe
 from helpers import vra  # noqa: F401
 from voxel_rs_amd import hip
 
-ROOT = Path(__file__).resolve().parent.parent
 _vp = C.c_void_p
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "voxel_hip.h"
-int main(void) {
-    printf("vx_hit %zu\nvx_uniforms %zu\n", sizeof(vx_hit), sizeof(vx_uniforms));
-    printf("fovy %zu\naspect %zu\nambient %zu\nlight_dir %zu\ncam_pos %zu\nrender_shadows %zu\nshadow_distance %zu\nhighlight_pos %zu\n", offsetof(vx_uniforms, fovy),
+# what the probe prints beside the sizes, and what the compiler checks behind it: the declaration has the documented signature
+PRINTS = r"""    printf("fovy %zu\naspect %zu\nambient %zu\nlight_dir %zu\ncam_pos %zu\nrender_shadows %zu\nshadow_distance %zu\nhighlight_pos %zu\n", offsetof(vx_uniforms, fovy),
            offsetof(vx_uniforms, aspect), offsetof(vx_uniforms, ambient), offsetof(vx_uniforms, light_dir), offsetof(vx_uniforms, cam_pos),
            offsetof(vx_uniforms, render_shadows), offsetof(vx_uniforms, shadow_distance), offsetof(vx_uniforms, highlight_pos));
-    printf("formats %d %d\nmemory %d %d\n", VX_FORMAT_RGBA32F, VX_FORMAT_RGBA8, VX_MEM_HOST, VX_MEM_DEVICE);
-    return 0;
-}
-typedef int (*trace_views_fn)(vx_context*, const vx_uniforms*, uint32_t, uint32_t, uint32_t, int, void*, int, vx_hit*);
-_Static_assert(__builtin_types_compatible_p(__typeof__(&vx_trace_views), trace_views_fn), "the documented signature");
-"""
+    printf("formats %d %d\nmemory %d %d\n", VX_FORMAT_RGBA32F, VX_FORMAT_RGBA8, VX_MEM_HOST, VX_MEM_DEVICE);"""
+SIGNATURE = r"""typedef int (*trace_views_fn)(vx_context*, const vx_uniforms*, uint32_t, uint32_t, uint32_t, int, void*, int, vx_hit*);
+_Static_assert(__builtin_types_compatible_p(__typeof__(&vx_trace_views), trace_views_fn), "the documented signature");"""
 
 
 def test_the_library_exports_it():
@@ -37,18 +27,12 @@ def test_the_library_exports_it():
 
 
 def test_struct_sizes_are_unchanged(tmp_path):
-    (tmp_path / "probe.c").write_text(PROBE)
-    exe = tmp_path / "probe"
-    r = subprocess.run(["gcc", "-std=gnu11", "-O1", "-Wall", "-Wextra", "-Werror", f"-I{ROOT}/include", str(tmp_path / "probe.c"), "-o", str(exe)],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout  # (the static assertion: the declaration has the documented signature)
-    out = subprocess.run([str(exe)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    probe = {ln.split()[0]: tuple(int(v) for v in ln.split()[1:]) for ln in out.splitlines()}
-    assert probe["vx_hit"] == (48,) == (hip.HIT_DTYPE.itemsize,)
-    assert probe["vx_uniforms"] == (120,) == (C.sizeof(hip.Uniforms),)
+    said = probe(tmp_path, ["vx_hit", "vx_uniforms"], more=PRINTS, after=SIGNATURE, std="gnu11")
+    assert said["vx_hit"] == (48,) == (hip.HIT_DTYPE.itemsize,)
+    assert said["vx_uniforms"] == (120,) == (C.sizeof(hip.Uniforms),)
     for f in ("fovy", "aspect", "ambient", "light_dir", "cam_pos", "render_shadows", "shadow_distance", "highlight_pos"):
-        assert probe[f] == (getattr(hip.Uniforms, f).offset,), f
-    assert probe["formats"] == (hip.VX_FORMAT_RGBA32F, hip.VX_FORMAT_RGBA8) and probe["memory"] == (hip.VX_MEM_HOST, hip.VX_MEM_DEVICE)
+        assert said[f] == (getattr(hip.Uniforms, f).offset,), f
+    assert said["formats"] == (hip.VX_FORMAT_RGBA32F, hip.VX_FORMAT_RGBA8) and said["memory"] == (hip.VX_MEM_HOST, hip.VX_MEM_DEVICE)
 
 
 class Args:

@@ -2,33 +2,19 @@
 gcc, the way the C-ABI client is compiled) and the Python binding and the Rust declarations agree with them, check_walk's messages as the
 host harness prints them, and the entry point's argument checks, which come before any HIP call, name the field they refuse."""
 import ctypes as C
-import re
 import subprocess
-from pathlib import Path
 
 import numpy as np
 
+from abi_checks import ROOT, Rust, probe, refusing
 from helpers import vra  # noqa: F401
 from voxel_rs_amd import hip
 from walk_cases import harness
 
-ROOT = Path(__file__).resolve().parent.parent
 _vp = C.c_void_p
 
 SHAPE_FIELDS = ["size", "seed_at", "max_steps", "pass_value", "height", "climb", "drop", "path_capacity", "flags"]
 INFO_FIELDS = ["reached", "farthest", "faces", "seed_value", "start_ry", "goal_ry", "path_steps", "_pad"]
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "voxel_hip.h"
-#define F(S, M) printf(#S "." #M " %zu %zu\n", offsetof(S, M), sizeof(((S*)0)->M))
-#define K(N) printf(#N " %lu\n", (unsigned long)N)
-int main(void) {
-    printf("vx_walk_shape %zu\nvx_walk_info %zu\n", sizeof(vx_walk_shape), sizeof(vx_walk_info));
-    K(VX_WALK_MAX_STEPS); K(VX_WALK_NO_POSITION); K(VX_WALK_UNREACHED); K(VX_WALK_NO_STAND); K(VX_WALK_STOP_AT_GOAL); K(VX_WALK_NONE);
-""" + "".join(f"    F(vx_walk_shape, {f});\n" for f in SHAPE_FIELDS) + "".join(f"    F(vx_walk_info, {f});\n" for f in INFO_FIELDS) + """    return 0;
-}
-"""
 CONSTANTS = {"VX_WALK_MAX_STEPS": 250, "VX_WALK_NO_POSITION": 0xFD, "VX_WALK_UNREACHED": 0xFE, "VX_WALK_NO_STAND": 0xFF, "VX_WALK_STOP_AT_GOAL": 1, "VX_WALK_NONE": 0xFFFFFFFF}
 
 
@@ -40,45 +26,33 @@ def test_the_library_exports_it():
 
 
 def test_the_structs_have_the_headers_layout(tmp_path):
-    (tmp_path / "probe.c").write_text(PROBE)
-    exe = tmp_path / "probe"
-    r = subprocess.run(["gcc", "-std=c11", "-O1", "-Wall", "-Wextra", "-Werror", f"-I{ROOT}/include", str(tmp_path / "probe.c"), "-o", str(exe)],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    out = subprocess.run([str(exe)], stdout=subprocess.PIPE, text=True, check=True).stdout
-    probe = {ln.split()[0]: tuple(int(v) for v in ln.split()[1:]) for ln in out.splitlines()}
-    assert probe["vx_walk_info"] == (32,) == (hip.WALK_INFO_DTYPE.itemsize,)
-    assert probe["vx_walk_shape"] == (52,) == (C.sizeof(hip.WalkShape),)
+    said = probe(tmp_path, {"vx_walk_shape": SHAPE_FIELDS, "vx_walk_info": INFO_FIELDS}, CONSTANTS)
+    assert said["vx_walk_info"] == (32,) == (hip.WALK_INFO_DTYPE.itemsize,)
+    assert said["vx_walk_shape"] == (52,) == (C.sizeof(hip.WalkShape),)
     for name, value in CONSTANTS.items():
-        assert probe[name] == (value,) == (getattr(hip, name),), name
+        assert said[name] == (value,) == (getattr(hip, name),), name
     assert [n for n, _ in hip.WalkShape._fields_] == SHAPE_FIELDS
     for name, _ in hip.WalkShape._fields_:
         field = getattr(hip.WalkShape, name)
-        assert probe[f"vx_walk_shape.{name}"] == (field.offset, field.size), name
+        assert said[f"vx_walk_shape.{name}"] == (field.offset, field.size), name
     assert list(hip.WALK_INFO_DTYPE.names) == INFO_FIELDS
     for k, f in enumerate(hip.WALK_INFO_DTYPE.names):
         dt, offset = hip.WALK_INFO_DTYPE.fields[f][:2]
-        assert probe[f"vx_walk_info.{f}"] == (offset, dt.itemsize) == (4 * k, 4) and dt.str == "<u4", f
+        assert said[f"vx_walk_info.{f}"] == (offset, dt.itemsize) == (4 * k, 4) and dt.str == "<u4", f
     s = hip.walk_shape((31, 3, 17), max_steps=24, pass_value=9, height=1, climb=0, drop=2, path_capacity=8, flags=1)
     assert (list(s.size), list(s.seed_at), s.max_steps, s.pass_value, s.height, s.climb, s.drop, s.path_capacity, s.flags) == ([31, 3, 17], [15, 1, 8], 24, 9, 1, 0, 2, 8, 1)
 
 
 def test_the_rust_declarations_agree():
     """What tests/test_rust_shim.py's parser cannot see of this call: the constants (the header writes them in hexadecimal with a `u` suffix)."""
-    text = (ROOT / "integration" / "rust" / "voxel_hip_sys.rs").read_text()
+    rust = Rust()
     for name, value in CONSTANTS.items():
         kind = "u8" if name in ("VX_WALK_NO_POSITION", "VX_WALK_UNREACHED", "VX_WALK_NO_STAND") else "u32"
-        m = re.search(rf"pub const {name}\s*:\s*{kind}\s*=\s*([^;]+);", text)
-        assert m, name
-        said = m.group(1).strip()
-        assert (said == "u32::MAX" and value == 0xFFFFFFFF) or int(said.replace("_", ""), 0) == value, name
-    body = re.search(r"pub struct vx_walk_info\s*\{(.*?)\}", text, flags=re.S).group(1)
-    assert re.findall(r"pub\s+(\w+)\s*:\s*([^,\n]+),", body) == [(f, "u32") for f in INFO_FIELDS]
-    body = re.search(r"pub struct vx_walk_shape\s*\{(.*?)\}", text, flags=re.S).group(1)
-    assert re.findall(r"pub\s+(\w+)\s*:\s*([^,\n]+),", body) == [("size", "[u32; 3]"), ("seed_at", "[u32; 3]")] + [(f, "u32") for f in SHAPE_FIELDS[2:]]
-    assert "size_of::<vx_walk_info>() == 32" in text and "size_of::<vx_walk_shape>() == 52" in text
-    decl = re.search(r"pub fn vx_walk_points\((.*?)\)\s*->\s*c_int;", text, flags=re.S).group(1)
-    assert [a.split(":")[0].strip() for a in decl.split(",")] == ["ctx", "pos", "pos_stride", "goal", "goal_stride", "count", "shape", "memory", "fields", "field_stride",
+        assert rust.const_int(name) == (kind, value), name
+    assert rust.struct("vx_walk_info") == [(f, "u32") for f in INFO_FIELDS]
+    assert rust.struct("vx_walk_shape") == [("size", "[u32; 3]"), ("seed_at", "[u32; 3]")] + [(f, "u32") for f in SHAPE_FIELDS[2:]]
+    assert rust.asserts_size("vx_walk_info", 32) and rust.asserts_size("vx_walk_shape", 52)
+    assert rust.args("vx_walk_points") == ["ctx", "pos", "pos_stride", "goal", "goal_stride", "count", "shape", "memory", "fields", "field_stride",
                                                                    "paths", "info"]
 
 
@@ -113,21 +87,19 @@ def test_argument_checks_need_no_device():
     fields = np.full(2 * 3472 + 32, 0x5a, dtype=np.uint8)
     paths = np.full(2 * 252 + 8, 0x5a5a5a5a, dtype=np.uint32)
     info = np.full(3 * 32, 0x5a, dtype=np.uint8)
-    sentinel = fields.tobytes() + paths.tobytes() + info.tobytes()
     v = np.arange(64, dtype=np.float32)
     base = v.ctypes.data
     u3 = C.c_uint32 * 3
     assert base % 4 == 0
 
-    def refused(word, count=2, memory=hip.VX_MEM_HOST, pos=base, pos_stride=12, goal=base + 64, goal_stride=12, f=fields.ctypes.data, field_stride=0, p=paths.ctypes.data,
+    def call(count=2, memory=hip.VX_MEM_HOST, pos=base, pos_stride=12, goal=base + 64, goal_stride=12, f=fields.ctypes.data, field_stride=0, p=paths.ctypes.data,
                 i=info.ctypes.data, shape=True, **shape_fields):
         s = hip.walk_shape((17, 12, 17), (8, 6, 8), 250, path_capacity=252)
         for k, val in shape_fields.items():
             setattr(s, k, val)
-        rc = L.vx_walk_points(None, pos, pos_stride, goal, goal_stride, count, C.byref(s) if shape else None, memory, f, field_stride, p, i)
-        assert rc == 1 and word in L.vx_last_error(), (word, rc, L.vx_last_error())
-        assert fields.tobytes() + paths.tobytes() + info.tobytes() == sentinel
+        return L.vx_walk_points(None, pos, pos_stride, goal, goal_stride, count, C.byref(s) if shape else None, memory, f, field_stride, p, i)
 
+    refused = refusing(L, call, (fields, paths, info))
     refused(b"null context")
     refused(b"VX_MEM", memory=5)
     refused(b"VX_MEM", memory=-1)

@@ -8,16 +8,14 @@ boolean arrays with the three edge kinds (a query leaves the batch when its fron
 run once per shape and pass_value to VX_WALK_MAX_STEPS; a smaller step limit's field is that field with the larger step counts turned into
 VX_WALK_UNREACHED, and VX_WALK_STOP_AT_GOAL is the step limit min(max_steps, path_steps), as the header states it. Nothing of the code under
 test is used. Also the runner of the host harness (tests/cpp/walk_on_host.cpp), a stand-alone program, plain and built with sanitizers."""
-import subprocess
-import tempfile
-from pathlib import Path
 
 import numpy as np
 
 from batch_cases import _chunk_of
-from blocks_cases import BUILD, dense_region
+from blocks_cases import dense_region
+from host_harness import HostRunner, build_harness, outputs_differing
 from flood_cases import BURROW_AT, FLOOD_CASES, in_form, make_flood_case, torch_positions  # noqa: F401  (the forms are the flood's)
-from helpers import ROOT, vra
+from helpers import vra
 from scan_cases import ScanCase, start_of
 from voxel_rs_amd import hip, host
 
@@ -479,46 +477,23 @@ def batches(count, field_stride):
 
 
 def harness(sanitize=False):
-    """tests/_build/walk_on_host (or walk_on_host_san: the same program under AddressSanitizer and UndefinedBehaviorSanitizer, every finding
-    fatal), built when it is older than its sources."""
-    BUILD.mkdir(exist_ok=True)
-    exe = BUILD / ("walk_on_host_san" if sanitize else "walk_on_host")
-    blocks = Path(ROOT) / "voxel-rs_amd" / "csrc" / "blocks"
-    deps = [Path(ROOT) / "tests" / "cpp" / "walk_on_host.cpp", blocks / "vx_walk.hpp", blocks / "vx_flood.hpp", blocks / "vx_scan.hpp", blocks / "vx_blocks.hpp",
-            Path(ROOT) / "include" / "voxel_hip.h"]
-    if not exe.exists() or exe.stat().st_mtime < max(p.stat().st_mtime for p in deps):
-        flags = ["-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else []
-        cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", *flags, f"-I{ROOT}/include", f"-I{ROOT}/tests/cpp/shims", f"-I{blocks}", str(deps[0]), "-o", str(exe)]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout
-    return exe
+    """tests/_build/walk_on_host, or walk_on_host_san: host_harness.build_harness's."""
+    return build_harness("walk_on_host", sanitize)
 
 
-class HostWalk:
+class HostWalk(HostRunner):
     """The harness on one world: the frame is written once, every call is a run of the program."""
-
-    def __init__(self, exe, c):
-        self.exe, self.c = exe, c
-        self.dir = tempfile.TemporaryDirectory()
-        self.world = Path(self.dir.name) / "world.bin"
-        c.frame.tofile(self.world)
 
     def walk(self, raw, stride, graw, gstride, count, shape, max_steps, path_capacity=0, flags=0, pass_value=0, field_stride=0, fields=True, info=True, paths=None):
         """(fields [count, field_stride or padded] or None, WALK_INFO_DTYPE records or None, paths uint32 [count, path_capacity] or None).
         graw None: no goal; paths None: asked for when there is a goal."""
         paths = graw is not None if paths is None else paths
-        d = Path(self.dir.name)
-        np.asarray(raw).view(np.uint8).tofile(d / "points.bin")
-        if graw is not None:
-            np.asarray(graw).view(np.uint8).tofile(d / "goals.bin")
-        args = [self.exe, self.c.svo_type, self.world, "walk", d / "points.bin", stride, d / "goals.bin" if graw is not None else "-", gstride, count, *shape.size,
-                *shape.seed_at, max_steps, pass_value, shape.height, shape.climb, shape.drop, path_capacity, flags, field_stride,
-                d / "fields.bin" if fields else "-", d / "paths.bin" if paths else "-", d / "info.bin" if info else "-"]
-        r = subprocess.run([str(a) for a in args], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout
-        f = np.fromfile(d / "fields.bin", dtype=np.uint8).reshape(count, field_stride or shape.padded) if fields else None
-        i = np.fromfile(d / "info.bin", dtype=hip.WALK_INFO_DTYPE) if info else None
-        p = np.fromfile(d / "paths.bin", dtype=np.uint32).reshape(count, path_capacity) if paths else None
+        self.run("walk", self.put("points.bin", raw), stride, "-" if graw is None else self.put("goals.bin", graw), gstride, count, *shape.size, *shape.seed_at, max_steps,
+                 pass_value, shape.height, shape.climb, shape.drop, path_capacity, flags, field_stride, self.path("fields.bin", fields), self.path("paths.bin", paths),
+                 self.path("info.bin", info))
+        f = self.get("fields.bin", np.uint8, fields, (count, field_stride or shape.padded))
+        i = self.get("info.bin", hip.WALK_INFO_DTYPE, info)
+        p = self.get("paths.bin", np.uint32, paths, (count, path_capacity))
         assert i is None or len(i) == count
         return f, i, p
 
@@ -531,21 +506,7 @@ class HostWalk:
         graw, gstride, _ = in_form(goals, form)
         return self.walk(raw, stride, graw, gstride, len(pts), shape, max_steps, cap, flags, pass_value)
 
-    def close(self):
-        self.dir.cleanup()
-
 
 def differing(got, exp):
     """A message naming the first query whose field, record or path differs between two (fields, info, paths), or None."""
-    (gf, gi, gp), (ef, ei, ep) = got, exp
-    if gf.shape != ef.shape or gi.shape != ei.shape or gp.shape != ep.shape:
-        return f"shapes differ: {gf.shape}, {gi.shape}, {gp.shape} vs {ef.shape}, {ei.shape}, {ep.shape}"
-    bad = (gf != ef).any(axis=1) | (gi.view(np.uint32).reshape(-1, 8) != ei.view(np.uint32).reshape(-1, 8)).any(axis=1) | (gp != ep).any(axis=1)
-    bad = np.flatnonzero(bad)
-    if not len(bad):
-        return None
-    i = int(bad[0])
-    cells, entries = np.flatnonzero(gf[i] != ef[i]), np.flatnonzero(gp[i] != ep[i])
-    return (f"{len(bad)} queries differ, first {i}: record {gi[i]} expected {ei[i]}; {len(cells)} cells differ"
-            + (f", first at {int(cells[0])}: {int(gf[i][cells[0]])} expected {int(ef[i][cells[0]])}" if len(cells) else "")
-            + (f"; {len(entries)} path entries differ, first at {int(entries[0])}: {int(gp[i][entries[0]]):#x} expected {int(ep[i][entries[0]]):#x}" if len(entries) else ""))
+    return outputs_differing(got, exp)

@@ -17,6 +17,7 @@
 #include <cstdint>
 
 #include "voxel_hip.h"
+#include "vx_rules.hpp"
 
 #if defined(__HIPCC__)
 #define VXB_FN __host__ __device__ __forceinline__  // (a call would put its pointer arguments -- a position, a cursor -- into scratch)
@@ -306,8 +307,8 @@ inline void read_region(const W& w, const int32_t lo[3], const uint32_t size[3],
 inline const char* check_points(const void* pos, uint32_t pos_stride, uint32_t count, const void* out) {
     if (count == 0) return nullptr;  // nothing is read or written: nothing to refuse
     if (count > kMaxCount) return "count exceeds 16777216 (2^24)";
-    if (pos_stride % 4 || pos_stride < 12) return "pos_stride must be a multiple of 4 and >= 12";
-    if (reinterpret_cast<uintptr_t>(pos) % 4) return "pos must be aligned to 4 bytes";
+    if (!stride_ok(pos_stride)) return "pos_stride must be a multiple of 4 and >= 12";
+    if (!aligned_to_4(pos)) return "pos must be aligned to 4 bytes";
     if (!pos) return "null pos";
     if (!out) return "null out";
     return nullptr;

@@ -205,12 +205,12 @@ inline const char* check_boxes(const vx_box_batch* boxes, uint32_t count, const 
     if (!out) return "null out";
     if (!boxes->origin) return "null origin";
     if (!boxes->extents) return "null extents";
-    if (boxes->origin_stride % 4 || boxes->origin_stride < 12) return "origin_stride must be a multiple of 4 and >= 12";
-    if (boxes->offset && (boxes->offset_stride % 4 || (boxes->offset_stride && boxes->offset_stride < 12))) return "offset_stride must be 0, or a multiple of 4 and >= 12";
-    if (boxes->extents_stride % 4 || (boxes->extents_stride && boxes->extents_stride < 12)) return "extents_stride must be 0, or a multiple of 4 and >= 12";
-    if (reinterpret_cast<uintptr_t>(boxes->origin) % 4) return "origin must be aligned to 4 bytes";
-    if (reinterpret_cast<uintptr_t>(boxes->offset) % 4) return "offset must be aligned to 4 bytes";
-    if (reinterpret_cast<uintptr_t>(boxes->extents) % 4) return "extents must be aligned to 4 bytes";
+    if (!stride_ok(boxes->origin_stride)) return "origin_stride must be a multiple of 4 and >= 12";
+    if (boxes->offset && !stride_ok(boxes->offset_stride, true)) return "offset_stride must be 0, or a multiple of 4 and >= 12";
+    if (!stride_ok(boxes->extents_stride, true)) return "extents_stride must be 0, or a multiple of 4 and >= 12";
+    if (!aligned_to_4(boxes->origin)) return "origin must be aligned to 4 bytes";
+    if (!aligned_to_4(boxes->offset)) return "offset must be aligned to 4 bytes";
+    if (!aligned_to_4(boxes->extents)) return "extents must be aligned to 4 bytes";
     return nullptr;
 }
 

@@ -24,7 +24,6 @@
 namespace vxb {
 
 constexpr uint32_t kDistanceMaxCount = 1u << 20;  // boxes of a call
-constexpr uint32_t kDistanceMaxBytes = 1u << 24;  // of all fields of a call
 constexpr uint32_t kDistanceNone = VX_DISTANCE_NONE;
 constexpr uint32_t kDistanceCells = kFloodRows * kFloodSide;  // 32,768: an entry's number has 15 bits
 
@@ -199,38 +198,25 @@ inline void distance_boxes(const W& w, const uint8_t* lo, uint32_t lo_stride, ui
     }
 }
 
-// Do the bytes [a, a + an) and [b, b + bn) share one? (an absent part has no bytes)
-inline bool distance_spans_meet(const void* a, uint64_t an, const void* b, uint64_t bn) {
-    const uint64_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return a && b && an && bn && pa < pb + bn && pb < pa + an;
-}
-
 // the rules of the call that need no device: what is wrong, naming the field, or null. (Alignment of device memory: blocks_runtime.cpp.)
 inline const char* check_distance(const void* lo, uint32_t lo_stride, uint32_t count, const vx_distance_shape* s, const void* fields, uint32_t field_stride,
                                   const void* info) {
     if (count == 0) return nullptr;  // nothing is read or written: nothing to refuse
     if (count > kDistanceMaxCount) return "count exceeds 1048576 (2^20)";
     if (!s) return "null shape";
-    if (!lo) return "null lo";
-    if (!fields && !info) return "fields and info are both null";
-    if (lo_stride % 4 || lo_stride < 12) return "lo_stride must be a multiple of 4 and >= 12";
-    if (reinterpret_cast<uintptr_t>(lo) % 4) return "lo must be aligned to 4 bytes";
-    for (int a = 0; a < 3; ++a)
-        if (s->size[a] == 0 || s->size[a] > kFloodSide) return "size: every component must be 1..32";
+    if (const char* what = lo_rule(lo, lo_stride, fields || info ? nullptr : "fields and info are both null")) return what;
+    if (const char* what = size_rule(s->size, kFloodSide, "size: every component must be 1..32")) return what;
     if (s->flags & ~uint32_t(VX_DISTANCE_TO_AIR)) return "flags holds a bit other than VX_DISTANCE_TO_AIR";
     if (s->match_value && s->pass_value) return "pass_value must be 0 with a match_value";
-    uint64_t field_bytes = 0;
-    if (fields) {
-        const uint32_t least = 2u * distance_voxels(*s);
-        if (field_stride % 16u || (field_stride && field_stride < least)) return "field_stride must be 0, or a multiple of 16 and at least 2 * size.x * size.y * size.z";
-        const uint64_t stride = field_stride ? field_stride : distance_field_bytes(*s);
-        if (uint64_t(count) * stride > kDistanceMaxBytes) return "count * field_stride exceeds 16777216 (2^24) bytes";
-        field_bytes = uint64_t(count - 1u) * stride + distance_field_bytes(*s);
-    }
-    const uint64_t lo_bytes = uint64_t(count - 1u) * lo_stride + 12u, info_bytes = info ? uint64_t(count) * sizeof(vx_distance_info) : 0u;
-    if (distance_spans_meet(fields, field_bytes, lo, lo_bytes)) return "fields overlaps lo";
-    if (distance_spans_meet(info, info_bytes, lo, lo_bytes)) return "info overlaps lo";
-    if (distance_spans_meet(fields, field_bytes, info, info_bytes)) return "fields overlaps info";
+    const uint32_t packed = distance_field_bytes(*s);
+    const char* const at_least = "field_stride must be 0, or a multiple of 16 and at least 2 * size.x * size.y * size.z";
+    if (fields)
+        if (const char* what = field_stride_rule(count, field_stride, 2u * distance_voxels(*s), packed, at_least)) return what;
+    const uint64_t lo_bytes = lo_span(count, lo_stride), field_bytes = fields ? field_span(count, field_stride, packed) : 0u;
+    const uint64_t info_bytes = info ? uint64_t(count) * sizeof(vx_distance_info) : 0u;
+    if (spans_meet(fields, field_bytes, lo, lo_bytes)) return "fields overlaps lo";
+    if (spans_meet(info, info_bytes, lo, lo_bytes)) return "info overlaps lo";
+    if (spans_meet(fields, field_bytes, info, info_bytes)) return "fields overlaps info";
     return nullptr;
 }
 

@@ -23,7 +23,6 @@ namespace vxb {
 
 constexpr uint32_t kFloodSide = 32, kFloodRows = kFloodSide * kFloodSide;  // a box is at most 32 cells an axis: a row is a dword
 constexpr uint32_t kFloodThreads = 256, kFloodOwned = kFloodRows / kFloodThreads;  // rows a thread owns
-constexpr uint32_t kFloodMaxBytes = 1u << 24;                              // of all fields of a call
 constexpr uint32_t kFloodLanes = kBrick * kBrick;
 
 VXB_FN bool flood_has_position(const float p[3]) { return is_finite(p[0]) && is_finite(p[1]) && is_finite(p[2]); }
@@ -192,18 +191,11 @@ inline const char* check_flood(const void* pos, uint32_t pos_stride, uint32_t co
     if (!s) return "null shape";
     if (!fields && !info) return "fields and info are both null";
     if (const char* what = check_points(pos, pos_stride, count, fields ? fields : info)) return what;  // (its `out`: the output there is)
-    for (int a = 0; a < 3; ++a) {
-        if (s->size[a] == 0 || s->size[a] > kFloodSide) return "size: every component must be 1..32";
-        if (s->seed_at[a] >= s->size[a]) return "seed_at: every component must be below size's";
-    }
+    if (const char* what = size_rule(s->size, kFloodSide, "size: every component must be 1..32", s->seed_at)) return what;
     if (s->max_steps > VX_FLOOD_MAX_STEPS) return "max_steps exceeds VX_FLOOD_MAX_STEPS (250)";
     if (s->flags & ~uint32_t(VX_FLOOD_SEED_ALWAYS)) return "flags holds a bit other than VX_FLOOD_SEED_ALWAYS";
-    if (fields) {
-        const uint32_t voxels = flood_voxels(*s);
-        if (field_stride % 16u || (field_stride && field_stride < voxels)) return "field_stride must be 0, or a multiple of 16 and at least size.x * size.y * size.z";
-        const uint64_t stride = field_stride ? field_stride : flood_round16(voxels);
-        if (uint64_t(count) * stride > kFloodMaxBytes) return "count * field_stride exceeds 16777216 (2^24) bytes";
-    }
+    const uint32_t voxels = flood_voxels(*s);
+    if (fields) return field_stride_rule(count, field_stride, voxels, flood_round16(voxels), "field_stride must be 0, or a multiple of 16 and at least size.x * size.y * size.z");
     return nullptr;
 }
 

@@ -25,7 +25,7 @@
 namespace vxb {
 
 constexpr uint32_t kLabelMaxCount = 1u << 20;  // boxes of a call: a query may run thousands of steps, and the launch must end in bounded time
-constexpr uint32_t kLabelMaxBytes = 1u << 24;  // of all fields, and of all piece records, of a call
+constexpr uint32_t kLabelMaxBytes = 1u << 24;  // of all piece records of a call (the fields: vx_rules.hpp)
 constexpr uint32_t kLabelNoSeed = 0xffffffffu;
 
 VXB_FN uint32_t label_voxels(const vx_label_shape& s) { return s.size[0] * s.size[1] * s.size[2]; }
@@ -254,46 +254,33 @@ inline void label_boxes(const W& w, const uint8_t* lo, uint32_t lo_stride, uint3
     }
 }
 
-// Do the bytes [a, a + an) and [b, b + bn) share one? (an absent part has no bytes)
-inline bool label_spans_meet(const void* a, uint64_t an, const void* b, uint64_t bn) {
-    const uint64_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return a && b && an && bn && pa < pb + bn && pb < pa + an;
-}
-
 // the rules of the call that need no device: what is wrong, naming the field, or null. (Alignment of device memory: blocks_runtime.cpp.)
 inline const char* check_label(const void* lo, uint32_t lo_stride, uint32_t count, const vx_label_shape* s, const void* fields, uint32_t field_stride,
                                const void* pieces, const void* info) {
     if (count == 0) return nullptr;  // nothing is read or written: nothing to refuse
     if (count > kLabelMaxCount) return "count exceeds 1048576 (2^20)";
     if (!s) return "null shape";
-    if (!lo) return "null lo";
-    if (!fields && !pieces && !info) return "fields, pieces and info are all null";
-    if (lo_stride % 4 || lo_stride < 12) return "lo_stride must be a multiple of 4 and >= 12";
-    if (reinterpret_cast<uintptr_t>(lo) % 4) return "lo must be aligned to 4 bytes";
-    for (int a = 0; a < 3; ++a)
-        if (s->size[a] == 0 || s->size[a] > kFloodSide) return "size: every component must be 1..32";
+    if (const char* what = lo_rule(lo, lo_stride, fields || pieces || info ? nullptr : "fields, pieces and info are all null")) return what;
+    if (const char* what = size_rule(s->size, kFloodSide, "size: every component must be 1..32")) return what;
     if (s->anchor_faces & ~uint32_t(VX_LABEL_ALL_FACES)) return "anchor_faces holds a bit above bit 5";
     if (s->max_pieces > VX_LABEL_MAX_PIECES) return "max_pieces exceeds VX_LABEL_MAX_PIECES (250)";
     if (s->max_steps > VX_LABEL_MAX_STEPS) return "max_steps exceeds VX_LABEL_MAX_STEPS (4096)";
     if (s->flags) return "flags must be 0";
     if (pieces && s->max_pieces == 0) return "pieces with max_pieces == 0";
-    uint64_t field_bytes = 0;
-    if (fields) {
-        const uint32_t voxels = label_voxels(*s);
-        if (field_stride % 16u || (field_stride && field_stride < voxels)) return "field_stride must be 0, or a multiple of 16 and at least size.x * size.y * size.z";
-        const uint64_t stride = field_stride ? field_stride : flood_round16(voxels);
-        if (uint64_t(count) * stride > kLabelMaxBytes) return "count * field_stride exceeds 16777216 (2^24) bytes";
-        field_bytes = uint64_t(count - 1u) * stride + flood_round16(voxels);
-    }
+    const uint32_t packed = flood_round16(label_voxels(*s));
+    const char* const at_least = "field_stride must be 0, or a multiple of 16 and at least size.x * size.y * size.z";
+    if (fields)
+        if (const char* what = field_stride_rule(count, field_stride, label_voxels(*s), packed, at_least)) return what;
     const uint64_t piece_bytes = pieces ? uint64_t(count) * s->max_pieces * sizeof(vx_label_piece) : 0u;
     if (piece_bytes > kLabelMaxBytes) return "count * max_pieces * 16 exceeds 16777216 (2^24) bytes";
-    const uint64_t lo_bytes = uint64_t(count - 1u) * lo_stride + 12u, info_bytes = info ? uint64_t(count) * sizeof(vx_label_info) : 0u;
-    if (label_spans_meet(fields, field_bytes, lo, lo_bytes)) return "fields overlaps lo";
-    if (label_spans_meet(pieces, piece_bytes, lo, lo_bytes)) return "pieces overlaps lo";
-    if (label_spans_meet(info, info_bytes, lo, lo_bytes)) return "info overlaps lo";
-    if (label_spans_meet(fields, field_bytes, pieces, piece_bytes)) return "fields overlaps pieces";
-    if (label_spans_meet(fields, field_bytes, info, info_bytes)) return "fields overlaps info";
-    if (label_spans_meet(pieces, piece_bytes, info, info_bytes)) return "pieces overlaps info";
+    const uint64_t lo_bytes = lo_span(count, lo_stride), field_bytes = fields ? field_span(count, field_stride, packed) : 0u;
+    const uint64_t info_bytes = info ? uint64_t(count) * sizeof(vx_label_info) : 0u;
+    if (spans_meet(fields, field_bytes, lo, lo_bytes)) return "fields overlaps lo";
+    if (spans_meet(pieces, piece_bytes, lo, lo_bytes)) return "pieces overlaps lo";
+    if (spans_meet(info, info_bytes, lo, lo_bytes)) return "info overlaps lo";
+    if (spans_meet(fields, field_bytes, pieces, piece_bytes)) return "fields overlaps pieces";
+    if (spans_meet(fields, field_bytes, info, info_bytes)) return "fields overlaps info";
+    if (spans_meet(pieces, piece_bytes, info, info_bytes)) return "pieces overlaps info";
     return nullptr;
 }
 

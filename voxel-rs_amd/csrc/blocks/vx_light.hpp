@@ -38,7 +38,6 @@ namespace vxb {
 
 constexpr uint32_t kLightSide = VX_LIGHT_MAX_SIDE, kLightRows = kLightSide * kLightSide;  // a box is at most 48 cells an axis: a row is 64 bits
 constexpr uint32_t kLightThreads = 256, kLightOwned = kLightRows / kLightThreads;           // rows a thread owns: 9
-constexpr uint32_t kLightMaxBytes = 1u << 24;                                               // of all fields of a call
 constexpr uint32_t kLightTop = 15, kLightSteps = 14;                                        // the levels 14 .. 1 are found by spreading
 static_assert(kLightOwned * kLightThreads == kLightRows, "every row has an owner");
 
@@ -277,24 +276,16 @@ inline const char* check_light(const void* lo, uint32_t lo_stride, uint32_t coun
     if (count == 0) return nullptr;  // nothing is read or written: nothing to refuse
     if (count > kMaxCount) return "count exceeds 16777216 (2^24)";
     if (!s) return "null shape";
-    if (!lo) return "null lo";
-    if (!fields && !info) return "fields and info are both null";
-    if (lo_stride % 4 || lo_stride < 12) return "lo_stride must be a multiple of 4 and >= 12";
-    if (reinterpret_cast<uintptr_t>(lo) % 4) return "lo must be aligned to 4 bytes";
-    for (int a = 0; a < 3; ++a)
-        if (s->size[a] == 0 || s->size[a] > kLightSide) return "size: every component must be 1..48";
+    if (const char* what = lo_rule(lo, lo_stride, fields || info ? nullptr : "fields and info are both null")) return what;
+    if (const char* what = size_rule(s->size, kLightSide, "size: every component must be 1..48")) return what;
     if (s->flags & ~uint32_t(VX_LIGHT_NO_SKY | VX_LIGHT_NO_BLOCKS)) return "flags holds a bit other than VX_LIGHT_NO_SKY and VX_LIGHT_NO_BLOCKS";
     if (s->flags == uint32_t(VX_LIGHT_NO_SKY | VX_LIGHT_NO_BLOCKS)) return "flags: VX_LIGHT_NO_SKY and VX_LIGHT_NO_BLOCKS together leave nothing to do";
     if (s->props_count > VX_LIGHT_MAX_PROPS) return "props_count exceeds VX_LIGHT_MAX_PROPS (4096)";
     if (s->props_count && !s->props) return "null props with props_count > 0";
     for (uint32_t k = 0; k < s->props_count; ++k)
         if (s->props[k] & 0xE0u) return "props: a byte has one of bits 5..7 set";
-    if (fields) {
-        const uint32_t voxels = light_voxels(s->size);
-        if (field_stride % 16u || (field_stride && field_stride < voxels)) return "field_stride must be 0, or a multiple of 16 and at least size.x * size.y * size.z";
-        const uint64_t stride = field_stride ? field_stride : light_round16(voxels);
-        if (uint64_t(count) * stride > kLightMaxBytes) return "count * field_stride exceeds 16777216 (2^24) bytes";
-    }
+    const uint32_t voxels = light_voxels(s->size);
+    if (fields) return field_stride_rule(count, field_stride, voxels, light_round16(voxels), "field_stride must be 0, or a multiple of 16 and at least size.x * size.y * size.z");
     return nullptr;
 }
 

@@ -250,8 +250,8 @@ inline const char* check_move(const vx_box_batch* boxes, const void* motion, uin
     if (count == 0) return nullptr;  // nothing is read or written: nothing more to refuse
     if (const char* what = check_boxes(boxes, count, out)) return what;
     if (!motion) return "null motion";
-    if (motion_stride % 4 || (motion_stride && motion_stride < 12)) return "motion_stride must be 0, or a multiple of 4 and >= 12";
-    if (reinterpret_cast<uintptr_t>(motion) % 4) return "motion must be aligned to 4 bytes";
+    if (!stride_ok(motion_stride, true)) return "motion_stride must be 0, or a multiple of 4 and >= 12";
+    if (!aligned_to_4(motion)) return "motion must be aligned to 4 bytes";
     return nullptr;
 }
 

@@ -24,7 +24,7 @@
 namespace vxb {
 
 constexpr uint32_t kWalkMaxPath = 252;        // entries of a path: 63 16-byte stores
-constexpr uint32_t kWalkMaxBytes = 1u << 24;  // of all fields, and of all paths, of a call
+constexpr uint32_t kWalkMaxBytes = 1u << 24;  // of all paths of a call (the fields: vx_rules.hpp)
 constexpr uint32_t kWalkMaxHeight = 4, kWalkMaxDrop = 3;
 constexpr uint32_t kWalkFieldBytes = kFloodSide * (kFloodSide - 1u) * kFloodSide;  // size.y <= 31: a multiple of 16
 
@@ -280,13 +280,10 @@ inline const char* check_walk(const void* pos, uint32_t pos_stride, const void* 
     if (paths && !goal) return "paths without goal";
     if (const char* what = check_points(pos, pos_stride, count, fields ? fields : info ? info : paths)) return what;  // (its `out`: the output there is)
     if (goal) {
-        if (goal_stride && (goal_stride % 4 || goal_stride < 12)) return "goal_stride must be 0, or a multiple of 4 and >= 12";
-        if (reinterpret_cast<uintptr_t>(goal) % 4) return "goal must be aligned to 4 bytes";
+        if (!stride_ok(goal_stride, true)) return "goal_stride must be 0, or a multiple of 4 and >= 12";
+        if (!aligned_to_4(goal)) return "goal must be aligned to 4 bytes";
     }
-    for (int a = 0; a < 3; ++a) {
-        if (s->size[a] == 0 || s->size[a] > kFloodSide) return "size: every component must be 1..32";
-        if (s->seed_at[a] >= s->size[a]) return "seed_at: every component must be below size's";
-    }
+    if (const char* what = size_rule(s->size, kFloodSide, "size: every component must be 1..32", s->seed_at)) return what;
     if (s->height == 0 || s->height > kWalkMaxHeight) return "height must be 1..4";
     if (s->size[1] + s->height > kFloodSide) return "size[1] + height exceeds 32";
     if (s->max_steps > VX_WALK_MAX_STEPS) return "max_steps exceeds VX_WALK_MAX_STEPS (250)";
@@ -294,12 +291,10 @@ inline const char* check_walk(const void* pos, uint32_t pos_stride, const void* 
     if (s->drop > kWalkMaxDrop) return "drop must be 0..3";
     if (s->path_capacity > kWalkMaxPath || s->path_capacity % 4u) return "path_capacity must be a multiple of 4 and at most 252";
     if (s->flags & ~uint32_t(VX_WALK_STOP_AT_GOAL)) return "flags holds a bit other than VX_WALK_STOP_AT_GOAL";
-    if (fields) {
-        const uint32_t voxels = walk_voxels(*s);
-        if (field_stride % 16u || (field_stride && field_stride < voxels)) return "field_stride must be 0, or a multiple of 16 and at least size.x * size.y * size.z";
-        const uint64_t stride = field_stride ? field_stride : flood_round16(voxels);
-        if (uint64_t(count) * stride > kWalkMaxBytes) return "count * field_stride exceeds 16777216 (2^24) bytes";
-    }
+    const uint32_t voxels = walk_voxels(*s);
+    const char* const at_least = "field_stride must be 0, or a multiple of 16 and at least size.x * size.y * size.z";
+    if (fields)
+        if (const char* what = field_stride_rule(count, field_stride, voxels, flood_round16(voxels), at_least)) return what;
     if (paths && uint64_t(count) * s->path_capacity * 4u > kWalkMaxBytes) return "count * path_capacity * 4 exceeds 16777216 (2^24) bytes";
     return nullptr;
 }

@@ -8,19 +8,12 @@ import numpy as np
 import pytest
 
 from batch_cases import CASES, DT, STEPS, describe_entity, describe_ray, first_difference, make_case, oracle_hits
+from gpu_harness import make_context
 from helpers import orc, vra  # noqa: F401
 from test_raycast_batch import assert_is_picker_result, tasks_of
 from voxel_rs_amd import hip, host
 
 pytestmark = pytest.mark.gpu
-
-
-def make_context(c):
-    svo = hip.Svo(c.svo_type, c.world.size_in_bytes + (1 << 20))
-    svo.set_materials(c.mats)
-    svo.set_textures(c.tex, 6)
-    svo.update_full(c.world)  # (the whole frame: a world keeps its dirty ranges for one target only, and the cases' worlds are shared)
-    return svo
 
 
 _cases = {}

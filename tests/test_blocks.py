@@ -6,26 +6,12 @@ import pytest
 
 from batch_cases import CASES, RAY_SEED, TRANSLUCENT_IDS, _chunk_of, build_rays_for, oracle_hits
 from blocks_cases import REGIONS, check_cells, classify, dense_region, harness, host_points, make_block_case
+from gpu_harness import big_esvo_context, leaves_the_outputs_alone, make_context, no_image_context, to_device
 from helpers import vra  # noqa: F401
 from voxel_rs_amd import hip
 
 pytestmark = pytest.mark.gpu
 COUNTS = [1, 63, 64, 65, None]  # None: the whole set
-
-
-def make_context(c, world=None):
-    world = c.world if world is None else world
-    svo = hip.Svo(c.svo_type, world.size_in_bytes + (1 << 20))
-    svo.set_materials(c.mats)
-    svo.set_textures(c.tex, 6)
-    svo.update_full(world)
-    return svo
-
-
-def to_device(array):
-    import torch
-
-    return torch.from_numpy(np.array(array, order="C")).cuda()  # (a copy: the shared arrays are read-only)
 
 
 def region_to_numpy(t):
@@ -115,15 +101,10 @@ def test_a_regions_voxels_are_the_points_at_their_centres(case):
 
 def test_without_a_traversal_image_the_bytes_are_the_same(case, monkeypatch):
     """2, last item: a context created with VX_TRAVERSAL_IMAGE=0 (read when a context is created) answers with the same bytes."""
-    monkeypatch.setenv("VX_TRAVERSAL_IMAGE", "0")
-    svo = make_context(case)
-    try:
-        assert svo.image_info()["layout"] == 0  # (no traversal image in this context)
+    with no_image_context(case, monkeypatch) as svo:
         assert svo.block_points(case.pts).tobytes() == case.host_cells.tobytes()
         for lo, size in [REGIONS[case.name]] + small_regions(case):
             assert svo.read_region(lo, size).tobytes() == case.svo.read_region(lo, size).tobytes(), (lo, size)
-    finally:
-        svo.close()
 
 
 @pytest.mark.parametrize("fmt", ["esvo", "csvo"])
@@ -162,21 +143,8 @@ def test_esvo_big():
     """The glasshouse in an ESVO context of 4 GiB, which selects the VX_SVO_ESVO_BIG builds of both kernels (runtime.cpp: ctx->big depends on the
     capacity alone; the world is read through a 64-bit address with an explicit range check): points from device and host memory and the
     regions, against the host harness's records and the dense array."""
-    import ctypes as C
-
     c = make_block_case("glasshouse", "esvo")
-    h = C.c_void_p()
-    rc = hip.lib().vx_create(c.svo_type, 1 << 32, 0, C.byref(h))
-    if rc == 3:  # VX_ERR_OUT_OF_MEMORY, from vx_create itself: the one reason to skip (as tests/test_batch_physics_worlds.py::test_esvo_big)
-        pytest.skip("vx_create: " + hip.lib().vx_last_error().decode())
-    assert rc == 0, hip.lib().vx_last_error()
-    svo = hip.Svo.__new__(hip.Svo)
-    svo._h, svo.svo_type = h, c.svo_type
-    try:
-        svo.set_materials(c.mats)
-        svo.set_textures(c.tex, 6)
-        svo.update_full(c.world)
-        assert svo.get_stats()["capacity_bytes"] == 1 << 32
+    with big_esvo_context(c) as svo:
         exp = host_points(harness(), c, c.pts, 12, len(c.pts))
         check_cells(c, exp)
         d_pts = to_device(c.pts)
@@ -188,8 +156,6 @@ def test_esvo_big():
         for (lo, size), dev in zip(boxes, on_device):
             want = dense_region(c.info, c.truth, lo, size)
             assert (region_to_numpy(dev) == want).all() and svo.read_region(lo, size).tobytes() == want.tobytes(), (lo, size)
-    finally:
-        svo.close()
 
 
 def test_the_block_behind_a_hit_face_is_the_hits_value(case):
@@ -224,24 +190,16 @@ def test_errors_leave_the_output_alone(case):
     L, h, vp = hip.lib(), case.svo._h, C.c_void_p
     pts = np.array(case.pts[:8], order="C")
     out = np.full(8 * 8, 0x5a, dtype=np.uint8)
-    sentinel = out.tobytes()
     lo3, size3 = (C.c_int32 * 3)(0, 0, 0), (C.c_uint32 * 3)(2, 2, 2)
     o = vp(out.ctypes.data)
-    for call, word in ((lambda: L.vx_block_points(h, vp(pts.ctypes.data), 8, 8, hip.VX_MEM_HOST, o), b"pos_stride"),
-                       (lambda: L.vx_block_points(h, None, 12, 8, hip.VX_MEM_HOST, o), b"null pos"),
-                       (lambda: L.vx_block_points(h, vp(pts.ctypes.data), 12, 8, 3, o), b"VX_MEM"),
-                       (lambda: L.vx_read_region(h, None, C.byref(size3), hip.VX_MEM_HOST, o), b"null lo"),
-                       (lambda: L.vx_read_region(h, C.byref(lo3), C.byref((C.c_uint32 * 3)(256, 256, 257)), hip.VX_MEM_HOST, o), b"size.x")):
-        rc = call()
-        assert rc == 1 and word in L.vx_last_error(), (rc, word, L.vx_last_error())
-        assert out.tobytes() == sentinel
-    assert L.vx_block_points(h, None, 12, 0, hip.VX_MEM_HOST, None) == 0
-    assert L.vx_block_points(h, vp(pts.ctypes.data + 1), 5, 0, hip.VX_MEM_DEVICE, vp(out.ctypes.data + 3)) == 0  # (no points: nothing to refuse)
-    assert L.vx_read_region(h, C.byref(lo3), C.byref((C.c_uint32 * 3)(2, 0, 2)), hip.VX_MEM_DEVICE, None) == 0
-    fresh = hip.Svo(case.svo_type, 1 << 20)
-    try:
-        assert L.vx_block_points(fresh._h, vp(pts.ctypes.data), 12, 8, hip.VX_MEM_HOST, vp(out.ctypes.data)) == 6 and b"committed" in L.vx_last_error()
-        assert L.vx_read_region(fresh._h, C.byref(lo3), C.byref(size3), hip.VX_MEM_HOST, vp(out.ctypes.data)) == 6 and b"committed" in L.vx_last_error()
-        assert out.tobytes() == sentinel
-    finally:
-        fresh.close()
+    refusals = ((lambda: L.vx_block_points(h, vp(pts.ctypes.data), 8, 8, hip.VX_MEM_HOST, o), b"pos_stride"),
+                (lambda: L.vx_block_points(h, None, 12, 8, hip.VX_MEM_HOST, o), b"null pos"),
+                (lambda: L.vx_block_points(h, vp(pts.ctypes.data), 12, 8, 3, o), b"VX_MEM"),
+                (lambda: L.vx_read_region(h, None, C.byref(size3), hip.VX_MEM_HOST, o), b"null lo"),
+                (lambda: L.vx_read_region(h, C.byref(lo3), C.byref((C.c_uint32 * 3)(256, 256, 257)), hip.VX_MEM_HOST, o), b"size.x"))
+    uncommitted = (lambda ctx: L.vx_block_points(ctx, vp(pts.ctypes.data), 12, 8, hip.VX_MEM_HOST, vp(out.ctypes.data)),
+                   lambda ctx: L.vx_read_region(ctx, C.byref(lo3), C.byref(size3), hip.VX_MEM_HOST, vp(out.ctypes.data)))
+    nothing_to_do = (lambda: L.vx_block_points(h, None, 12, 0, hip.VX_MEM_HOST, None),
+                     lambda: L.vx_block_points(h, vp(pts.ctypes.data + 1), 5, 0, hip.VX_MEM_DEVICE, vp(out.ctypes.data + 3)),  # (no points: nothing to refuse)
+                     lambda: L.vx_read_region(h, C.byref(lo3), C.byref((C.c_uint32 * 3)(2, 0, 2)), hip.VX_MEM_DEVICE, None))
+    leaves_the_outputs_alone(case, [out], [], refusals, uncommitted, nothing_to_do)

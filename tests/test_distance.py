@@ -11,34 +11,17 @@ import pytest
 from batch_cases import _chunk_of
 from distance_cases import (ABSENT, DISTANCE_CASES, NONE, SEVENTEEN, SHAPE, TO_AIR, HostDistance, boxes_for, calls_for, differing, distance_truth, harness, in_form,
                             make_distance_case, pick_for, torch_boxes)
+from gpu_harness import (SENTINEL, big_esvo_context, field_rows, leaves_the_outputs_alone, make_context, records_head, sentinel_bytes, sentinel_words, shared_cases)
 from helpers import vra  # noqa: F401
 from label_cases import ROCK, RUBBLE_AT, SEEDED, SOLID_ROCK, rubble_blocks
 from voxel_rs_amd import hip
 
 pytestmark = pytest.mark.gpu
-SENTINEL = 0x5A5A5A5A
-TAIL = 48  # bytes behind the last field a call may write to, which it has to leave alone
-
-
-def make_context(c, capacity=None):
-    svo = hip.Svo(c.svo_type, c.world.size_in_bytes + (1 << 20) if capacity is None else capacity)
-    svo.set_materials(c.mats)
-    svo.set_textures(c.tex, 6)
-    svo.update_full(c.world)
-    return svo
-
-
-def filled_fields(count, stride):
-    """count fields at `stride` bytes and a tail, every byte 0x5a."""
-    import torch
-
-    return torch.full((count * stride + TAIL,), 0x5A, dtype=torch.uint8, device="cuda")
+filled_fields = sentinel_bytes  # (count, stride in bytes): the fields at their stride and the tail
 
 
 def filled_info(count):
-    import torch
-
-    return torch.full((count + 2, 4), SENTINEL, dtype=torch.int32, device="cuda")
+    return sentinel_words(count, 4)
 
 
 def check_device(fields, info, count, stride, expected, what):
@@ -47,15 +30,9 @@ def check_device(fields, info, count, stride, expected, what):
     exp_fields, exp_info = expected
     got_fields, got_info = exp_fields, exp_info
     if fields is not None:
-        raw = fields.cpu().numpy()
-        rows = raw[:count * stride].reshape(count, stride)
-        written = 2 * exp_fields.shape[1]
-        got_fields = np.ascontiguousarray(rows[:, :written]).view(np.uint16)
-        assert (rows[:, written:] == 0x5A).all() and (raw[count * stride:] == 0x5A).all(), what
+        got_fields = np.ascontiguousarray(field_rows(fields, count, stride, 2 * exp_fields.shape[1], what)).view(np.uint16)
     if info is not None:
-        raw = hip.distance_infos_to_numpy(info)
-        got_info = raw[:count]
-        assert (raw[count:].view(np.uint32) == SENTINEL).all(), what
+        got_info = records_head(hip.distance_infos_to_numpy(info), count, what)
     assert differing((got_fields, got_info), expected) is None, f"{what}: {differing((got_fields, got_info), expected)}"
 
 
@@ -70,33 +47,18 @@ def gpu_boxes(c, shape):
     return boxes_for(c, shape)[pick_for(c, shape)][gpu_pick(c, shape)]
 
 
-_CASES = {}
-
-
-def the_case(name, fmt):
+def build(name, fmt):
     """The world, a context that has it, the boxes the GPU is asked about and the harness's bytes for every call; shared by the tests."""
-    if (name, fmt) not in _CASES:
-        c = make_distance_case(name, fmt)
-        c.calls = calls_for(c)
-        host = HostDistance(harness(), c)
-        c.expected = {call[0]: host.call(c, call, gpu_pick(c, call[1])) for call in c.calls}
-        host.close()
-        c.svo = make_context(c)
-        _CASES[name, fmt] = c
-    return _CASES[name, fmt]
+    c = make_distance_case(name, fmt)
+    c.calls = calls_for(c)
+    host = HostDistance(harness(), c)
+    c.expected = {call[0]: host.call(c, call, gpu_pick(c, call[1])) for call in c.calls}
+    host.close()
+    c.svo = make_context(c)
+    return c
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _contexts():
-    yield
-    for c in _CASES.values():
-        c.svo.close()
-    _CASES.clear()
-
-
-@pytest.fixture(scope="module", params=DISTANCE_CASES, ids=[f"{n}-{f}" for n, f in DISTANCE_CASES])
-def case(request):
-    return the_case(*request.param)
+the_case, _contexts, case = shared_cases(build, DISTANCE_CASES)
 
 
 def asked(c, call, svo=None):
@@ -271,23 +233,11 @@ def test_a_commit_changes_the_field(fmt):
 def test_esvo_big():
     """`rubble` in an ESVO context of 4 GiB, which selects the VX_SVO_ESVO_BIG build of the kernel: every call."""
     c = the_case("rubble", "esvo")
-    h = C.c_void_p()
-    rc = hip.lib().vx_create(c.svo_type, 1 << 32, 0, C.byref(h))
-    if rc == 3:  # VX_ERR_OUT_OF_MEMORY, from vx_create itself: the one reason to skip (as tests/test_blocks.py::test_esvo_big)
-        pytest.skip("vx_create: " + hip.lib().vx_last_error().decode())
-    assert rc == 0, hip.lib().vx_last_error()
-    svo = hip.Svo.__new__(hip.Svo)
-    svo._h, svo.svo_type = h, c.svo_type
-    try:
-        svo.set_materials(c.mats)
-        svo.set_textures(c.tex, 6)
-        svo.update_full(c.world)
+    with big_esvo_context(c) as svo:
         queued = [asked(c, call, svo) for call in c.calls]
         svo.sync()
         for call, (lo, f, i, stride) in zip(c.calls, queued):
             check_device(f, i, len(lo), stride, c.expected[call[0]], call[0])
-    finally:
-        svo.close()
 
 
 def test_errors_leave_the_output_alone(case):
@@ -298,8 +248,6 @@ def test_errors_leave_the_output_alone(case):
     L, h, vp = hip.lib(), case.svo._h, C.c_void_p
     fields = np.full(2 * 8192 + 16, 0x5A, dtype=np.uint8)
     info = np.full(3, SENTINEL, dtype=np.uint32).repeat(4)
-    everything = lambda: fields.tobytes() + info.tobytes()
-    sentinel = everything()
     d_fields, d_info = filled_fields(2, 8192), filled_info(2)
     v = np.tile(np.array([3, 3, 3], dtype=np.int32), 8)
     d_v = torch.from_numpy(v).cuda()
@@ -316,48 +264,37 @@ def test_errors_leave_the_output_alone(case):
     hf, hi = vp(fields.ctypes.data), vp(info.ctypes.data)
     df, di = vp(d_fields.data_ptr()), vp(d_info.data_ptr())
     H, D = hip.VX_MEM_HOST, hip.VX_MEM_DEVICE
-    for call, word in ((lambda: L.vx_distance_boxes(None, hb, 12, 2, C.byref(shape()), H, hf, 0, hi), b"null context"),
-                       (lambda: L.vx_distance_boxes(h, hb, 12, 2, C.byref(shape()), 3, hf, 0, hi), b"VX_MEM"),
-                       (lambda: L.vx_distance_boxes(h, hb, 12, 2, None, H, hf, 0, hi), b"null shape"),
-                       (lambda: L.vx_distance_boxes(h, None, 12, 2, C.byref(shape()), H, hf, 0, hi), b"null lo"),
-                       (lambda: L.vx_distance_boxes(h, hb, 12, 2, C.byref(shape()), H, None, 0, None), b"fields and info are both null"),
-                       (lambda: L.vx_distance_boxes(h, hb, 8, 2, C.byref(shape()), H, hf, 0, hi), b"lo_stride"),
-                       (lambda: L.vx_distance_boxes(h, hb + 2, 12, 2, C.byref(shape()), H, hf, 0, hi), b"lo must be aligned"),
-                       (lambda: L.vx_distance_boxes(h, hb, 12, 2, C.byref(shape(size=u3(16, 0, 16))), H, hf, 0, hi), b"size"),
-                       (lambda: L.vx_distance_boxes(h, hb, 12, 2, C.byref(shape(size=u3(16, 16, 33))), H, hf, 0, hi), b"size"),
-                       (lambda: L.vx_distance_boxes(h, db, 12, 2, C.byref(shape(size=u3(33, 16, 16))), D, df, 0, di), b"size"),
-                       (lambda: L.vx_distance_boxes(h, hb, 12, 2, C.byref(shape(flags=2)), H, hf, 0, hi), b"flags"),
-                       (lambda: L.vx_distance_boxes(h, db, 12, 2, C.byref(shape(flags=3)), D, df, 0, di), b"flags"),
-                       (lambda: L.vx_distance_boxes(h, hb, 12, 2, C.byref(shape(pass_value=9, match_value=3)), H, hf, 0, hi), b"pass_value must be 0"),
-                       (lambda: L.vx_distance_boxes(h, db, 12, 2, C.byref(shape(pass_value=9, match_value=3)), D, df, 0, di), b"pass_value must be 0"),
-                       (lambda: L.vx_distance_boxes(h, hb, 12, 2, C.byref(shape()), H, hf, 8176, hi), b"field_stride"),
-                       (lambda: L.vx_distance_boxes(h, hb, 12, 2, C.byref(shape()), H, hf, 8200, hi), b"field_stride"),
-                       (lambda: L.vx_distance_boxes(h, db, 12, 2, C.byref(shape()), D, df, 4096, di), b"field_stride"),
-                       (lambda: L.vx_distance_boxes(h, hb, 12, (1 << 20) + 1, C.byref(shape()), H, None, 0, hi), b"count exceeds"),
-                       (lambda: L.vx_distance_boxes(h, hb, 12, 2049, C.byref(shape()), H, hf, 0, None), b"count * field_stride"),
-                       (lambda: L.vx_distance_boxes(h, hb, 12, 2, C.byref(shape()), H, hf, 0, vp(fields.ctypes.data + 8192)), b"fields overlaps info"),
-                       (lambda: L.vx_distance_boxes(h, db, 12, 2, C.byref(shape()), D, df, 0, vp(d_fields.data_ptr() + 64)), b"fields overlaps info"),
-                       (lambda: L.vx_distance_boxes(h, db, 12, 2, C.byref(shape()), D, None, 0, vp(db)), b"info overlaps lo"),
-                       (lambda: L.vx_distance_boxes(h, db, 12, 2, C.byref(shape()), D, vp(d_fields.data_ptr() + 8), 0, di), b"fields in device memory"),
-                       (lambda: L.vx_distance_boxes(h, db, 12, 2, C.byref(shape()), D, df, 0, vp(d_info.data_ptr() + 4)), b"info in device memory"),
-                       (lambda: L.vx_distance_boxes(h, db + 1, 12, 2, C.byref(shape()), D, df, 0, di), b"lo must be aligned")):
-        rc = call()
-        assert rc == 1 and word in L.vx_last_error(), (rc, word, L.vx_last_error())
-        assert everything() == sentinel
-    fresh = hip.Svo(case.svo_type, 1 << 20)
-    try:
-        assert L.vx_distance_boxes(fresh._h, hb, 12, 2, C.byref(shape()), H, hf, 0, hi) == 6 and b"committed" in L.vx_last_error()
-        assert L.vx_distance_boxes(fresh._h, db, 12, 2, C.byref(shape()), D, df, 0, di) == 6
-        assert everything() == sentinel
-    finally:
-        fresh.close()
+    refusals = ((lambda: L.vx_distance_boxes(None, hb, 12, 2, C.byref(shape()), H, hf, 0, hi), b"null context"),
+                (lambda: L.vx_distance_boxes(h, hb, 12, 2, C.byref(shape()), 3, hf, 0, hi), b"VX_MEM"),
+                (lambda: L.vx_distance_boxes(h, hb, 12, 2, None, H, hf, 0, hi), b"null shape"),
+                (lambda: L.vx_distance_boxes(h, None, 12, 2, C.byref(shape()), H, hf, 0, hi), b"null lo"),
+                (lambda: L.vx_distance_boxes(h, hb, 12, 2, C.byref(shape()), H, None, 0, None), b"fields and info are both null"),
+                (lambda: L.vx_distance_boxes(h, hb, 8, 2, C.byref(shape()), H, hf, 0, hi), b"lo_stride"),
+                (lambda: L.vx_distance_boxes(h, hb + 2, 12, 2, C.byref(shape()), H, hf, 0, hi), b"lo must be aligned"),
+                (lambda: L.vx_distance_boxes(h, hb, 12, 2, C.byref(shape(size=u3(16, 0, 16))), H, hf, 0, hi), b"size"),
+                (lambda: L.vx_distance_boxes(h, hb, 12, 2, C.byref(shape(size=u3(16, 16, 33))), H, hf, 0, hi), b"size"),
+                (lambda: L.vx_distance_boxes(h, db, 12, 2, C.byref(shape(size=u3(33, 16, 16))), D, df, 0, di), b"size"),
+                (lambda: L.vx_distance_boxes(h, hb, 12, 2, C.byref(shape(flags=2)), H, hf, 0, hi), b"flags"),
+                (lambda: L.vx_distance_boxes(h, db, 12, 2, C.byref(shape(flags=3)), D, df, 0, di), b"flags"),
+                (lambda: L.vx_distance_boxes(h, hb, 12, 2, C.byref(shape(pass_value=9, match_value=3)), H, hf, 0, hi), b"pass_value must be 0"),
+                (lambda: L.vx_distance_boxes(h, db, 12, 2, C.byref(shape(pass_value=9, match_value=3)), D, df, 0, di), b"pass_value must be 0"),
+                (lambda: L.vx_distance_boxes(h, hb, 12, 2, C.byref(shape()), H, hf, 8176, hi), b"field_stride"),
+                (lambda: L.vx_distance_boxes(h, hb, 12, 2, C.byref(shape()), H, hf, 8200, hi), b"field_stride"),
+                (lambda: L.vx_distance_boxes(h, db, 12, 2, C.byref(shape()), D, df, 4096, di), b"field_stride"),
+                (lambda: L.vx_distance_boxes(h, hb, 12, (1 << 20) + 1, C.byref(shape()), H, None, 0, hi), b"count exceeds"),
+                (lambda: L.vx_distance_boxes(h, hb, 12, 2049, C.byref(shape()), H, hf, 0, None), b"count * field_stride"),
+                (lambda: L.vx_distance_boxes(h, hb, 12, 2, C.byref(shape()), H, hf, 0, vp(fields.ctypes.data + 8192)), b"fields overlaps info"),
+                (lambda: L.vx_distance_boxes(h, db, 12, 2, C.byref(shape()), D, df, 0, vp(d_fields.data_ptr() + 64)), b"fields overlaps info"),
+                (lambda: L.vx_distance_boxes(h, db, 12, 2, C.byref(shape()), D, None, 0, vp(db)), b"info overlaps lo"),
+                (lambda: L.vx_distance_boxes(h, db, 12, 2, C.byref(shape()), D, vp(d_fields.data_ptr() + 8), 0, di), b"fields in device memory"),
+                (lambda: L.vx_distance_boxes(h, db, 12, 2, C.byref(shape()), D, df, 0, vp(d_info.data_ptr() + 4)), b"info in device memory"),
+                (lambda: L.vx_distance_boxes(h, db + 1, 12, 2, C.byref(shape()), D, df, 0, di), b"lo must be aligned"))
+    uncommitted = (lambda ctx: L.vx_distance_boxes(ctx, hb, 12, 2, C.byref(shape()), H, hf, 0, hi), lambda ctx: L.vx_distance_boxes(ctx, db, 12, 2, C.byref(shape()), D, df, 0, di))
     # count == 0: VX_OK whatever the rest is; nothing is read or written
-    assert L.vx_distance_boxes(h, hb, 12, 0, C.byref(shape()), H, hf, 0, hi) == 0
-    assert L.vx_distance_boxes(h, None, 0, 0, None, H, None, 0, None) == 0
-    assert L.vx_distance_boxes(h, db, 12, 0, C.byref(shape(flags=7)), D, df, 0, di) == 0
-    case.svo.sync()
-    assert everything() == sentinel
-    assert (d_fields.cpu().numpy() == 0x5A).all() and (d_info.cpu().numpy().view(np.uint32) == SENTINEL).all()
+    nothing_to_do = (lambda: L.vx_distance_boxes(h, hb, 12, 0, C.byref(shape()), H, hf, 0, hi),
+                     lambda: L.vx_distance_boxes(h, None, 0, 0, None, H, None, 0, None),
+                     lambda: L.vx_distance_boxes(h, db, 12, 0, C.byref(shape(flags=7)), D, df, 0, di))
+    leaves_the_outputs_alone(case, [fields, info], [d_fields, d_info], refusals, uncommitted, nothing_to_do)
     # and the call still works: two boxes at (3, 3, 3), as numpy has them
     assert L.vx_distance_boxes(h, hb, 12, 2, C.byref(shape()), H, hf, 0, hi) == 0
     exp_fields, exp_info = distance_truth(case, v[:6].reshape(2, 3), (16, 16, 16))

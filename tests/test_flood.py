@@ -10,74 +10,41 @@ import pytest
 from batch_cases import _chunk_of
 from flood_cases import (BLOCKED, FLOOD_CASES, INVALID, MAX_STEPS, SEEDED, SHAPE, HostFlood, burrow_blocks, calls_for, differing, harness, in_form, make_flood_case,
                          points_truth, positions_for, torch_positions)
+from gpu_harness import (SENTINEL, big_esvo_context, field_rows, flying_entities, leaves_the_outputs_alone, make_context, records_head, sentinel_bytes,
+                         sentinel_words, shared_cases)
 from helpers import vra  # noqa: F401
 from physics_cases import DT
 from voxel_rs_amd import hip
 
 pytestmark = pytest.mark.gpu
-SENTINEL = 0x5A5A5A5A
-TAIL = 48  # bytes behind the last field a call may write to, which it has to leave alone
-
-
-def make_context(c, capacity=None):
-    svo = hip.Svo(c.svo_type, c.world.size_in_bytes + (1 << 20) if capacity is None else capacity)
-    svo.set_materials(c.mats)
-    svo.set_textures(c.tex, 6)
-    svo.update_full(c.world)
-    return svo
-
-
-def filled_fields(count, stride):
-    import torch
-
-    return torch.full((count * stride + TAIL,), 0x5A, dtype=torch.uint8, device="cuda")
+filled_fields = sentinel_bytes  # (count, stride): the fields at their stride and the tail
 
 
 def filled_info(count):
-    import torch
-
-    return torch.full((count + 2, 4), SENTINEL, dtype=torch.int32, device="cuda")
+    return sentinel_words(count, 4)
 
 
 def check_device(fields, info, count, stride, exp_fields, exp_info, what):
     """Buffers longer than the call needs: the fields at their stride with the sentinel between and behind them, the records and two more.
     info None: a call that was given no records."""
-    got_info = exp_info if info is None else hip.flood_infos_to_numpy(info)
-    got = fields.cpu().numpy()
-    rows = got[:count * stride].reshape(count, stride)
-    written = exp_fields.shape[1]
-    assert differing(rows[:, :written], got_info[:count], exp_fields, exp_info) is None, f"{what}: {differing(rows[:, :written], got_info[:count], exp_fields, exp_info)}"
-    assert (rows[:, written:] == 0x5A).all() and (got[count * stride:] == 0x5A).all() and (got_info[count:].view(np.uint32) == SENTINEL).all(), what
+    got_fields = field_rows(fields, count, stride, exp_fields.shape[1], what)
+    got_info = exp_info if info is None else records_head(hip.flood_infos_to_numpy(info), count, what)
+    assert differing(got_fields, got_info, exp_fields, exp_info) is None, f"{what}: {differing(got_fields, got_info, exp_fields, exp_info)}"
 
 
-_CASES = {}
-
-
-def the_case(name, fmt):
+def build(name, fmt):
     """The world, a context that has it, the positions the GPU is asked about and the harness's bytes for every call; shared by the tests."""
-    if (name, fmt) not in _CASES:
-        c = make_flood_case(name, fmt)
-        c.pick = np.concatenate([np.arange(100), np.arange(SEEDED, len(c.positions))])
-        c.calls = calls_for(c)
-        host = HostFlood(harness(), c)
-        c.expected = {call[0]: host.call(c, call, c.pick) for call in c.calls}
-        host.close()
-        c.svo = make_context(c)
-        _CASES[name, fmt] = c
-    return _CASES[name, fmt]
+    c = make_flood_case(name, fmt)
+    c.pick = np.concatenate([np.arange(100), np.arange(SEEDED, len(c.positions))])
+    c.calls = calls_for(c)
+    host = HostFlood(harness(), c)
+    c.expected = {call[0]: host.call(c, call, c.pick) for call in c.calls}
+    host.close()
+    c.svo = make_context(c)
+    return c
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _contexts():
-    yield
-    for c in _CASES.values():
-        c.svo.close()
-    _CASES.clear()
-
-
-@pytest.fixture(scope="module", params=FLOOD_CASES, ids=[f"{n}-{f}" for n, f in FLOOD_CASES])
-def case(request):
-    return the_case(*request.param)
+the_case, _contexts, case = shared_cases(build, FLOOD_CASES)
 
 
 def test_device_and_host_memory_give_the_harness_bytes(case):
@@ -120,7 +87,7 @@ def test_outputs_and_strides(case):
     svo.sync()
     assert f_only[1] is None and i_only[0] is None
     check_device(f_only[0], None, n, shape.padded, exp_fields, exp_info, "fields only")
-    assert hip.flood_infos_to_numpy(i_only[1])[:n].tobytes() == exp_info.tobytes() and (hip.flood_infos_to_numpy(i_only[1])[n:].view(np.uint32) == SENTINEL).all()
+    assert records_head(hip.flood_infos_to_numpy(i_only[1]), n, "records only").tobytes() == exp_info.tobytes()
     check_device(both[0], both[1], n, wide, exp_fields, exp_info, "a stride larger than the box")
     check_device(one[0], one[1], 1, shape.padded, exp_fields[7:8], exp_info[7:8], "one query")
     check_device(none[0], none[1], 0, shape.padded, exp_fields[:0], exp_info[:0], "no query")
@@ -163,11 +130,7 @@ def test_behind_physics_step(fmt):
 
     c = the_case("glasshouse", fmt)
     rng = np.random.default_rng(91)
-    e = np.zeros(256, dtype=hip.ENTITY_DTYPE)
-    e["position"] = rng.uniform((2.0, 2.0, 2.0), (30.0, 14.0, 30.0), (256, 3))
-    e["velocity"] = np.stack([rng.uniform(-30, 30, len(e)), np.full(len(e), -40.0), rng.uniform(-30, 30, len(e))], axis=1)
-    e["aabb_offset"], e["aabb_extents"] = (-0.4, 0.0, -0.4), (0.8, 1.8, 0.8)
-    e["gravity"], e["max_fall_velocity"], e["flags"] = 20.0, 50.0, hip.ENTITY_FLYING
+    e = flying_entities(256, rng.uniform((2.0, 2.0, 2.0), (30.0, 14.0, 30.0), (256, 3)), rng)
     shape = SHAPE["17"]
     d = torch.from_numpy(e.view(np.uint8).copy()).cuda()
     c.svo.physics_step(d, DT, 8)
@@ -219,18 +182,7 @@ def test_a_commit_opens_the_sealed_room(fmt):
 def test_esvo_big():
     """The glasshouse in an ESVO context of 4 GiB, which selects the VX_SVO_ESVO_BIG build of the kernel: every call."""
     c = the_case("glasshouse", "esvo")
-    h = C.c_void_p()
-    rc = hip.lib().vx_create(c.svo_type, 1 << 32, 0, C.byref(h))
-    if rc == 3:  # VX_ERR_OUT_OF_MEMORY, from vx_create itself: the one reason to skip (as tests/test_blocks.py::test_esvo_big)
-        pytest.skip("vx_create: " + hip.lib().vx_last_error().decode())
-    assert rc == 0, hip.lib().vx_last_error()
-    svo = hip.Svo.__new__(hip.Svo)
-    svo._h, svo.svo_type = h, c.svo_type
-    try:
-        svo.set_materials(c.mats)
-        svo.set_textures(c.tex, 6)
-        svo.update_full(c.world)
-        assert svo.get_stats()["capacity_bytes"] == 1 << 32
+    with big_esvo_context(c) as svo:
         n, queued = len(c.pick), []
         for name, shape, max_steps, pass_value, flags, form in c.calls:
             raw, stride, view = in_form(positions_for(c, shape)[c.pick], form)
@@ -243,8 +195,6 @@ def test_esvo_big():
         _, _, view = in_form(positions_for(c, shape)[c.pick], form)
         hf, hi = svo.flood_points(view, shape.size, shape.seed_at, max_steps, pass_value, flags)
         assert differing(hf, hi, *c.expected[name]) is None
-    finally:
-        svo.close()
 
 
 def test_errors_leave_the_output_alone(case):
@@ -255,7 +205,6 @@ def test_errors_leave_the_output_alone(case):
     L, h, vp = hip.lib(), case.svo._h, C.c_void_p
     fields = np.full(2 * 4928 + 16, 0x5A, dtype=np.uint8)
     info = np.full(3, SENTINEL, dtype=np.uint32).repeat(4)
-    sentinel = fields.tobytes() + info.tobytes()
     d_fields, d_info = filled_fields(2, 4928), filled_info(2)
     v = np.tile(np.array([3.5, 3.5, 3.5], dtype=np.float32), 8)
     d_v = torch.from_numpy(v).cuda()
@@ -271,42 +220,31 @@ def test_errors_leave_the_output_alone(case):
     hb, db = v.ctypes.data, d_v.data_ptr()
     hf, hi, df, di = vp(fields.ctypes.data), vp(info.ctypes.data), vp(d_fields.data_ptr()), vp(d_info.data_ptr())
     H, D = hip.VX_MEM_HOST, hip.VX_MEM_DEVICE
-    for call, word in ((lambda: L.vx_flood_points(None, hb, 12, 2, C.byref(shape()), H, hf, 0, hi), b"null context"),
-                       (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape()), 3, hf, 0, hi), b"VX_MEM"),
-                       (lambda: L.vx_flood_points(h, hb, 12, 2, None, H, hf, 0, hi), b"null shape"),
-                       (lambda: L.vx_flood_points(h, None, 12, 2, C.byref(shape()), H, hf, 0, hi), b"null pos"),
-                       (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape()), H, None, 0, None), b"fields and info"),
-                       (lambda: L.vx_flood_points(h, hb, 8, 2, C.byref(shape()), H, hf, 0, hi), b"pos_stride"),
-                       (lambda: L.vx_flood_points(h, hb + 2, 12, 2, C.byref(shape()), H, hf, 0, hi), b"pos must be aligned"),
-                       (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape(size=u3(17, 0, 17), seed_at=u3(8, 0, 8))), H, hf, 0, hi), b"size"),
-                       (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape(size=u3(17, 17, 33))), H, hf, 0, hi), b"size"),
-                       (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape(seed_at=u3(17, 8, 8))), H, hf, 0, hi), b"seed_at"),
-                       (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape(max_steps=251)), H, hf, 0, hi), b"max_steps"),
-                       (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape(flags=2)), H, hf, 0, hi), b"flags"),
-                       (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape()), H, hf, 4912, hi), b"field_stride"),
-                       (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape()), H, hf, 4936, hi), b"field_stride"),
-                       (lambda: L.vx_flood_points(h, hb, 12, (1 << 24) + 1, C.byref(shape()), H, None, 0, hi), b"count exceeds"),
-                       (lambda: L.vx_flood_points(h, hb, 12, 3405, C.byref(shape()), H, hf, 0, hi), b"count * field_stride"),
-                       (lambda: L.vx_flood_points(h, db, 12, 2, C.byref(shape()), D, vp(d_fields.data_ptr() + 8), 0, di), b"fields in device memory"),
-                       (lambda: L.vx_flood_points(h, db, 12, 2, C.byref(shape()), D, df, 0, vp(d_info.data_ptr() + 4)), b"info in device memory"),
-                       (lambda: L.vx_flood_points(h, db + 1, 12, 2, C.byref(shape()), D, df, 0, di), b"pos must be aligned")):
-        rc = call()
-        assert rc == 1 and word in L.vx_last_error(), (rc, word, L.vx_last_error())
-        assert fields.tobytes() + info.tobytes() == sentinel
-    fresh = hip.Svo(case.svo_type, 1 << 20)
-    try:
-        assert L.vx_flood_points(fresh._h, hb, 12, 2, C.byref(shape()), H, hf, 0, hi) == 6 and b"committed" in L.vx_last_error()
-        assert L.vx_flood_points(fresh._h, db, 12, 2, C.byref(shape()), D, df, 0, di) == 6
-        assert fields.tobytes() + info.tobytes() == sentinel
-    finally:
-        fresh.close()
+    refusals = ((lambda: L.vx_flood_points(None, hb, 12, 2, C.byref(shape()), H, hf, 0, hi), b"null context"),
+                (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape()), 3, hf, 0, hi), b"VX_MEM"),
+                (lambda: L.vx_flood_points(h, hb, 12, 2, None, H, hf, 0, hi), b"null shape"),
+                (lambda: L.vx_flood_points(h, None, 12, 2, C.byref(shape()), H, hf, 0, hi), b"null pos"),
+                (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape()), H, None, 0, None), b"fields and info"),
+                (lambda: L.vx_flood_points(h, hb, 8, 2, C.byref(shape()), H, hf, 0, hi), b"pos_stride"),
+                (lambda: L.vx_flood_points(h, hb + 2, 12, 2, C.byref(shape()), H, hf, 0, hi), b"pos must be aligned"),
+                (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape(size=u3(17, 0, 17), seed_at=u3(8, 0, 8))), H, hf, 0, hi), b"size"),
+                (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape(size=u3(17, 17, 33))), H, hf, 0, hi), b"size"),
+                (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape(seed_at=u3(17, 8, 8))), H, hf, 0, hi), b"seed_at"),
+                (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape(max_steps=251)), H, hf, 0, hi), b"max_steps"),
+                (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape(flags=2)), H, hf, 0, hi), b"flags"),
+                (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape()), H, hf, 4912, hi), b"field_stride"),
+                (lambda: L.vx_flood_points(h, hb, 12, 2, C.byref(shape()), H, hf, 4936, hi), b"field_stride"),
+                (lambda: L.vx_flood_points(h, hb, 12, (1 << 24) + 1, C.byref(shape()), H, None, 0, hi), b"count exceeds"),
+                (lambda: L.vx_flood_points(h, hb, 12, 3405, C.byref(shape()), H, hf, 0, hi), b"count * field_stride"),
+                (lambda: L.vx_flood_points(h, db, 12, 2, C.byref(shape()), D, vp(d_fields.data_ptr() + 8), 0, di), b"fields in device memory"),
+                (lambda: L.vx_flood_points(h, db, 12, 2, C.byref(shape()), D, df, 0, vp(d_info.data_ptr() + 4)), b"info in device memory"),
+                (lambda: L.vx_flood_points(h, db + 1, 12, 2, C.byref(shape()), D, df, 0, di), b"pos must be aligned"))
+    uncommitted = (lambda ctx: L.vx_flood_points(ctx, hb, 12, 2, C.byref(shape()), H, hf, 0, hi), lambda ctx: L.vx_flood_points(ctx, db, 12, 2, C.byref(shape()), D, df, 0, di))
     # count == 0: VX_OK whatever the rest is; nothing is read or written
-    assert L.vx_flood_points(h, hb, 12, 0, C.byref(shape()), H, hf, 0, hi) == 0
-    assert L.vx_flood_points(h, None, 0, 0, None, H, None, 0, None) == 0
-    assert L.vx_flood_points(h, db, 12, 0, C.byref(shape()), D, df, 0, di) == 0
-    case.svo.sync()
-    assert fields.tobytes() + info.tobytes() == sentinel
-    assert (d_fields.cpu().numpy() == 0x5A).all() and (d_info.cpu().numpy().view(np.uint32) == SENTINEL).all()
+    nothing_to_do = (lambda: L.vx_flood_points(h, hb, 12, 0, C.byref(shape()), H, hf, 0, hi),
+                     lambda: L.vx_flood_points(h, None, 0, 0, None, H, None, 0, None),
+                     lambda: L.vx_flood_points(h, db, 12, 0, C.byref(shape()), D, df, 0, di))
+    leaves_the_outputs_alone(case, [fields, info], [d_fields, d_info], refusals, uncommitted, nothing_to_do)
     # and the call still works: two queries at (3.5, 3.5, 3.5), as numpy has them
     assert L.vx_flood_points(h, hb, 12, 2, C.byref(shape()), H, hf, 0, hi) == 0
     exp_fields, exp_info = points_truth(case, v[:6].reshape(2, 3), SHAPE["17"], 250)

@@ -9,40 +9,22 @@ import numpy as np
 import pytest
 
 from batch_cases import _chunk_of
+from gpu_harness import (SENTINEL, big_esvo_context, field_rows, leaves_the_outputs_alone, make_context, records_head, sentinel_bytes, sentinel_words, shared_cases)
 from helpers import vra  # noqa: F401
 from label_cases import (ALL_FACES, CUT, LABEL_CASES, LINK, MAX_PIECES, ROCK, RUBBLE_AT, RUBBLE_NAMED, SEEDED, SEVENTEEN, SHAPE, SOLID_ROCK, HostLabel, boxes_for,
                          calls_for, differing, harness, in_form, label_truth, make_label_case, rubble_blocks, torch_boxes)
 from voxel_rs_amd import hip
 
 pytestmark = pytest.mark.gpu
-SENTINEL = 0x5A5A5A5A
-TAIL = 48  # bytes behind the last field a call may write to, which it has to leave alone
-
-
-def make_context(c, capacity=None):
-    svo = hip.Svo(c.svo_type, c.world.size_in_bytes + (1 << 20) if capacity is None else capacity)
-    svo.set_materials(c.mats)
-    svo.set_textures(c.tex, 6)
-    svo.update_full(c.world)
-    return svo
-
-
-def filled_fields(count, stride):
-    import torch
-
-    return torch.full((count * stride + TAIL,), 0x5A, dtype=torch.uint8, device="cuda")
+filled_fields = sentinel_bytes  # (count, stride): the fields at their stride and the tail
 
 
 def filled_pieces(count, most):
-    import torch
-
-    return torch.full((count * most + 2, 4), SENTINEL, dtype=torch.int32, device="cuda")
+    return sentinel_words(count * most, 4)
 
 
 def filled_info(count):
-    import torch
-
-    return torch.full((count + 2, 8), SENTINEL, dtype=torch.int32, device="cuda")
+    return sentinel_words(count, 8)
 
 
 def check_device(fields, pieces, info, count, stride, most, expected, what):
@@ -51,18 +33,11 @@ def check_device(fields, pieces, info, count, stride, most, expected, what):
     exp_fields, exp_pieces, exp_info = expected
     got_fields, got_pieces, got_info = exp_fields, exp_pieces, exp_info
     if fields is not None:
-        raw = fields.cpu().numpy()
-        rows = raw[:count * stride].reshape(count, stride)
-        got_fields = rows[:, :exp_fields.shape[1]]
-        assert (rows[:, exp_fields.shape[1]:] == 0x5A).all() and (raw[count * stride:] == 0x5A).all(), what
+        got_fields = field_rows(fields, count, stride, exp_fields.shape[1], what)
     if pieces is not None:
-        raw = pieces.cpu().numpy().view(np.uint32)
-        got_pieces = np.ascontiguousarray(raw[:count * most]).view(hip.LABEL_PIECE_DTYPE).reshape(count, most)
-        assert (raw[count * most:] == SENTINEL).all(), what
+        got_pieces = np.ascontiguousarray(records_head(pieces, count * most, what)).view(hip.LABEL_PIECE_DTYPE).reshape(count, most)
     if info is not None:
-        raw = hip.label_infos_to_numpy(info)
-        got_info = raw[:count]
-        assert (raw[count:].view(np.uint32) == SENTINEL).all(), what
+        got_info = records_head(hip.label_infos_to_numpy(info), count, what)
     assert differing((got_fields, got_pieces, got_info), expected) is None, f"{what}: {differing((got_fields, got_pieces, got_info), expected)}"
 
 
@@ -73,34 +48,19 @@ def gpu_calls(c):
     return [call for call in calls_for(c) if "0x" in call[0] or call[0] in keep]
 
 
-_CASES = {}
-
-
-def the_case(name, fmt):
+def build(name, fmt):
     """The world, a context that has it, the boxes the GPU is asked about and the harness's bytes for every call; shared by the tests."""
-    if (name, fmt) not in _CASES:
-        c = make_label_case(name, fmt)
-        c.pick = np.concatenate([np.arange(14), np.arange(SEEDED - 26, SEEDED), np.arange(SEEDED, len(c.boxes))])
-        c.calls = gpu_calls(c)
-        host = HostLabel(harness(), c)
-        c.expected = {call[0]: host.call(c, call, c.pick) for call in c.calls}
-        host.close()
-        c.svo = make_context(c)
-        _CASES[name, fmt] = c
-    return _CASES[name, fmt]
+    c = make_label_case(name, fmt)
+    c.pick = np.concatenate([np.arange(14), np.arange(SEEDED - 26, SEEDED), np.arange(SEEDED, len(c.boxes))])
+    c.calls = gpu_calls(c)
+    host = HostLabel(harness(), c)
+    c.expected = {call[0]: host.call(c, call, c.pick) for call in c.calls}
+    host.close()
+    c.svo = make_context(c)
+    return c
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _contexts():
-    yield
-    for c in _CASES.values():
-        c.svo.close()
-    _CASES.clear()
-
-
-@pytest.fixture(scope="module", params=LABEL_CASES, ids=[f"{n}-{f}" for n, f in LABEL_CASES])
-def case(request):
-    return the_case(*request.param)
+the_case, _contexts, case = shared_cases(build, LABEL_CASES)
 
 
 def asked(c, call, svo=None):
@@ -266,24 +226,12 @@ def test_commits_change_the_pieces(fmt):
 def test_esvo_big():
     """`rubble` in an ESVO context of 4 GiB, which selects the VX_SVO_ESVO_BIG build of the kernel: every call."""
     c = the_case("rubble", "esvo")
-    h = C.c_void_p()
-    rc = hip.lib().vx_create(c.svo_type, 1 << 32, 0, C.byref(h))
-    if rc == 3:  # VX_ERR_OUT_OF_MEMORY, from vx_create itself: the one reason to skip (as tests/test_blocks.py::test_esvo_big)
-        pytest.skip("vx_create: " + hip.lib().vx_last_error().decode())
-    assert rc == 0, hip.lib().vx_last_error()
-    svo = hip.Svo.__new__(hip.Svo)
-    svo._h, svo.svo_type = h, c.svo_type
-    try:
-        svo.set_materials(c.mats)
-        svo.set_textures(c.tex, 6)
-        svo.update_full(c.world)
+    with big_esvo_context(c) as svo:
         n = len(c.pick)
         queued = [asked(c, call, svo) for call in c.calls]
         svo.sync()
         for call, (_, f, p, i) in zip(c.calls, queued):
             check_device(f, p, i, n, call[1].padded, call[3], c.expected[call[0]], call[0])
-    finally:
-        svo.close()
 
 
 def test_errors_leave_the_output_alone(case):
@@ -295,8 +243,6 @@ def test_errors_leave_the_output_alone(case):
     fields = np.full(2 * 4096 + 16, 0x5A, dtype=np.uint8)
     pieces = np.full(2 * 4 + 1, SENTINEL, dtype=np.uint32).repeat(4)
     info = np.full(3, SENTINEL, dtype=np.uint32).repeat(8)
-    everything = lambda: fields.tobytes() + pieces.tobytes() + info.tobytes()
-    sentinel = everything()
     d_fields, d_pieces, d_info = filled_fields(2, 4096), filled_pieces(2, 4), filled_info(2)
     v = np.tile(np.array([3, 3, 3], dtype=np.int32), 8)
     d_v = torch.from_numpy(v).cuda()
@@ -313,49 +259,38 @@ def test_errors_leave_the_output_alone(case):
     hf, hp, hi = vp(fields.ctypes.data), vp(pieces.ctypes.data), vp(info.ctypes.data)
     df, dp, di = vp(d_fields.data_ptr()), vp(d_pieces.data_ptr()), vp(d_info.data_ptr())
     H, D = hip.VX_MEM_HOST, hip.VX_MEM_DEVICE
-    for call, word in ((lambda: L.vx_label_boxes(None, hb, 12, 2, C.byref(shape()), H, hf, 0, hp, hi), b"null context"),
-                       (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape()), 3, hf, 0, hp, hi), b"VX_MEM"),
-                       (lambda: L.vx_label_boxes(h, hb, 12, 2, None, H, hf, 0, hp, hi), b"null shape"),
-                       (lambda: L.vx_label_boxes(h, None, 12, 2, C.byref(shape()), H, hf, 0, hp, hi), b"null lo"),
-                       (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape()), H, None, 0, None, None), b"fields, pieces and info"),
-                       (lambda: L.vx_label_boxes(h, hb, 8, 2, C.byref(shape()), H, hf, 0, hp, hi), b"lo_stride"),
-                       (lambda: L.vx_label_boxes(h, hb + 2, 12, 2, C.byref(shape()), H, hf, 0, hp, hi), b"lo must be aligned"),
-                       (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape(size=u3(16, 0, 16))), H, hf, 0, hp, hi), b"size"),
-                       (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape(size=u3(16, 16, 33))), H, hf, 0, hp, hi), b"size"),
-                       (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape(anchor_faces=0x40)), H, hf, 0, hp, hi), b"anchor_faces"),
-                       (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape(max_pieces=251)), H, hf, 0, hp, hi), b"max_pieces"),
-                       (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape(max_pieces=0)), H, hf, 0, hp, hi), b"pieces with max_pieces == 0"),
-                       (lambda: L.vx_label_boxes(h, db, 12, 2, C.byref(shape(max_pieces=0)), D, df, 0, dp, di), b"pieces with max_pieces == 0"),
-                       (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape(max_steps=4097)), H, hf, 0, hp, hi), b"max_steps"),
-                       (lambda: L.vx_label_boxes(h, db, 12, 2, C.byref(shape(max_steps=4097)), D, df, 0, dp, di), b"max_steps"),
-                       (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape(flags=1)), H, hf, 0, hp, hi), b"flags"),
-                       (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape()), H, hf, 4080, hp, hi), b"field_stride"),
-                       (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape()), H, hf, 4104, hp, hi), b"field_stride"),
-                       (lambda: L.vx_label_boxes(h, hb, 12, (1 << 20) + 1, C.byref(shape()), H, None, 0, None, hi), b"count exceeds"),
-                       (lambda: L.vx_label_boxes(h, hb, 12, 4097, C.byref(shape()), H, hf, 0, None, hi), b"count * field_stride"),
-                       (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape()), H, hf, 0, vp(fields.ctypes.data + 4096), hi), b"fields overlaps pieces"),
-                       (lambda: L.vx_label_boxes(h, db, 12, 2, C.byref(shape()), D, df, 0, dp, vp(d_pieces.data_ptr() + 64)), b"pieces overlaps info"),
-                       (lambda: L.vx_label_boxes(h, db, 12, 2, C.byref(shape()), D, vp(d_fields.data_ptr() + 8), 0, dp, di), b"fields in device memory"),
-                       (lambda: L.vx_label_boxes(h, db, 12, 2, C.byref(shape()), D, df, 0, vp(d_pieces.data_ptr() + 8), di), b"pieces in device memory"),
-                       (lambda: L.vx_label_boxes(h, db, 12, 2, C.byref(shape()), D, df, 0, dp, vp(d_info.data_ptr() + 4)), b"info in device memory"),
-                       (lambda: L.vx_label_boxes(h, db + 1, 12, 2, C.byref(shape()), D, df, 0, dp, di), b"lo must be aligned")):
-        rc = call()
-        assert rc == 1 and word in L.vx_last_error(), (rc, word, L.vx_last_error())
-        assert everything() == sentinel
-    fresh = hip.Svo(case.svo_type, 1 << 20)
-    try:
-        assert L.vx_label_boxes(fresh._h, hb, 12, 2, C.byref(shape()), H, hf, 0, hp, hi) == 6 and b"committed" in L.vx_last_error()
-        assert L.vx_label_boxes(fresh._h, db, 12, 2, C.byref(shape()), D, df, 0, dp, di) == 6
-        assert everything() == sentinel
-    finally:
-        fresh.close()
+    refusals = ((lambda: L.vx_label_boxes(None, hb, 12, 2, C.byref(shape()), H, hf, 0, hp, hi), b"null context"),
+                (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape()), 3, hf, 0, hp, hi), b"VX_MEM"),
+                (lambda: L.vx_label_boxes(h, hb, 12, 2, None, H, hf, 0, hp, hi), b"null shape"),
+                (lambda: L.vx_label_boxes(h, None, 12, 2, C.byref(shape()), H, hf, 0, hp, hi), b"null lo"),
+                (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape()), H, None, 0, None, None), b"fields, pieces and info"),
+                (lambda: L.vx_label_boxes(h, hb, 8, 2, C.byref(shape()), H, hf, 0, hp, hi), b"lo_stride"),
+                (lambda: L.vx_label_boxes(h, hb + 2, 12, 2, C.byref(shape()), H, hf, 0, hp, hi), b"lo must be aligned"),
+                (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape(size=u3(16, 0, 16))), H, hf, 0, hp, hi), b"size"),
+                (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape(size=u3(16, 16, 33))), H, hf, 0, hp, hi), b"size"),
+                (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape(anchor_faces=0x40)), H, hf, 0, hp, hi), b"anchor_faces"),
+                (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape(max_pieces=251)), H, hf, 0, hp, hi), b"max_pieces"),
+                (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape(max_pieces=0)), H, hf, 0, hp, hi), b"pieces with max_pieces == 0"),
+                (lambda: L.vx_label_boxes(h, db, 12, 2, C.byref(shape(max_pieces=0)), D, df, 0, dp, di), b"pieces with max_pieces == 0"),
+                (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape(max_steps=4097)), H, hf, 0, hp, hi), b"max_steps"),
+                (lambda: L.vx_label_boxes(h, db, 12, 2, C.byref(shape(max_steps=4097)), D, df, 0, dp, di), b"max_steps"),
+                (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape(flags=1)), H, hf, 0, hp, hi), b"flags"),
+                (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape()), H, hf, 4080, hp, hi), b"field_stride"),
+                (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape()), H, hf, 4104, hp, hi), b"field_stride"),
+                (lambda: L.vx_label_boxes(h, hb, 12, (1 << 20) + 1, C.byref(shape()), H, None, 0, None, hi), b"count exceeds"),
+                (lambda: L.vx_label_boxes(h, hb, 12, 4097, C.byref(shape()), H, hf, 0, None, hi), b"count * field_stride"),
+                (lambda: L.vx_label_boxes(h, hb, 12, 2, C.byref(shape()), H, hf, 0, vp(fields.ctypes.data + 4096), hi), b"fields overlaps pieces"),
+                (lambda: L.vx_label_boxes(h, db, 12, 2, C.byref(shape()), D, df, 0, dp, vp(d_pieces.data_ptr() + 64)), b"pieces overlaps info"),
+                (lambda: L.vx_label_boxes(h, db, 12, 2, C.byref(shape()), D, vp(d_fields.data_ptr() + 8), 0, dp, di), b"fields in device memory"),
+                (lambda: L.vx_label_boxes(h, db, 12, 2, C.byref(shape()), D, df, 0, vp(d_pieces.data_ptr() + 8), di), b"pieces in device memory"),
+                (lambda: L.vx_label_boxes(h, db, 12, 2, C.byref(shape()), D, df, 0, dp, vp(d_info.data_ptr() + 4)), b"info in device memory"),
+                (lambda: L.vx_label_boxes(h, db + 1, 12, 2, C.byref(shape()), D, df, 0, dp, di), b"lo must be aligned"))
+    uncommitted = (lambda ctx: L.vx_label_boxes(ctx, hb, 12, 2, C.byref(shape()), H, hf, 0, hp, hi), lambda ctx: L.vx_label_boxes(ctx, db, 12, 2, C.byref(shape()), D, df, 0, dp, di))
     # count == 0: VX_OK whatever the rest is; nothing is read or written
-    assert L.vx_label_boxes(h, hb, 12, 0, C.byref(shape()), H, hf, 0, hp, hi) == 0
-    assert L.vx_label_boxes(h, None, 0, 0, None, H, None, 0, None, None) == 0
-    assert L.vx_label_boxes(h, db, 12, 0, C.byref(shape(flags=7)), D, df, 0, dp, di) == 0
-    case.svo.sync()
-    assert everything() == sentinel
-    assert (d_fields.cpu().numpy() == 0x5A).all() and (d_pieces.cpu().numpy().view(np.uint32) == SENTINEL).all() and (d_info.cpu().numpy().view(np.uint32) == SENTINEL).all()
+    nothing_to_do = (lambda: L.vx_label_boxes(h, hb, 12, 0, C.byref(shape()), H, hf, 0, hp, hi),
+                     lambda: L.vx_label_boxes(h, None, 0, 0, None, H, None, 0, None, None),
+                     lambda: L.vx_label_boxes(h, db, 12, 0, C.byref(shape(flags=7)), D, df, 0, dp, di))
+    leaves_the_outputs_alone(case, [fields, pieces, info], [d_fields, d_pieces, d_info], refusals, uncommitted, nothing_to_do)
     # and the call still works: two boxes at (3, 3, 3), as numpy has them
     assert L.vx_label_boxes(h, hb, 12, 2, C.byref(shape()), H, hf, 0, hp, hi) == 0
     exp_fields, exp_pieces, exp_info = label_truth(case, v[:6].reshape(2, 3), (16, 16, 16), max_pieces=4)

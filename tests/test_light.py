@@ -8,75 +8,41 @@ import numpy as np
 import pytest
 
 from batch_cases import _chunk_of
+from gpu_harness import (SENTINEL, big_esvo_context, field_rows, leaves_the_outputs_alone, make_context, records_head, sentinel_bytes, sentinel_words, shared_cases)
 from helpers import vra  # noqa: F401
 from light_cases import (LIGHT_CASES, NO_BLOCKS, NO_SKY, ROCK, SEEDED, SHAPE, SIXTEEN, HostLight, boxes_for, calls_for, differing, harness, in_form, lantern_blocks,
                          light_truth, make_light_case, torch_boxes)
 from voxel_rs_amd import hip
 
 pytestmark = pytest.mark.gpu
-SENTINEL = 0x5A5A5A5A
-TAIL = 48  # bytes behind the last field a call may write to, which it has to leave alone
-
-
-def make_context(c, capacity=None):
-    svo = hip.Svo(c.svo_type, c.world.size_in_bytes + (1 << 20) if capacity is None else capacity)
-    svo.set_materials(c.mats)
-    svo.set_textures(c.tex, 6)
-    svo.update_full(c.world)
-    return svo
-
-
-def filled_fields(count, stride):
-    import torch
-
-    return torch.full((count * stride + TAIL,), 0x5A, dtype=torch.uint8, device="cuda")
+filled_fields = sentinel_bytes  # (count, stride): the fields at their stride and the tail
 
 
 def filled_info(count):
-    import torch
-
-    return torch.full((count + 2, 4), SENTINEL, dtype=torch.int32, device="cuda")
+    return sentinel_words(count, 4)
 
 
 def check_device(fields, info, count, stride, exp_fields, exp_info, what):
     """Buffers longer than the call needs: the fields at their stride with the sentinel between and behind them, the records and two more.
     info None: a call that was given no records."""
-    got_info = exp_info if info is None else hip.light_infos_to_numpy(info)
-    got = fields.cpu().numpy()
-    rows = got[:count * stride].reshape(count, stride)
-    written = exp_fields.shape[1]
-    assert differing(rows[:, :written], got_info[:count], exp_fields, exp_info) is None, f"{what}: {differing(rows[:, :written], got_info[:count], exp_fields, exp_info)}"
-    assert (rows[:, written:] == 0x5A).all() and (got[count * stride:] == 0x5A).all() and (got_info[count:].view(np.uint32) == SENTINEL).all(), what
+    got_fields = field_rows(fields, count, stride, exp_fields.shape[1], what)
+    got_info = exp_info if info is None else records_head(hip.light_infos_to_numpy(info), count, what)
+    assert differing(got_fields, got_info, exp_fields, exp_info) is None, f"{what}: {differing(got_fields, got_info, exp_fields, exp_info)}"
 
 
-_CASES = {}
-
-
-def the_case(name, fmt):
+def build(name, fmt):
     """The world, a context that has it, the boxes the GPU is asked about and the harness's bytes for every call; shared by the tests."""
-    if (name, fmt) not in _CASES:
-        c = make_light_case(name, fmt)
-        c.pick = np.concatenate([np.arange(40), np.arange(SEEDED, len(c.boxes))])
-        c.calls = calls_for(c)
-        host = HostLight(harness(), c)
-        c.expected = {call[0]: host.call(c, call, c.pick) for call in c.calls}
-        host.close()
-        c.svo = make_context(c)
-        _CASES[name, fmt] = c
-    return _CASES[name, fmt]
+    c = make_light_case(name, fmt)
+    c.pick = np.concatenate([np.arange(40), np.arange(SEEDED, len(c.boxes))])
+    c.calls = calls_for(c)
+    host = HostLight(harness(), c)
+    c.expected = {call[0]: host.call(c, call, c.pick) for call in c.calls}
+    host.close()
+    c.svo = make_context(c)
+    return c
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _contexts():
-    yield
-    for c in _CASES.values():
-        c.svo.close()
-    _CASES.clear()
-
-
-@pytest.fixture(scope="module", params=LIGHT_CASES, ids=[f"{n}-{f}" for n, f in LIGHT_CASES])
-def case(request):
-    return the_case(*request.param)
+the_case, _contexts, case = shared_cases(build, LIGHT_CASES)
 
 
 def test_device_and_host_memory_give_the_harness_bytes(case):
@@ -118,7 +84,7 @@ def test_outputs_and_strides(case):
     svo.sync()
     assert f_only[1] is None and i_only[0] is None
     check_device(f_only[0], None, n, shape.padded, exp_fields, exp_info, "fields only")
-    assert hip.light_infos_to_numpy(i_only[1])[:n].tobytes() == exp_info.tobytes() and (hip.light_infos_to_numpy(i_only[1])[n:].view(np.uint32) == SENTINEL).all()
+    assert records_head(hip.light_infos_to_numpy(i_only[1]), n, "records only").tobytes() == exp_info.tobytes()
     check_device(both[0], both[1], n, wide, exp_fields, exp_info, "a stride larger than the box")
     check_device(one[0], one[1], 1, shape.padded, exp_fields[7:8], exp_info[7:8], "one box")
     check_device(none[0], none[1], 0, shape.padded, exp_fields[:0], exp_info[:0], "no box")
@@ -217,17 +183,7 @@ def test_a_section_with_its_margin_does_not_depend_on_the_box(case):
 def test_esvo_big():
     """The lantern in an ESVO context of 4 GiB, which selects the VX_SVO_ESVO_BIG build of the kernel: every call."""
     c = the_case("lantern", "esvo")
-    h = C.c_void_p()
-    rc = hip.lib().vx_create(c.svo_type, 1 << 32, 0, C.byref(h))
-    if rc == 3:  # VX_ERR_OUT_OF_MEMORY, from vx_create itself: the one reason to skip (as tests/test_blocks.py::test_esvo_big)
-        pytest.skip("vx_create: " + hip.lib().vx_last_error().decode())
-    assert rc == 0, hip.lib().vx_last_error()
-    svo = hip.Svo.__new__(hip.Svo)
-    svo._h, svo.svo_type = h, c.svo_type
-    try:
-        svo.set_materials(c.mats)
-        svo.set_textures(c.tex, 6)
-        svo.update_full(c.world)
+    with big_esvo_context(c) as svo:
         n, queued = len(c.pick), []
         for name, shape, props, flags, stride in c.calls:
             lo = torch_boxes(in_form(boxes_for(c, shape)[c.pick], stride)[0], stride, n)
@@ -235,8 +191,6 @@ def test_esvo_big():
         svo.sync()
         for (name, shape, *_), (_, (f, i)) in zip(c.calls, queued):
             check_device(f, i, n, shape.padded, *c.expected[name], name)
-    finally:
-        svo.close()
 
 
 def test_errors_leave_the_output_alone(case):
@@ -247,7 +201,6 @@ def test_errors_leave_the_output_alone(case):
     L, h, vp = hip.lib(), case.svo._h, C.c_void_p
     fields = np.full(2 * 4096 + 16, 0x5A, dtype=np.uint8)
     info = np.full(3, SENTINEL, dtype=np.uint32).repeat(4)
-    sentinel = fields.tobytes() + info.tobytes()
     d_fields, d_info = filled_fields(2, 4096), filled_info(2)
     v = np.tile(np.array([3, 3, 3], dtype=np.int32), 8)
     d_v = torch.from_numpy(v).cuda()
@@ -267,45 +220,34 @@ def test_errors_leave_the_output_alone(case):
     hb, db = v.ctypes.data, d_v.data_ptr()
     hf, hi, df, di = vp(fields.ctypes.data), vp(info.ctypes.data), vp(d_fields.data_ptr()), vp(d_info.data_ptr())
     H, D = hip.VX_MEM_HOST, hip.VX_MEM_DEVICE
-    for call, word in ((lambda: L.vx_light_boxes(None, hb, 12, 2, C.byref(shape()), H, hf, 0, hi), b"null context"),
-                       (lambda: L.vx_light_boxes(h, hb, 12, 2, C.byref(shape()), 3, hf, 0, hi), b"VX_MEM"),
-                       (lambda: L.vx_light_boxes(h, hb, 12, 2, None, H, hf, 0, hi), b"null shape"),
-                       (lambda: L.vx_light_boxes(h, None, 12, 2, C.byref(shape()), H, hf, 0, hi), b"null lo"),
-                       (lambda: L.vx_light_boxes(h, hb, 12, 2, C.byref(shape()), H, None, 0, None), b"fields and info"),
-                       (lambda: L.vx_light_boxes(h, hb, 8, 2, C.byref(shape()), H, hf, 0, hi), b"lo_stride"),
-                       (lambda: L.vx_light_boxes(h, hb + 2, 12, 2, C.byref(shape()), H, hf, 0, hi), b"lo must be aligned"),
-                       (lambda: L.vx_light_boxes(h, hb, 12, 2, C.byref(shape(size=u3(16, 0, 16))), H, hf, 0, hi), b"size"),
-                       (lambda: L.vx_light_boxes(h, hb, 12, 2, C.byref(shape(size=u3(16, 16, 49))), H, hf, 0, hi), b"size"),
-                       (lambda: L.vx_light_boxes(h, hb, 12, 2, C.byref(shape(flags=4)), H, hf, 0, hi), b"flags"),
-                       (lambda: L.vx_light_boxes(h, hb, 12, 2, C.byref(shape(flags=NO_SKY | NO_BLOCKS)), H, hf, 0, hi), b"flags"),
-                       (lambda: L.vx_light_boxes(h, hb, 12, 2, C.byref(shape(props_count=4097)), H, hf, 0, hi), b"props_count"),
-                       (lambda: L.vx_light_boxes(h, hb, 12, 2, C.byref(shape(props=None)), H, hf, 0, hi), b"null props"),
-                       (lambda: L.vx_light_boxes(h, hb, 12, 2, C.byref(shape(bad)), H, hf, 0, hi), b"props: a byte"),
-                       (lambda: L.vx_light_boxes(h, db, 12, 2, C.byref(shape(bad)), D, df, 0, di), b"props: a byte"),
-                       (lambda: L.vx_light_boxes(h, hb, 12, 2, C.byref(shape()), H, hf, 4080, hi), b"field_stride"),
-                       (lambda: L.vx_light_boxes(h, hb, 12, 2, C.byref(shape()), H, hf, 4104, hi), b"field_stride"),
-                       (lambda: L.vx_light_boxes(h, hb, 12, (1 << 24) + 1, C.byref(shape()), H, None, 0, hi), b"count exceeds"),
-                       (lambda: L.vx_light_boxes(h, hb, 12, 4097, C.byref(shape()), H, hf, 0, hi), b"count * field_stride"),
-                       (lambda: L.vx_light_boxes(h, db, 12, 2, C.byref(shape()), D, vp(d_fields.data_ptr() + 8), 0, di), b"fields in device memory"),
-                       (lambda: L.vx_light_boxes(h, db, 12, 2, C.byref(shape()), D, df, 0, vp(d_info.data_ptr() + 4)), b"info in device memory"),
-                       (lambda: L.vx_light_boxes(h, db + 1, 12, 2, C.byref(shape()), D, df, 0, di), b"lo must be aligned")):
-        rc = call()
-        assert rc == 1 and word in L.vx_last_error(), (rc, word, L.vx_last_error())
-        assert fields.tobytes() + info.tobytes() == sentinel
-    fresh = hip.Svo(case.svo_type, 1 << 20)
-    try:
-        assert L.vx_light_boxes(fresh._h, hb, 12, 2, C.byref(shape()), H, hf, 0, hi) == 6 and b"committed" in L.vx_last_error()
-        assert L.vx_light_boxes(fresh._h, db, 12, 2, C.byref(shape()), D, df, 0, di) == 6
-        assert fields.tobytes() + info.tobytes() == sentinel
-    finally:
-        fresh.close()
+    refusals = ((lambda: L.vx_light_boxes(None, hb, 12, 2, C.byref(shape()), H, hf, 0, hi), b"null context"),
+                (lambda: L.vx_light_boxes(h, hb, 12, 2, C.byref(shape()), 3, hf, 0, hi), b"VX_MEM"),
+                (lambda: L.vx_light_boxes(h, hb, 12, 2, None, H, hf, 0, hi), b"null shape"),
+                (lambda: L.vx_light_boxes(h, None, 12, 2, C.byref(shape()), H, hf, 0, hi), b"null lo"),
+                (lambda: L.vx_light_boxes(h, hb, 12, 2, C.byref(shape()), H, None, 0, None), b"fields and info"),
+                (lambda: L.vx_light_boxes(h, hb, 8, 2, C.byref(shape()), H, hf, 0, hi), b"lo_stride"),
+                (lambda: L.vx_light_boxes(h, hb + 2, 12, 2, C.byref(shape()), H, hf, 0, hi), b"lo must be aligned"),
+                (lambda: L.vx_light_boxes(h, hb, 12, 2, C.byref(shape(size=u3(16, 0, 16))), H, hf, 0, hi), b"size"),
+                (lambda: L.vx_light_boxes(h, hb, 12, 2, C.byref(shape(size=u3(16, 16, 49))), H, hf, 0, hi), b"size"),
+                (lambda: L.vx_light_boxes(h, hb, 12, 2, C.byref(shape(flags=4)), H, hf, 0, hi), b"flags"),
+                (lambda: L.vx_light_boxes(h, hb, 12, 2, C.byref(shape(flags=NO_SKY | NO_BLOCKS)), H, hf, 0, hi), b"flags"),
+                (lambda: L.vx_light_boxes(h, hb, 12, 2, C.byref(shape(props_count=4097)), H, hf, 0, hi), b"props_count"),
+                (lambda: L.vx_light_boxes(h, hb, 12, 2, C.byref(shape(props=None)), H, hf, 0, hi), b"null props"),
+                (lambda: L.vx_light_boxes(h, hb, 12, 2, C.byref(shape(bad)), H, hf, 0, hi), b"props: a byte"),
+                (lambda: L.vx_light_boxes(h, db, 12, 2, C.byref(shape(bad)), D, df, 0, di), b"props: a byte"),
+                (lambda: L.vx_light_boxes(h, hb, 12, 2, C.byref(shape()), H, hf, 4080, hi), b"field_stride"),
+                (lambda: L.vx_light_boxes(h, hb, 12, 2, C.byref(shape()), H, hf, 4104, hi), b"field_stride"),
+                (lambda: L.vx_light_boxes(h, hb, 12, (1 << 24) + 1, C.byref(shape()), H, None, 0, hi), b"count exceeds"),
+                (lambda: L.vx_light_boxes(h, hb, 12, 4097, C.byref(shape()), H, hf, 0, hi), b"count * field_stride"),
+                (lambda: L.vx_light_boxes(h, db, 12, 2, C.byref(shape()), D, vp(d_fields.data_ptr() + 8), 0, di), b"fields in device memory"),
+                (lambda: L.vx_light_boxes(h, db, 12, 2, C.byref(shape()), D, df, 0, vp(d_info.data_ptr() + 4)), b"info in device memory"),
+                (lambda: L.vx_light_boxes(h, db + 1, 12, 2, C.byref(shape()), D, df, 0, di), b"lo must be aligned"))
+    uncommitted = (lambda ctx: L.vx_light_boxes(ctx, hb, 12, 2, C.byref(shape()), H, hf, 0, hi), lambda ctx: L.vx_light_boxes(ctx, db, 12, 2, C.byref(shape()), D, df, 0, di))
     # count == 0: VX_OK whatever the rest is; nothing is read or written
-    assert L.vx_light_boxes(h, hb, 12, 0, C.byref(shape()), H, hf, 0, hi) == 0
-    assert L.vx_light_boxes(h, None, 0, 0, None, H, None, 0, None) == 0
-    assert L.vx_light_boxes(h, db, 12, 0, C.byref(shape(bad)), D, df, 0, di) == 0
-    case.svo.sync()
-    assert fields.tobytes() + info.tobytes() == sentinel
-    assert (d_fields.cpu().numpy() == 0x5A).all() and (d_info.cpu().numpy().view(np.uint32) == SENTINEL).all()
+    nothing_to_do = (lambda: L.vx_light_boxes(h, hb, 12, 0, C.byref(shape()), H, hf, 0, hi),
+                     lambda: L.vx_light_boxes(h, None, 0, 0, None, H, None, 0, None),
+                     lambda: L.vx_light_boxes(h, db, 12, 0, C.byref(shape(bad)), D, df, 0, di))
+    leaves_the_outputs_alone(case, [fields, info], [d_fields, d_info], refusals, uncommitted, nothing_to_do)
     # and the call still works: two boxes at (3, 3, 3), as numpy has them
     assert L.vx_light_boxes(h, hb, 12, 2, C.byref(shape()), H, hf, 0, hi) == 0
     exp_fields, exp_info = light_truth(case, v[:6].reshape(2, 3), (16, 16, 16), good)

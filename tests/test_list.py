@@ -2,6 +2,7 @@
 the host harness's records (tests/cpp/list_on_host.cpp: the same header on the host, which tests/test_list_on_host.py holds against the dense
 arrays) and against numpy directly where the world changes. Three worlds, both formats; every comparison is byte for byte. A case is
 computed once and left unchanged."""
+import contextlib
 import types
 
 import numpy as np
@@ -9,24 +10,16 @@ import pytest
 
 from batch_cases import _chunk_of
 from blocks_cases import REGIONS
+from gpu_harness import SENTINEL, big_esvo_context, leaves_the_outputs_alone, make_context, no_image_context
 from helpers import vra  # noqa: F401
 from list_cases import EXPOSED, FACES, FLAG_SETS, MAIN_BOXES, SCAN_CASES, HostLists, boxes_for, differing, expected_list, harness, make_scan_case
 from voxel_rs_amd import hip
 
 pytestmark = pytest.mark.gpu
-SENTINEL = 0x5A5A5A5A
-
-
-def make_context(c, capacity=None):
-    svo = hip.Svo(c.svo_type, c.world.size_in_bytes + (1 << 20) if capacity is None else capacity)
-    svo.set_materials(c.mats)
-    svo.set_textures(c.tex, 6)
-    svo.update_full(c.world)
-    return svo
 
 
 def filled(records):
-    """A device buffer of `records` records, every byte 0x5a."""
+    """A device buffer of exactly `records` records (a capacity is a part of this call), every byte 0x5a."""
     import torch
 
     return torch.full((records, 2), SENTINEL, dtype=torch.int32, device="cuda")
@@ -170,45 +163,23 @@ def test_ordered_between_commits(fmt):
 
 def test_esvo_big():
     """The glasshouse in an ESVO context of 4 GiB, which selects the VX_SVO_ESVO_BIG builds of the kernels: every box and flag set."""
-    import ctypes as C
-
     c = make_scan_case("glasshouse", "esvo")
-    h = C.c_void_p()
-    rc = hip.lib().vx_create(c.svo_type, 1 << 32, 0, C.byref(h))
-    if rc == 3:  # VX_ERR_OUT_OF_MEMORY, from vx_create itself: the one reason to skip (as tests/test_blocks.py::test_esvo_big)
-        pytest.skip("vx_create: " + hip.lib().vx_last_error().decode())
-    assert rc == 0, hip.lib().vx_last_error()
-    svo = hip.Svo.__new__(hip.Svo)
-    svo._h, svo.svo_type = h, c.svo_type
-    host = HostLists(harness(), c)
-    try:
-        svo.set_materials(c.mats)
-        svo.set_textures(c.tex, 6)
-        svo.update_full(c.world)
-        assert svo.get_stats()["capacity_bytes"] == 1 << 32
+    with big_esvo_context(c) as svo, contextlib.closing(HostLists(harness(), c)) as host:
         calls = [(name, lo, size, flags, host.list(lo, size, flags)[0]) for name, lo, size in boxes_for(c) for flags in FLAG_SETS]
         queued = [svo.list_region(lo, size, flags, out=filled(len(exp) + 1)) for _, lo, size, flags, exp in calls]
         svo.sync()
         for (name, lo, size, flags, exp), (dev, total) in zip(calls, queued):
             assert int(total.item()) == len(exp) and differing(as_records(dev)[:len(exp)], exp) is None, (name, flags)
             assert svo.list_region(lo, size, flags)[0].tobytes() == exp.tobytes(), (name, flags)
-    finally:
-        svo.close()
-        host.close()
 
 
 def test_without_a_traversal_image_the_bytes_are_the_same(case, monkeypatch):
     """A context created with VX_TRAVERSAL_IMAGE=0 (read when a context is created) answers with the same bytes."""
-    monkeypatch.setenv("VX_TRAVERSAL_IMAGE", "0")
-    svo = make_context(case)
-    try:
-        assert svo.image_info()["layout"] == 0  # (no traversal image in this context)
+    with no_image_context(case, monkeypatch) as svo:
         for name, lo, size in case.boxes:
             for flags in FLAG_SETS:
                 got, total = svo.list_region(lo, size, flags)
                 assert total == len(case.lists[name, flags]) and got.tobytes() == case.lists[name, flags].tobytes(), (name, flags)
-    finally:
-        svo.close()
 
 
 def test_errors_leave_the_output_alone(case):
@@ -221,33 +192,24 @@ def test_errors_leave_the_output_alone(case):
     out = np.full(8 * 8, 0x5a, dtype=np.uint8)
     total = np.full(4, 0x5a, dtype=np.uint8)
     d_out, d_total = filled(8), filled(1)
-    sentinel = out.tobytes(), total.tobytes()
+    sentinel = out.tobytes()
     lo3, size3 = (C.c_int32 * 3)(0, 0, 0), (C.c_uint32 * 3)(2, 2, 2)
     o, t = vp(out.ctypes.data), vp(total.ctypes.data)
-    for call, word in ((lambda: L.vx_list_region(h, None, C.byref(size3), 0, hip.VX_MEM_HOST, o, 8, t), b"null lo"),
-                       (lambda: L.vx_list_region(h, C.byref(lo3), None, 0, hip.VX_MEM_HOST, o, 8, t), b"null size"),
-                       (lambda: L.vx_list_region(h, C.byref(lo3), C.byref(size3), 4, hip.VX_MEM_HOST, o, 8, t), b"flags"),
-                       (lambda: L.vx_list_region(h, C.byref(lo3), C.byref(size3), 0, 3, o, 8, t), b"VX_MEM"),
-                       (lambda: L.vx_list_region(h, C.byref(lo3), C.byref(size3), 0, hip.VX_MEM_HOST, o, 8, None), b"null total"),
-                       (lambda: L.vx_list_region(h, C.byref(lo3), C.byref(size3), 0, hip.VX_MEM_HOST, None, 8, t), b"null out"),
-                       (lambda: L.vx_list_region(h, C.byref(lo3), C.byref((C.c_uint32 * 3)(256, 256, 257)), 0, hip.VX_MEM_HOST, o, 8, t), b"size.x"),
-                       (lambda: L.vx_list_region(h, C.byref(lo3), C.byref(size3), 0, hip.VX_MEM_DEVICE, vp(d_out.data_ptr() + 4), 7, vp(d_total.data_ptr())), b"out in device memory"),
-                       (lambda: L.vx_list_region(h, C.byref(lo3), C.byref(size3), 0, hip.VX_MEM_DEVICE, vp(d_out.data_ptr()), 8, vp(d_total.data_ptr() + 2)), b"total in device memory")):
-        rc = call()
-        assert rc == 1 and word in L.vx_last_error(), (rc, word, L.vx_last_error())
-        assert (out.tobytes(), total.tobytes()) == sentinel
-    fresh = hip.Svo(case.svo_type, 1 << 20)
-    try:
-        assert L.vx_list_region(fresh._h, C.byref(lo3), C.byref(size3), 0, hip.VX_MEM_HOST, o, 8, t) == 6 and b"committed" in L.vx_last_error()
-        assert (out.tobytes(), total.tobytes()) == sentinel
-    finally:
-        fresh.close()
-    case.svo.sync()
-    assert (d_out.cpu().numpy().view(np.uint32) == SENTINEL).all() and (d_total.cpu().numpy().view(np.uint32) == SENTINEL).all()
+    refusals = ((lambda: L.vx_list_region(h, None, C.byref(size3), 0, hip.VX_MEM_HOST, o, 8, t), b"null lo"),
+                (lambda: L.vx_list_region(h, C.byref(lo3), None, 0, hip.VX_MEM_HOST, o, 8, t), b"null size"),
+                (lambda: L.vx_list_region(h, C.byref(lo3), C.byref(size3), 4, hip.VX_MEM_HOST, o, 8, t), b"flags"),
+                (lambda: L.vx_list_region(h, C.byref(lo3), C.byref(size3), 0, 3, o, 8, t), b"VX_MEM"),
+                (lambda: L.vx_list_region(h, C.byref(lo3), C.byref(size3), 0, hip.VX_MEM_HOST, o, 8, None), b"null total"),
+                (lambda: L.vx_list_region(h, C.byref(lo3), C.byref(size3), 0, hip.VX_MEM_HOST, None, 8, t), b"null out"),
+                (lambda: L.vx_list_region(h, C.byref(lo3), C.byref((C.c_uint32 * 3)(256, 256, 257)), 0, hip.VX_MEM_HOST, o, 8, t), b"size.x"),
+                (lambda: L.vx_list_region(h, C.byref(lo3), C.byref(size3), 0, hip.VX_MEM_DEVICE, vp(d_out.data_ptr() + 4), 7, vp(d_total.data_ptr())), b"out in device memory"),
+                (lambda: L.vx_list_region(h, C.byref(lo3), C.byref(size3), 0, hip.VX_MEM_DEVICE, vp(d_out.data_ptr()), 8, vp(d_total.data_ptr() + 2)), b"total in device memory"))
+    uncommitted = (lambda ctx: L.vx_list_region(ctx, C.byref(lo3), C.byref(size3), 0, hip.VX_MEM_HOST, o, 8, t),)
+    leaves_the_outputs_alone(case, [out, total], [d_out, d_total], refusals, uncommitted)
     # any size component 0: total = 0, out not touched; with no total, nothing at all
     empty = (C.c_uint32 * 3)(2, 0, 2)
     assert L.vx_list_region(h, C.byref(lo3), C.byref(empty), 3, hip.VX_MEM_HOST, o, 8, t) == 0
-    assert out.tobytes() == sentinel[0] and total.view(np.uint32)[0] == 0
+    assert out.tobytes() == sentinel and total.view(np.uint32)[0] == 0
     assert L.vx_list_region(h, C.byref(lo3), C.byref(empty), 0, hip.VX_MEM_HOST, None, 8, None) == 0
     assert L.vx_list_region(h, C.byref(lo3), C.byref(empty), 0, hip.VX_MEM_DEVICE, vp(d_out.data_ptr()), 8, vp(d_total.data_ptr())) == 0
     case.svo.sync()

@@ -9,72 +9,49 @@ import pytest
 
 from batch_cases import _chunk_of
 from boxes_cases import Boxes
+from gpu_harness import (above_the_blocks, big_esvo_context, flying_entities, leaves_the_outputs_alone, make_context, no_image_context, records_head, sentinel_words,
+                         shared_cases)
 from helpers import vra  # noqa: F401
 from move_cases import (INVALID, SCAN_CASES, SEEDED, SKIN, YXZ, HostMoves, Moves, calls_for, differing, harness, make_moves, make_scan_case, moves_truth)
 from physics_cases import DT
 from voxel_rs_amd import hip
 
 pytestmark = pytest.mark.gpu
-SENTINEL = 0x5A5A5A5A
 
 
-def make_context(c, capacity=None):
-    svo = hip.Svo(c.svo_type, c.world.size_in_bytes + (1 << 20) if capacity is None else capacity)
-    svo.set_materials(c.mats)
-    svo.set_textures(c.tex, 6)
-    svo.update_full(c.world)
-    return svo
-
-
-def filled(records):
-    """A device buffer of `records` records, every byte 0x5a."""
-    import torch
-
-    return torch.full((records, 12), SENTINEL, dtype=torch.int32, device="cuda")
+def filled(count):
+    """A device buffer two records longer than a batch of `count`, every byte 0x5a."""
+    return sentinel_words(count, 12)
 
 
 def check_buffer(dev, exp, what):
     """A buffer two records longer than the batch: the records, then the untouched tail."""
-    got = hip.move_hits_to_numpy(dev)
-    assert differing(got[:len(exp)], exp) is None, f"{what}: {differing(got[:len(exp)], exp)}"
-    assert len(got) == len(exp) + 2 and (got[len(exp):].view(np.uint32) == SENTINEL).all(), what
+    raw = hip.move_hits_to_numpy(dev)
+    got = records_head(raw, len(exp), what)
+    assert differing(got, exp) is None, f"{what}: {differing(got, exp)}"
+    assert len(raw) == len(exp) + 2, what
 
 
 def shape_of(how):
     return dict(scale=how["scale"], skin=how["skin"], order=how["order"], only_value=how["only_value"])
 
 
-_CASES = {}
-
-
-def the_case(name, fmt):
+def build(name, fmt):
     """The world, a context that has it, its boxes and motions in every form and the harness's records of each; shared by the tests of this
     module."""
-    if (name, fmt) not in _CASES:
-        c = make_scan_case(name, fmt)
-        c.moves = make_moves(c)
-        c.calls = calls_for(c, c.moves)
-        host = HostMoves(harness(), c)
-        c.records = {call: host.records(mv, **how) for call, mv, how in c.calls}
-        host.close()
-        for a in c.records.values():
-            a.setflags(write=False)
-        c.svo = make_context(c)
-        _CASES[name, fmt] = c
-    return _CASES[name, fmt]
+    c = make_scan_case(name, fmt)
+    c.moves = make_moves(c)
+    c.calls = calls_for(c, c.moves)
+    host = HostMoves(harness(), c)
+    c.records = {call: host.records(mv, **how) for call, mv, how in c.calls}
+    host.close()
+    for a in c.records.values():
+        a.setflags(write=False)
+    c.svo = make_context(c)
+    return c
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _contexts():
-    yield
-    for c in _CASES.values():
-        c.svo.close()
-    _CASES.clear()
-
-
-@pytest.fixture(scope="module", params=SCAN_CASES, ids=[f"{n}-{f}" for n, f in SCAN_CASES])
-def case(request):
-    return the_case(*request.param)
+the_case, _contexts, case = shared_cases(build, SCAN_CASES)
 
 
 def test_device_and_host_memory_give_the_harness_records(case):
@@ -85,7 +62,7 @@ def test_device_and_host_memory_give_the_harness_records(case):
     queued = []
     for call, mv, how in case.calls:
         args = mv.torch_args()
-        queued.append((args, svo.move_boxes(**args, **shape_of(how), out=filled(len(mv) + 2))))
+        queued.append((args, svo.move_boxes(**args, **shape_of(how), out=filled(len(mv)))))
     svo.sync()
     for (call, mv, how), (_, dev) in zip(case.calls, queued):
         check_buffer(dev, case.records[call], f"{case.name}-{case.fmt} {call}")
@@ -106,7 +83,7 @@ def test_one_box(case):
     for i in picks:
         one = mv.picked(np.array([i]))
         args = one.torch_args()
-        queued.append((one, args, case.svo.move_boxes(**args, out=filled(3))))
+        queued.append((one, args, case.svo.move_boxes(**args, out=filled(1))))
     case.svo.sync()
     for i, (one, _, dev) in zip(picks, queued):
         check_buffer(dev, exp[i:i + 1], f"box {i}")
@@ -121,7 +98,7 @@ def test_a_grid_beyond_65535_workgroups(fmt):
     many = c.moves.picked(idx)
     exp = c.records["packed"][idx]
     args = many.torch_args()
-    dev = c.svo.move_boxes(**args, out=filled(len(many) + 2))
+    dev = c.svo.move_boxes(**args, out=filled(len(many)))
     c.svo.sync()
     check_buffer(dev, exp, "device")
     assert c.svo.move_boxes(**many.numpy_args()).tobytes() == exp.tobytes()
@@ -136,20 +113,11 @@ def test_behind_physics_step(fmt):
 
     c = the_case("glasshouse", fmt)
     rng = np.random.default_rng(91)
-    t = c.truth
-    top = np.where((t != 0).any(axis=1), t.shape[1] - 1 - (t[:, ::-1, :] != 0).argmax(axis=1), -1)  # [x][z]: the highest block
-    held = np.argwhere(top >= 0)
-    e = np.zeros(256, dtype=hip.ENTITY_DTYPE)
-    for k in range(len(e)):
-        x, z = (int(v) for v in held[rng.integers(len(held))])
-        e["position"][k] = c.info["lo"] + (x + 0.5, top[x, z] + 1 + rng.uniform(1.3, 1.5), z + 0.5)
-    e["velocity"] = np.stack([rng.uniform(-30, 30, len(e)), np.full(len(e), -40.0), rng.uniform(-30, 30, len(e))], axis=1)
-    e["aabb_offset"], e["aabb_extents"] = (-0.4, 0.0, -0.4), (0.8, 1.8, 0.8)
-    e["gravity"], e["max_fall_velocity"], e["flags"] = 20.0, 50.0, hip.ENTITY_FLYING
+    e = flying_entities(256, above_the_blocks(c, 256, rng, 1.3, 1.5), rng)  # 1.3 to 1.5 above their column's highest block
     d = torch.from_numpy(e.view(np.uint8).copy()).cuda()
     c.svo.physics_step(d, DT, 8)
     origin, extents, offset = hip.entity_boxes(d)
-    dev = c.svo.move_boxes(origin, extents, hip.entity_velocities(d), offset=offset, scale=float(DT), out=filled(len(e) + 2))  # no sync in between
+    dev = c.svo.move_boxes(origin, extents, hip.entity_velocities(d), offset=offset, scale=float(DT), out=filled(len(e)))  # no sync in between
     c.svo.sync()
     after = d.cpu().numpy().view(hip.ENTITY_DTYPE)
     assert (after["position"][:, 1] < e["position"][:, 1] - 1.0).all()
@@ -179,7 +147,7 @@ def test_ordered_between_commits(fmt):
         mv = Moves(boxes, np.concatenate([seeded.motion[:SEEDED], np.array([r[3] for r in extra], dtype=np.float32)]))
         args = mv.torch_args()
         old = moves_truth(c, mv)
-        first = svo.move_boxes(**args, out=filled(len(mv) + 2))  # enqueued; the commit below has to wait for it on the device
+        first = svo.move_boxes(**args, out=filled(len(mv)))  # enqueued; the commit below has to wait for it on the device
         blocks = c.info["blocks"].copy()
         assert blocks[6, 0, 24] != 0 and not blocks[16:19, 16:18, 16:18].any()
         blocks[17, 16:18, 16:18], blocks[6, 0, 24] = 12, 0  # a wall in the air, one block of the floor removed
@@ -188,7 +156,7 @@ def test_ordered_between_commits(fmt):
         svo.update_full(c.world)  # vx_commit_all
         changed = types.SimpleNamespace(name="glasshouse, changed", fmt=fmt, info=c.info, truth=blocks, size=c.size)  # (no LOD chunk here: the world shows its blocks)
         new = moves_truth(changed, mv)
-        second = svo.move_boxes(**args, out=filled(len(mv) + 2))  # enqueued behind the commit's upload
+        second = svo.move_boxes(**args, out=filled(len(mv)))  # enqueued behind the commit's upload
         svo.sync()
         assert old.tobytes() != new.tobytes()
         assert old["moved"][SEEDED][0] == 4 and old["contacts"][SEEDED] == 0 and new["moved"][SEEDED][0] == np.float32(1.75) - np.float32(SKIN)
@@ -203,43 +171,23 @@ def test_ordered_between_commits(fmt):
 
 def test_esvo_big():
     """The glasshouse in an ESVO context of 4 GiB, which selects the VX_SVO_ESVO_BIG build of the kernel: every call."""
-    import ctypes as C
-
     c = the_case("glasshouse", "esvo")
-    h = C.c_void_p()
-    rc = hip.lib().vx_create(c.svo_type, 1 << 32, 0, C.byref(h))
-    if rc == 3:  # VX_ERR_OUT_OF_MEMORY, from vx_create itself: the one reason to skip (as tests/test_boxes.py::test_esvo_big)
-        pytest.skip("vx_create: " + hip.lib().vx_last_error().decode())
-    assert rc == 0, hip.lib().vx_last_error()
-    svo = hip.Svo.__new__(hip.Svo)
-    svo._h, svo.svo_type = h, c.svo_type
-    try:
-        svo.set_materials(c.mats)
-        svo.set_textures(c.tex, 6)
-        svo.update_full(c.world)
-        assert svo.get_stats()["capacity_bytes"] == 1 << 32
+    with big_esvo_context(c) as svo:
         queued = []
         for call, mv, how in c.calls:
             args = mv.torch_args()
-            queued.append((args, svo.move_boxes(**args, **shape_of(how), out=filled(len(mv) + 2))))
+            queued.append((args, svo.move_boxes(**args, **shape_of(how), out=filled(len(mv)))))
         svo.sync()
         for (call, mv, how), (_, dev) in zip(c.calls, queued):
             check_buffer(dev, c.records[call], call)
             assert svo.move_boxes(**mv.numpy_args(), **shape_of(how)).tobytes() == c.records[call].tobytes(), call
-    finally:
-        svo.close()
 
 
 def test_without_a_traversal_image_the_bytes_are_the_same(case, monkeypatch):
     """A context created with VX_TRAVERSAL_IMAGE=0 (read when a context is created) answers with the same bytes."""
-    monkeypatch.setenv("VX_TRAVERSAL_IMAGE", "0")
-    svo = make_context(case)
-    try:
-        assert svo.image_info()["layout"] == 0  # (no traversal image in this context)
+    with no_image_context(case, monkeypatch) as svo:
         for call, mv, how in case.calls:
             assert svo.move_boxes(**mv.numpy_args(), **shape_of(how)).tobytes() == case.records[call].tobytes(), call
-    finally:
-        svo.close()
 
 
 def test_errors_leave_the_output_alone(case):
@@ -250,8 +198,7 @@ def test_errors_leave_the_output_alone(case):
 
     L, h, vp = hip.lib(), case.svo._h, C.c_void_p
     out = np.full(48 * 4, 0x5a, dtype=np.uint8)
-    sentinel = out.tobytes()
-    d_out = filled(4)
+    d_out = filled(2)
     v = np.tile(np.array([3.0, 3.0, 3.0], dtype=np.float32), 32)
     d_v = torch.from_numpy(v).cuda()
     assert d_out.data_ptr() % 16 == 0 and out.ctypes.data % 4 == 0
@@ -272,51 +219,41 @@ def test_errors_leave_the_output_alone(case):
     hm, dm = vp(hb + 288), vp(db + 288)
     o, do = vp(out.ctypes.data), vp(d_out.data_ptr())
     H, D = hip.VX_MEM_HOST, hip.VX_MEM_DEVICE
-    for call, word in ((lambda: L.vx_move_boxes(None, C.byref(batch(hb)), hm, 12, 2, shape(), H, o), b"null context"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, shape(), 3, o), b"VX_MEM"),
-                       (lambda: L.vx_move_boxes(h, None, hm, 12, 2, shape(), H, o), b"null boxes"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), None, 12, 2, shape(), H, o), b"null motion"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, None, H, o), b"null shape"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, shape(), H, None), b"null out"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(hb, origin=None)), hm, 12, 2, shape(), H, o), b"null origin"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(hb, extents=None)), hm, 12, 2, shape(), H, o), b"null extents"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(hb, origin_stride=8)), hm, 12, 2, shape(), H, o), b"origin_stride"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(hb, offset_stride=14)), hm, 12, 2, shape(), H, o), b"offset_stride"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(hb, extents_stride=8)), hm, 12, 2, shape(), H, o), b"extents_stride"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 8, 2, shape(), H, o), b"motion_stride"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 14, 2, shape(), H, o), b"motion_stride"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), vp(hb + 290), 12, 2, shape(), H, o), b"motion must be aligned"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(hb, origin=hb + 2)), hm, 12, 2, shape(), H, o), b"origin must be aligned"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, (1 << 24) + 1, shape(), H, o), b"count exceeds"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, shape(scale=float("nan")), H, o), b"scale"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, shape(scale=float("inf")), H, o), b"scale"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, shape(skin=-0.001), H, o), b"skin"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, shape(skin=1.5), H, o), b"skin"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, shape(skin=float("nan")), H, o), b"skin"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, shape(order=0), H, o), b"order"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, shape(order=0x23), H, o), b"order"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, shape(order=0x21 | 0x40), H, o), b"order"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, shape(flags=1), H, o), b"flags"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(db)), dm, 12, 2, shape(), D, vp(d_out.data_ptr() + 8)), b"out in device memory"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(db)), dm, 6, 2, shape(), D, do), b"motion_stride"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(db)), dm, 12, 2, shape(order=0x3f), D, do), b"order"),
-                       (lambda: L.vx_move_boxes(h, C.byref(batch(db, origin=db + 1)), dm, 12, 2, shape(), D, do), b"origin must be aligned")):
-        rc = call()
-        assert rc == 1 and word in L.vx_last_error(), (rc, word, L.vx_last_error())
-        assert out.tobytes() == sentinel
-    fresh = hip.Svo(case.svo_type, 1 << 20)
-    try:
-        assert L.vx_move_boxes(fresh._h, C.byref(batch(hb)), hm, 12, 2, shape(), H, o) == 6 and b"committed" in L.vx_last_error()
-        assert L.vx_move_boxes(fresh._h, C.byref(batch(db)), dm, 12, 2, shape(), D, do) == 6
-        assert out.tobytes() == sentinel
-    finally:
-        fresh.close()
+    refusals = ((lambda: L.vx_move_boxes(None, C.byref(batch(hb)), hm, 12, 2, shape(), H, o), b"null context"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, shape(), 3, o), b"VX_MEM"),
+                (lambda: L.vx_move_boxes(h, None, hm, 12, 2, shape(), H, o), b"null boxes"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), None, 12, 2, shape(), H, o), b"null motion"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, None, H, o), b"null shape"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, shape(), H, None), b"null out"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(hb, origin=None)), hm, 12, 2, shape(), H, o), b"null origin"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(hb, extents=None)), hm, 12, 2, shape(), H, o), b"null extents"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(hb, origin_stride=8)), hm, 12, 2, shape(), H, o), b"origin_stride"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(hb, offset_stride=14)), hm, 12, 2, shape(), H, o), b"offset_stride"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(hb, extents_stride=8)), hm, 12, 2, shape(), H, o), b"extents_stride"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 8, 2, shape(), H, o), b"motion_stride"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 14, 2, shape(), H, o), b"motion_stride"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), vp(hb + 290), 12, 2, shape(), H, o), b"motion must be aligned"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(hb, origin=hb + 2)), hm, 12, 2, shape(), H, o), b"origin must be aligned"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, (1 << 24) + 1, shape(), H, o), b"count exceeds"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, shape(scale=float("nan")), H, o), b"scale"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, shape(scale=float("inf")), H, o), b"scale"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, shape(skin=-0.001), H, o), b"skin"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, shape(skin=1.5), H, o), b"skin"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, shape(skin=float("nan")), H, o), b"skin"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, shape(order=0), H, o), b"order"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, shape(order=0x23), H, o), b"order"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, shape(order=0x21 | 0x40), H, o), b"order"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, shape(flags=1), H, o), b"flags"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(db)), dm, 12, 2, shape(), D, vp(d_out.data_ptr() + 8)), b"out in device memory"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(db)), dm, 6, 2, shape(), D, do), b"motion_stride"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(db)), dm, 12, 2, shape(order=0x3f), D, do), b"order"),
+                (lambda: L.vx_move_boxes(h, C.byref(batch(db, origin=db + 1)), dm, 12, 2, shape(), D, do), b"origin must be aligned"))
+    uncommitted = (lambda ctx: L.vx_move_boxes(ctx, C.byref(batch(hb)), hm, 12, 2, shape(), H, o), lambda ctx: L.vx_move_boxes(ctx, C.byref(batch(db)), dm, 12, 2, shape(), D, do))
     # count == 0: VX_OK whatever the rest is (a shape there must be); nothing is read or written
-    assert L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 0, shape(), H, o) == 0
-    assert L.vx_move_boxes(h, None, None, 0, 0, shape(), H, None) == 0
-    assert L.vx_move_boxes(h, C.byref(batch(db)), dm, 12, 0, shape(), D, do) == 0
-    case.svo.sync()
-    assert out.tobytes() == sentinel and (d_out.cpu().numpy().view(np.uint32) == SENTINEL).all()
+    nothing_to_do = (lambda: L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 0, shape(), H, o),
+                     lambda: L.vx_move_boxes(h, None, None, 0, 0, shape(), H, None),
+                     lambda: L.vx_move_boxes(h, C.byref(batch(db)), dm, 12, 0, shape(), D, do))
+    leaves_the_outputs_alone(case, [out], [d_out], refusals, uncommitted, nothing_to_do)
     # and the call still works: two boxes of 3^3 voxels at (3, 3, 3) moving by (3, 3, 3)
     two = Moves(Boxes(v[:6].reshape(2, 3), v[24:30].reshape(2, 3), v[48:54].reshape(2, 3), "packed"), v[72:78].reshape(2, 3))
     assert L.vx_move_boxes(h, C.byref(batch(hb)), hm, 12, 2, shape(), H, o) == 0

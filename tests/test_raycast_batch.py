@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_harness import to_device
 from helpers import orc, vra  # noqa: F401
 from physics_cases import DT, heightfield, place_entities
 from voxel_rs_amd import hip, host
@@ -133,12 +134,6 @@ def assert_is_picker_result(hits, res):
     miss = hits[~hit]
     assert (miss["dst"] == -1).all() and not miss["value"].any() and not miss["face_id"].any() and not miss["inside_voxel"].any() and not miss["pos"].any()
     assert not hits["_pad"].any()
-
-
-def to_device(array):
-    import torch
-
-    return torch.from_numpy(np.array(array, order="C")).cuda()  # (a copy: the shared arrays are read-only)
 
 
 def test_the_ray_set_holds_every_kind(case):

@@ -8,27 +8,12 @@ import pytest
 from batch_cases import TRANSLUCENT_IDS, _chunk_of, oracle_hits
 from scan_cases import (DIR_NAMES, DIRECTIONS, GAP, NONE, SCAN_CASES, TO_EDGE, axes_of, boxes_for, columns_truth, differing, first_of_region, harness,
                         host_scan_columns, host_scan_points, make_scan_case, points_truth)
+from gpu_harness import SENTINEL, big_esvo_context, leaves_the_outputs_alone, make_context, no_image_context, to_device
 from helpers import vra  # noqa: F401
 from voxel_rs_amd import hip
 
 pytestmark = pytest.mark.gpu
 COUNTS = [1, 63, 64, 65, None]  # None: the whole set
-SENTINEL = -7
-
-
-def make_context(c, world=None):
-    world = c.world if world is None else world
-    svo = hip.Svo(c.svo_type, world.size_in_bytes + (1 << 20))
-    svo.set_materials(c.mats)
-    svo.set_textures(c.tex, 6)
-    svo.update_full(world)
-    return svo
-
-
-def to_device(array):
-    import torch
-
-    return torch.from_numpy(np.array(array, order="C")).cuda()  # (a copy: the shared arrays are read-only)
 
 
 def host_records(c):
@@ -210,37 +195,19 @@ def test_against_rays():
 
 def test_without_a_traversal_image_the_bytes_are_the_same(case, monkeypatch):
     """A context created with VX_TRAVERSAL_IMAGE=0 (read when a context is created) answers with the same bytes."""
-    monkeypatch.setenv("VX_TRAVERSAL_IMAGE", "0")
-    svo = make_context(case)
-    try:
-        assert svo.image_info()["layout"] == 0  # (no traversal image in this context)
+    with no_image_context(case, monkeypatch) as svo:
         for d in DIRECTIONS:
             assert svo.scan_points(case.pts, d).tobytes() == case.exp_points[d].tobytes(), DIR_NAMES[d]
             for name, lo, size in case.boxes[d]:
                 assert svo.scan_columns(lo, size, d).tobytes() == case.exp_boxes[d, name].tobytes(), (DIR_NAMES[d], name)
-    finally:
-        svo.close()
 
 
 def test_esvo_big():
     """The glasshouse in an ESVO context of 4 GiB, which selects the VX_SVO_ESVO_BIG builds of both kernels (runtime.cpp: ctx->big depends on the
     capacity alone; the world is read through a 64-bit address with an explicit range check): points from device and host memory and the
     boxes, against the host harness's records."""
-    import ctypes as C
-
     c = make_scan_case("glasshouse", "esvo")
-    h = C.c_void_p()
-    rc = hip.lib().vx_create(c.svo_type, 1 << 32, 0, C.byref(h))
-    if rc == 3:  # VX_ERR_OUT_OF_MEMORY, from vx_create itself: the one reason to skip (as tests/test_blocks.py::test_esvo_big)
-        pytest.skip("vx_create: " + hip.lib().vx_last_error().decode())
-    assert rc == 0, hip.lib().vx_last_error()
-    svo = hip.Svo.__new__(hip.Svo)
-    svo._h, svo.svo_type = h, c.svo_type
-    try:
-        svo.set_materials(c.mats)
-        svo.set_textures(c.tex, 6)
-        svo.update_full(c.world)
-        assert svo.get_stats()["capacity_bytes"] == 1 << 32
+    with big_esvo_context(c) as svo:
         host_records(c)
         d_pts = to_device(c.pts)
         points = {d: svo.scan_points(d_pts, d) for d in DIRECTIONS}
@@ -251,8 +218,6 @@ def test_esvo_big():
             for name, lo, size in c.boxes[d]:
                 assert differing(hip.scan_hits_to_numpy(boxes[d, name]), c.exp_boxes[d, name]) is None, (DIR_NAMES[d], name)
                 assert svo.scan_columns(lo, size, d).tobytes() == c.exp_boxes[d, name].tobytes(), (DIR_NAMES[d], name)
-    finally:
-        svo.close()
 
 
 @pytest.mark.parametrize("fmt", ["esvo", "csvo"])
@@ -296,28 +261,19 @@ def test_errors_leave_the_output_alone(case):
     L, h, vp = hip.lib(), case.svo._h, C.c_void_p
     pts = np.array(case.pts[:8], order="C")
     out = np.full(8 * 16, 0x5a, dtype=np.uint8)
-    sentinel = out.tobytes()
     lo3, size3 = (C.c_int32 * 3)(0, 0, 0), (C.c_uint32 * 3)(2, 2, 2)
     o, p = vp(out.ctypes.data), vp(pts.ctypes.data)
-    for call, word in ((lambda: L.vx_scan_points(h, p, 8, 8, 2, 1, hip.VX_MEM_HOST, o), b"pos_stride"),
-                       (lambda: L.vx_scan_points(h, None, 12, 8, 2, 1, hip.VX_MEM_HOST, o), b"null pos"),
-                       (lambda: L.vx_scan_points(h, p, 12, 8, 6, 1, hip.VX_MEM_HOST, o), b"direction"),
-                       (lambda: L.vx_scan_points(h, p, 12, 8, 2, 0, hip.VX_MEM_HOST, o), b"reach"),
-                       (lambda: L.vx_scan_points(h, p, 12, 8, 2, 1, 3, o), b"VX_MEM"),
-                       (lambda: L.vx_scan_columns(h, None, C.byref(size3), 2, hip.VX_MEM_HOST, o), b"null lo"),
-                       (lambda: L.vx_scan_columns(h, C.byref(lo3), C.byref(size3), -1, hip.VX_MEM_HOST, o), b"direction"),
-                       (lambda: L.vx_scan_columns(h, C.byref(lo3), C.byref((C.c_uint32 * 3)(4097, 1, 4096)), 2, hip.VX_MEM_HOST, o), b"size"),
-                       (lambda: L.vx_scan_columns(h, C.byref(lo3), C.byref((C.c_uint32 * 3)(1, (1 << 24) + 1, 1)), 2, hip.VX_MEM_HOST, o), b"size")):
-        rc = call()
-        assert rc == 1 and word in L.vx_last_error(), (rc, word, L.vx_last_error())
-        assert out.tobytes() == sentinel
-    assert L.vx_scan_points(h, None, 12, 0, 2, 1, hip.VX_MEM_HOST, None) == 0
-    assert L.vx_scan_points(h, vp(pts.ctypes.data + 1), 5, 0, 0, 0, hip.VX_MEM_DEVICE, vp(out.ctypes.data + 3)) == 0  # (no points: nothing to refuse)
-    assert L.vx_scan_columns(h, C.byref(lo3), C.byref((C.c_uint32 * 3)(2, 0, 2)), 2, hip.VX_MEM_DEVICE, None) == 0
-    fresh = hip.Svo(case.svo_type, 1 << 20)
-    try:
-        assert L.vx_scan_points(fresh._h, p, 12, 8, 2, 1, hip.VX_MEM_HOST, o) == 6 and b"committed" in L.vx_last_error()
-        assert L.vx_scan_columns(fresh._h, C.byref(lo3), C.byref(size3), 2, hip.VX_MEM_HOST, o) == 6 and b"committed" in L.vx_last_error()
-        assert out.tobytes() == sentinel
-    finally:
-        fresh.close()
+    refusals = ((lambda: L.vx_scan_points(h, p, 8, 8, 2, 1, hip.VX_MEM_HOST, o), b"pos_stride"),
+                (lambda: L.vx_scan_points(h, None, 12, 8, 2, 1, hip.VX_MEM_HOST, o), b"null pos"),
+                (lambda: L.vx_scan_points(h, p, 12, 8, 6, 1, hip.VX_MEM_HOST, o), b"direction"),
+                (lambda: L.vx_scan_points(h, p, 12, 8, 2, 0, hip.VX_MEM_HOST, o), b"reach"),
+                (lambda: L.vx_scan_points(h, p, 12, 8, 2, 1, 3, o), b"VX_MEM"),
+                (lambda: L.vx_scan_columns(h, None, C.byref(size3), 2, hip.VX_MEM_HOST, o), b"null lo"),
+                (lambda: L.vx_scan_columns(h, C.byref(lo3), C.byref(size3), -1, hip.VX_MEM_HOST, o), b"direction"),
+                (lambda: L.vx_scan_columns(h, C.byref(lo3), C.byref((C.c_uint32 * 3)(4097, 1, 4096)), 2, hip.VX_MEM_HOST, o), b"size"),
+                (lambda: L.vx_scan_columns(h, C.byref(lo3), C.byref((C.c_uint32 * 3)(1, (1 << 24) + 1, 1)), 2, hip.VX_MEM_HOST, o), b"size"))
+    uncommitted = (lambda ctx: L.vx_scan_points(ctx, p, 12, 8, 2, 1, hip.VX_MEM_HOST, o), lambda ctx: L.vx_scan_columns(ctx, C.byref(lo3), C.byref(size3), 2, hip.VX_MEM_HOST, o))
+    nothing_to_do = (lambda: L.vx_scan_points(h, None, 12, 0, 2, 1, hip.VX_MEM_HOST, None),
+                     lambda: L.vx_scan_points(h, vp(pts.ctypes.data + 1), 5, 0, 0, 0, hip.VX_MEM_DEVICE, vp(out.ctypes.data + 3)),  # (no points: nothing to refuse)
+                     lambda: L.vx_scan_columns(h, C.byref(lo3), C.byref((C.c_uint32 * 3)(2, 0, 2)), 2, hip.VX_MEM_DEVICE, None))
+    leaves_the_outputs_alone(case, [out], [], refusals, uncommitted, nothing_to_do)

@@ -17,6 +17,7 @@ import stream_cases as sc
 import trace_cases as tc
 from batch_cases import first_difference
 from blocks_cases import harness, host_points, host_region
+from gpu_harness import to_device
 from helpers import vra  # noqa: F401
 from physics_cases import DT
 from voxel_rs_amd import hip, scenes
@@ -33,12 +34,6 @@ def make_context(fmt):
     svo.set_materials(scenes.synthetic_materials())  # (as stream_cases.Scene hands them to the oracle)
     svo.set_textures(scenes.synthetic_textures(), 6)
     return svo
-
-
-def to_device(array):
-    import torch
-
-    return torch.from_numpy(np.array(array, order="C")).cuda()  # (a copy: the shared arrays are read-only)
 
 
 class Queued:

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import trace_cases as tc
+from gpu_harness import to_device
 from helpers import orc, vra  # noqa: F401
 from physics_cases import DT, heightfield, place_entities
 from voxel_rs_amd import hip
@@ -40,12 +41,6 @@ def contexts():
     yield get
     for svo in made.values():
         svo.close()
-
-
-def to_device(array):
-    import torch
-
-    return torch.from_numpy(np.array(array, order="C")).cuda()  # (a copy: the shared arrays are read-only)
 
 
 def assert_pixels(fmt, got, exp_colors, what):

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 
 from batch_cases import _chunk_of
+from gpu_harness import (SENTINEL, big_esvo_context, field_rows, flying_entities, leaves_the_outputs_alone, make_context, records_head, sentinel_bytes, sentinel_words,
+                         shared_cases)
 from helpers import vra  # noqa: F401
 from physics_cases import DT
 from voxel_rs_amd import hip
@@ -16,29 +18,8 @@ from walk_cases import (INVALID, MAX_STEPS, NONE, SEEDED, SHAPE, STEPS_AT, STOP,
                         positions_for, steps_blocks, torch_positions, truth_for)
 
 pytestmark = pytest.mark.gpu
-SENTINEL = 0x5A5A5A5A
-TAIL = 48  # bytes behind the last field a call may write to, which it has to leave alone
-
-
-def make_context(c, capacity=None):
-    svo = hip.Svo(c.svo_type, c.world.size_in_bytes + (1 << 20) if capacity is None else capacity)
-    svo.set_materials(c.mats)
-    svo.set_textures(c.tex, 6)
-    svo.update_full(c.world)
-    return svo
-
-
-def filled_fields(count, stride):
-    import torch
-
-    return torch.full((count * stride + TAIL,), 0x5A, dtype=torch.uint8, device="cuda")
-
-
-def filled_words(count, width):
-    """`count` rows of `width` sentinel words and two rows more (records: width 8; paths: the capacity, or 4 where it is 0)."""
-    import torch
-
-    return torch.full((count + 2, width), SENTINEL, dtype=torch.int32, device="cuda")
+filled_fields = sentinel_bytes  # (count, stride): the fields at their stride and the tail
+filled_words = sentinel_words  # (count, width): records are 8 words wide; a path is its capacity, or 4 where that is 0
 
 
 def walk(svo, pos, goals, shape, max_steps, cap=0, flags=0, pass_value=0, **outputs):
@@ -50,52 +31,29 @@ def check_device(got, count, stride, cap, exp, what):
     the paths and two rows more. An output that is None was not asked for."""
     fields, info, paths = got
     exp_fields, exp_info, exp_paths = exp
-    got_info = exp_info if info is None else hip.walk_infos_to_numpy(info)
-    got_paths = exp_paths if paths is None else paths.cpu().numpy().view(np.uint32).reshape(-1)
-    rows = np.zeros((count, stride), dtype=np.uint8)
-    rows[:, :exp_fields.shape[1]] = exp_fields
-    raw = None
-    if fields is not None:
-        raw = fields.cpu().numpy()
-        rows = raw[:count * stride].reshape(count, stride)
-    written = exp_fields.shape[1]
-    d = differing((rows[:, :written], got_info[:count], got_paths[:count * cap].reshape(count, cap)), exp)
+    got_fields = exp_fields if fields is None else field_rows(fields, count, stride, exp_fields.shape[1], what)
+    got_info = exp_info if info is None else records_head(hip.walk_infos_to_numpy(info), count, what)
+    got_paths = exp_paths if paths is None else records_head(paths.reshape(-1), count * cap, what).view(np.uint32).reshape(count, cap)
+    d = differing((got_fields, got_info, got_paths), exp)
     assert d is None, f"{what}: {d}"
-    assert raw is None or ((rows[:, written:] == 0x5A).all() and (raw[count * stride:] == 0x5A).all()), what
-    assert (got_info[count:].view(np.uint32) == SENTINEL).all() and (got_paths[count * cap:] == SENTINEL).all(), what
 
 
-_CASES = {}
-
-
-def the_case(name, fmt):
+def build(name, fmt):
     """The world, a context that has it, the positions the GPU is asked about and the harness's bytes for every call; shared by the tests."""
-    if (name, fmt) not in _CASES:
-        c = make_walk_case(name, fmt)
-        c.pick = np.concatenate([np.arange(0, SEEDED, 3), np.arange(SEEDED, len(c.positions))])
-        c.calls = calls_for(c)
-        host = HostWalk(harness(), c)
-        c.expected = {call[0]: host.call(c, call, c.pick) for call in c.calls}
-        host.close()
-        for name, shape, max_steps, cap, flags, pass_value, _ in c.calls:  # (the harness's bytes are numpy's)
-            truth = tuple(a[c.pick] for a in truth_for(c, shape, max_steps, cap, flags, pass_value))
-            assert differing(c.expected[name], truth) is None, f"{name}: the harness differs from the dense truth: {differing(c.expected[name], truth)}"
-        c.svo = make_context(c)
-        _CASES[name, fmt] = c
-    return _CASES[name, fmt]
+    c = make_walk_case(name, fmt)
+    c.pick = np.concatenate([np.arange(0, SEEDED, 3), np.arange(SEEDED, len(c.positions))])
+    c.calls = calls_for(c)
+    host = HostWalk(harness(), c)
+    c.expected = {call[0]: host.call(c, call, c.pick) for call in c.calls}
+    host.close()
+    for call, shape, max_steps, cap, flags, pass_value, _ in c.calls:  # (the harness's bytes are numpy's)
+        truth = tuple(a[c.pick] for a in truth_for(c, shape, max_steps, cap, flags, pass_value))
+        assert differing(c.expected[call], truth) is None, f"{call}: the harness differs from the dense truth: {differing(c.expected[call], truth)}"
+    c.svo = make_context(c)
+    return c
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _contexts():
-    yield
-    for c in _CASES.values():
-        c.svo.close()
-    _CASES.clear()
-
-
-@pytest.fixture(scope="module", params=WALK_CASES, ids=[f"{n}-{f}" for n, f in WALK_CASES])
-def case(request):
-    return the_case(*request.param)
+the_case, _contexts, case = shared_cases(build, WALK_CASES)
 
 
 def queue_calls(svo, c):
@@ -211,11 +169,7 @@ def test_behind_physics_step(fmt):
 
     c = the_case("glasshouse", fmt)
     rng = np.random.default_rng(191)
-    e = np.zeros(256, dtype=hip.ENTITY_DTYPE)
-    e["position"] = rng.uniform((2.0, 2.0, 2.0), (30.0, 6.0, 30.0), (256, 3))
-    e["velocity"] = np.stack([rng.uniform(-30, 30, len(e)), np.full(len(e), -40.0), rng.uniform(-30, 30, len(e))], axis=1)
-    e["aabb_offset"], e["aabb_extents"] = (-0.4, 0.0, -0.4), (0.8, 1.8, 0.8)
-    e["gravity"], e["max_fall_velocity"], e["flags"] = 20.0, 50.0, hip.ENTITY_FLYING
+    e = flying_entities(256, rng.uniform((2.0, 2.0, 2.0), (30.0, 6.0, 30.0), (256, 3)), rng)
     goal = np.array([16.5, 1.5, 6.5], dtype=np.float32)
     shape, cap = SHAPE["17"], 252
     d = torch.from_numpy(e.view(np.uint8).copy()).cuda()
@@ -270,18 +224,7 @@ def test_a_commit_opens_a_wall(fmt):
 def test_esvo_big():
     """`steps` in an ESVO context of 4 GiB, which selects the VX_SVO_ESVO_BIG build of the kernel: every call."""
     c = the_case("steps", "esvo")
-    h = C.c_void_p()
-    rc = hip.lib().vx_create(c.svo_type, 1 << 32, 0, C.byref(h))
-    if rc == 3:  # VX_ERR_OUT_OF_MEMORY, from vx_create itself: the one reason to skip (as tests/test_blocks.py::test_esvo_big)
-        pytest.skip("vx_create: " + hip.lib().vx_last_error().decode())
-    assert rc == 0, hip.lib().vx_last_error()
-    svo = hip.Svo.__new__(hip.Svo)
-    svo._h, svo.svo_type = h, c.svo_type
-    try:
-        svo.set_materials(c.mats)
-        svo.set_textures(c.tex, 6)
-        svo.update_full(c.world)
-        assert svo.get_stats()["capacity_bytes"] == 1 << 32
+    with big_esvo_context(c) as svo:
         queued = queue_calls(svo, c)
         svo.sync()
         for (name, shape, max_steps, cap, *_), (_, _, _, _, got) in zip(c.calls, queued):
@@ -289,8 +232,6 @@ def test_esvo_big():
         name, shape, max_steps, cap, flags, pass_value, form = c.calls[-1]
         _, _, view, gview, _ = queued[-1]
         assert differing(walk(svo, view, gview, shape, max_steps, cap, flags, pass_value, paths=True), c.expected[name]) is None
-    finally:
-        svo.close()
 
 
 def test_errors_leave_the_output_alone(case):
@@ -302,7 +243,6 @@ def test_errors_leave_the_output_alone(case):
     fields = np.full(2 * 3472 + 16, 0x5A, dtype=np.uint8)
     paths = np.full(3 * 252, SENTINEL, dtype=np.uint32)
     info = np.full(3, SENTINEL, dtype=np.uint32).repeat(8)
-    sentinel = fields.tobytes() + paths.tobytes() + info.tobytes()
     d_fields, d_paths, d_info = filled_fields(2, 3472), filled_words(2, 252), filled_words(2, 8)
     v = np.tile(np.array([3.5, 3.5, 3.5], dtype=np.float32), 8)
     d_v = torch.from_numpy(v).cuda()
@@ -323,54 +263,43 @@ def test_errors_leave_the_output_alone(case):
     def host_call(ctx=h, pos=hb, pos_stride=12, goal=hb, goal_stride=12, count=2, s=None, memory=H, f=hf, field_stride=0, p=hp, i=hi, no_shape=False, **shape_fields):
         return L.vx_walk_points(ctx, pos, pos_stride, goal, goal_stride, count, None if no_shape else C.byref(shape(**shape_fields)), memory, f, field_stride, p, i)
 
-    for call, word in ((lambda: host_call(ctx=None), b"null context"),
-                       (lambda: host_call(memory=3), b"VX_MEM"),
-                       (lambda: host_call(no_shape=True), b"null shape"),
-                       (lambda: host_call(pos=None), b"null pos"),
-                       (lambda: host_call(f=None, p=None, i=None), b"fields, info and paths"),
-                       (lambda: host_call(goal=None), b"paths without goal"),
-                       (lambda: host_call(pos_stride=8), b"pos_stride"),
-                       (lambda: host_call(pos=hb + 2), b"pos must be aligned"),
-                       (lambda: host_call(goal_stride=8), b"goal_stride"),
-                       (lambda: host_call(goal=hb + 2), b"goal must be aligned"),
-                       (lambda: host_call(size=u3(17, 0, 17), seed_at=u3(8, 0, 8)), b"size"),
-                       (lambda: host_call(size=u3(17, 12, 33)), b"size"),
-                       (lambda: host_call(seed_at=u3(17, 6, 8)), b"seed_at"),
-                       (lambda: host_call(height=0), b"height"),
-                       (lambda: host_call(height=5), b"height"),
-                       (lambda: host_call(size=u3(17, 31, 17)), b"size[1] + height"),
-                       (lambda: host_call(max_steps=251), b"max_steps"),
-                       (lambda: host_call(climb=2), b"climb"),
-                       (lambda: host_call(drop=4), b"drop"),
-                       (lambda: host_call(path_capacity=6), b"path_capacity"),
-                       (lambda: host_call(path_capacity=256), b"path_capacity"),
-                       (lambda: host_call(flags=2), b"flags"),
-                       (lambda: host_call(field_stride=3456), b"field_stride"),
-                       (lambda: host_call(field_stride=3480), b"field_stride"),
-                       (lambda: host_call(count=(1 << 24) + 1, f=None, p=None), b"count exceeds"),
-                       (lambda: host_call(count=4833), b"count * field_stride"),
-                       (lambda: host_call(count=16645, f=None), b"count * path_capacity * 4"),
-                       (lambda: host_call(pos=db, goal=db, memory=D, f=vp(d_fields.data_ptr() + 8), p=dp, i=di), b"fields in device memory"),
-                       (lambda: host_call(pos=db, goal=db, memory=D, f=df, p=vp(d_paths.data_ptr() + 4), i=di), b"paths in device memory"),
-                       (lambda: host_call(pos=db, goal=db, memory=D, f=df, p=dp, i=vp(d_info.data_ptr() + 4)), b"info in device memory"),
-                       (lambda: host_call(pos=db + 1, goal=db, memory=D, f=df, p=dp, i=di), b"pos must be aligned")):
-        rc = call()
-        assert rc == 1 and word in L.vx_last_error(), (rc, word, L.vx_last_error())
-        assert fields.tobytes() + paths.tobytes() + info.tobytes() == sentinel
-    fresh = hip.Svo(case.svo_type, 1 << 20)
-    try:
-        assert host_call(ctx=fresh._h) == 6 and b"committed" in L.vx_last_error()
-        assert host_call(ctx=fresh._h, pos=db, goal=db, memory=D, f=df, p=dp, i=di) == 6
-        assert fields.tobytes() + paths.tobytes() + info.tobytes() == sentinel
-    finally:
-        fresh.close()
+    refusals = ((lambda: host_call(ctx=None), b"null context"),
+                (lambda: host_call(memory=3), b"VX_MEM"),
+                (lambda: host_call(no_shape=True), b"null shape"),
+                (lambda: host_call(pos=None), b"null pos"),
+                (lambda: host_call(f=None, p=None, i=None), b"fields, info and paths"),
+                (lambda: host_call(goal=None), b"paths without goal"),
+                (lambda: host_call(pos_stride=8), b"pos_stride"),
+                (lambda: host_call(pos=hb + 2), b"pos must be aligned"),
+                (lambda: host_call(goal_stride=8), b"goal_stride"),
+                (lambda: host_call(goal=hb + 2), b"goal must be aligned"),
+                (lambda: host_call(size=u3(17, 0, 17), seed_at=u3(8, 0, 8)), b"size"),
+                (lambda: host_call(size=u3(17, 12, 33)), b"size"),
+                (lambda: host_call(seed_at=u3(17, 6, 8)), b"seed_at"),
+                (lambda: host_call(height=0), b"height"),
+                (lambda: host_call(height=5), b"height"),
+                (lambda: host_call(size=u3(17, 31, 17)), b"size[1] + height"),
+                (lambda: host_call(max_steps=251), b"max_steps"),
+                (lambda: host_call(climb=2), b"climb"),
+                (lambda: host_call(drop=4), b"drop"),
+                (lambda: host_call(path_capacity=6), b"path_capacity"),
+                (lambda: host_call(path_capacity=256), b"path_capacity"),
+                (lambda: host_call(flags=2), b"flags"),
+                (lambda: host_call(field_stride=3456), b"field_stride"),
+                (lambda: host_call(field_stride=3480), b"field_stride"),
+                (lambda: host_call(count=(1 << 24) + 1, f=None, p=None), b"count exceeds"),
+                (lambda: host_call(count=4833), b"count * field_stride"),
+                (lambda: host_call(count=16645, f=None), b"count * path_capacity * 4"),
+                (lambda: host_call(pos=db, goal=db, memory=D, f=vp(d_fields.data_ptr() + 8), p=dp, i=di), b"fields in device memory"),
+                (lambda: host_call(pos=db, goal=db, memory=D, f=df, p=vp(d_paths.data_ptr() + 4), i=di), b"paths in device memory"),
+                (lambda: host_call(pos=db, goal=db, memory=D, f=df, p=dp, i=vp(d_info.data_ptr() + 4)), b"info in device memory"),
+                (lambda: host_call(pos=db + 1, goal=db, memory=D, f=df, p=dp, i=di), b"pos must be aligned"))
+    uncommitted = (lambda ctx: host_call(ctx=ctx), lambda ctx: host_call(ctx=ctx, pos=db, goal=db, memory=D, f=df, p=dp, i=di))
     # count == 0: VX_OK whatever the rest is; nothing is read or written
-    assert host_call(count=0) == 0
-    assert L.vx_walk_points(h, None, 0, None, 0, 0, None, H, None, 0, None, None) == 0
-    assert host_call(count=0, pos=db, goal=db, memory=D, f=df, p=dp, i=di) == 0
-    case.svo.sync()
-    assert fields.tobytes() + paths.tobytes() + info.tobytes() == sentinel
-    assert (d_fields.cpu().numpy() == 0x5A).all() and (d_paths.cpu().numpy().view(np.uint32) == SENTINEL).all() and (d_info.cpu().numpy().view(np.uint32) == SENTINEL).all()
+    nothing_to_do = (lambda: host_call(count=0),
+                     lambda: L.vx_walk_points(h, None, 0, None, 0, 0, None, H, None, 0, None, None),
+                     lambda: host_call(count=0, pos=db, goal=db, memory=D, f=df, p=dp, i=di))
+    leaves_the_outputs_alone(case, [fields, paths, info], [d_fields, d_paths, d_info], refusals, uncommitted, nothing_to_do)
     # and the call still works: two queries at (3.5, 3.5, 3.5) with themselves as the goal, as numpy has them
     assert host_call() == 0
     pts = v[:6].reshape(2, 3)
